@@ -34,7 +34,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')   # before the HIP runtime initialises (face_vijnana_yolov3_amd/__init__.py says why); inherited by the ranks
 
 IMAGE_SIZE = 416
 PER_GPU_BATCH = 40
@@ -85,6 +84,8 @@ def parse():
     ap.add_argument('--no-loader', action='store_true', help='skip the loader-inclusive measurement')
     ap.add_argument('--no-three-scale', action='store_true', help='skip the three-scale training measurement')
     ap.add_argument('--loader-steps', type=int, default=16)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)')
     return ap.parse_args()
 
 
@@ -537,6 +538,45 @@ def pmc_traffic(B, S):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 20          # elements sampled from each 40.64 M-element vector: 4 MB each, about 24 MB in all with the index
+
+
+def training_state(eng):
+    """Copy of everything a training step reads besides its batch: weights, BN moving state, Adam moments and step counters."""
+    eng.ensure_optimizer()
+    return dict(tensors=[t.clone() for t in (eng.params, eng.state, eng.m, eng.v)], iterations=eng.iterations,
+                bn_updates=eng.bn_updates)
+
+
+def restore_training_state(eng, snap):
+    for dst, src in zip((eng.params, eng.state, eng.m, eng.v), snap['tensors']):
+        dst.copy_(src)                             # on the stream the library launches on: ordered with the steps
+    eng.iterations, eng.bn_updates = snap['iterations'], snap['bn_updates']
+
+
+def dump_outputs(dirpath, eng, loss):
+    """What the last timed step handed back, as .npy files under `dirpath`: the loss it returned, the BN moving state it
+    updated (whole), and the parameters, gradients and Adam moments it updated, each sampled at one fixed, seeded set of
+    indices (param_sample_index.npy, float64; everything else float32).
+    The steps before the last one leave weights that differ from run to run: the weight-gradient and BN-statistics kernels
+    sum with float atomics, and the random-init network amplifies such rounding within a few steps.  So with
+    --dump-outputs the last timed step starts from the seeded initial training state (restored just before it, on the
+    device, inside the timed region: four 162 MB copies once per run), and its inputs are the same bits in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    n = eng.n_params
+    idx = np.sort(np.random.default_rng(20240601).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx_d = torch.from_numpy(idx).to(eng.dev)
+    torch.cuda.synchronize(eng.dev)
+    out = {'loss': loss.detach().reshape(-1).float().cpu().numpy(), 'bn_state': eng.state.cpu().numpy(),
+           'param_sample_index': idx.astype(np.float64)}
+    for name in ('params', 'grads', 'm', 'v'):
+        out[name + '_sample'] = getattr(eng, name)[idx_d].cpu().numpy()
+    for k, a in out.items():
+        np.save(os.path.join(dirpath, k + '.npy'), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks as FRESH child processes through
     torch.distributed.run (one process per GPU, RCCL rendezvous on 127.0.0.1) BEFORE this process makes any GPU call,
@@ -612,6 +652,8 @@ def main():
     def step():
         return trainer.train_on_batch(x, y, **HPS)
 
+    initial = training_state(eng) if args.dump_outputs else None   # the seeded start, before any step
+
     for _ in range(args.warmup):
         step()
     for _ in range(64):                             # comm_mode 'auto' (N > 1): the choice is made before the timed region
@@ -625,6 +667,8 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            restore_training_state(eng, initial)
         loss = step()
         marks[i + 1].record()
     trainer.barrier()
@@ -635,6 +679,9 @@ def main():
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = trainer.max_over_ranks(per_step[len(per_step) // 2] if len(per_step) % 2 else
                                        0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)   # before any later section steps the weights again
+    initial = None
 
     # ---- N > 1: what the communication costs (every rank measures, rank 0 reports all of them)
     multi = None

@@ -88,7 +88,7 @@ class DataParallelTrainer(object):
         #   'main' blocking all_reduce on the compute stream (no overlap).
         # Measured on one MI355X with a world-size-1 nccl group (no RCCL kernel runs there: the stream / event traffic alone;
         # tools/dp_overhead2.py, tools/dp_trace.py; plain step 52.2 ms): 'wg' 52.2, 'main' 52.2, 'pg' 55.6, 'side' the same as
-        # 'pg' (worse at high priority or with GPU_MAX_HW_QUEUES=8), independent of the number of buckets.
+        # 'pg' (worse at high priority or with 8 hardware queues), independent of the number of buckets.
         #   'auto' (default) starts in 'wg'.  With more than one rank the first steps of the job time 'wg', 'main' and 'pg' over
         #          AUTO_STEPS steps each (max over ranks, so every rank decides alike) and 'wg' is kept unless another mode is
         #          more than 1 % faster -- self.auto_report says what was measured.  At one rank there is nothing to overlap
@@ -222,7 +222,7 @@ class DataParallelTrainer(object):
                 self._auto_t0 = time.perf_counter()
                 if j > 0:
                     # A mode whose FIRST step is several times slower than a 'wg' step is not a candidate: drop it after that one step
-                    # instead of timing eight more (two ranks rehearsing on one GPU with GPU_MAX_HW_QUEUES=8: 'pg' took 17 s per
+                    # instead of timing eight more (two ranks rehearsing on one GPU with 8 hardware queues: 'pg' took 17 s per
                     # step -- more streams than hardware queues left for two processes).  Decided on max-reduced numbers: alike everywhere.
                     t = torch.tensor([(self._auto_t0 - self._auto_tw) * 1e3, self._auto_ms[0]], dtype=torch.float64, device=self.eng.dev)
                     dist.all_reduce(t, op=dist.ReduceOp.MAX)

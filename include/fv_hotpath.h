@@ -40,9 +40,9 @@ int fv_abi_version(void);
  * that Keras creates behind FaceDetector.__init__ (fd.py:312-382). */
 int fv_create(int device, void* stream, fv_ctx** out);
 /* (The context owns a low-priority side stream for the backward overlap.  The HIP runtime multiplexes a process's streams onto
- * GPU_MAX_HW_QUEUES hardware queues, default 4: a context created AFTER an RCCL communicator has existed in the process can find
+ * a fixed number of hardware queues, 4 by default: a context created AFTER an RCCL communicator has existed in the process can find
  * its side stream sharing a hardware queue with the compute stream, which serialises the overlap -- 30 - 40 % on a training step.
- * Create contexts before communicators, or run the process with GPU_MAX_HW_QUEUES=8; the Python host package sets that default.
+ * Create contexts before communicators.
  * DESIGN 6.) */
 void fv_destroy(fv_ctx* ctx);
 const char* fv_last_error(const fv_ctx* ctx);
