@@ -98,8 +98,8 @@ class Engine(object):
     @staticmethod
     def max_infer_batch(image_size):
         """Largest batch one fv_forward_infer call takes at this image size: the kernels address a tensor through one buffer descriptor
-        (2 GiB, 2^29 floats) and the largest activation is the first layer's batch x S x S x 32 output."""
-        return (1 << 29) // (32 * int(image_size) * int(image_size))
+        (2 GiB, 2^29 floats) and the largest activation, the first layer's batch x S x S x 32 output, must stay below 2^29."""
+        return ((1 << 29) - 1) // (32 * int(image_size) * int(image_size))
 
     # ------------------------------------------------------------------ predict (fd.py:899)
     def predict_device(self, x):

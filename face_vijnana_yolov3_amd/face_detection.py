@@ -68,7 +68,7 @@ def default_loader_threads():
 
 def default_eval_batch(image_size):
     """hps['eval_batch_size'] when the configuration does not set it: 48 images per forward where the first layer's output fits
-    one 2 GiB buffer descriptor (batch x image_size^2 x 32 floats <= 2^29 elements: up to 416 and beyond), else the largest
+    one 2 GiB buffer descriptor (batch x image_size^2 x 32 floats < 2^29 elements: up to 416 and beyond), else the largest
     multiple of 8 that does (608: 40).  48, not 32: the loop is bound by the device (bench.py `test_loop`), and the 128-row tile
     rounds of the 26^2 / 52^2 layers come out whole at multiples of 24 images (device only, network + decode/NMS at 416^2:
     batch 24 / 32 / 40 / 48 / 64 = 2519 / 2360 / 2510 / 2610 / 2565 img/s, tools/eval_batch_probe.py)."""

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from ._lib import BUCKET_FN, Context, LayerDesc, lib, ptr
+from .engine import Engine
 
 COCO_ANCHORS = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]]  # yd.py:560
 
@@ -89,7 +90,7 @@ class Yolov3(object):
     def predict_device(self, x):
         x = torch.as_tensor(x).to(device=self.dev, dtype=torch.float32).contiguous()
         B, S = x.shape[0], x.shape[1]
-        cap = (1 << 29) // (32 * S * S)              # one buffer descriptor per tensor: see Engine.max_infer_batch
+        cap = Engine.max_infer_batch(S)              # one buffer descriptor per tensor
         if B > cap >= 1:
             step = cap // 8 * 8 if cap >= 8 else cap
             parts = [self.predict_device(x[i:i + step]) for i in range(0, B, step)]

@@ -213,14 +213,19 @@ def test_default_loader_threads_respects_affinity_and_quota():
     assert fdm.default_loader_threads() == max(4, min(32, n))
 
 
-def test_default_eval_batch_fits_one_buffer_descriptor():
+def test_default_eval_batch_stays_below_one_buffer_descriptor():
     """evaluate()/test() batch when hps.eval_batch_size is absent: 48 where the first layer's output (batch x S^2 x 32 floats) stays
-    within the 2^29 elements a 2 GiB buffer descriptor addresses (fv_forward_infer refuses more), the largest multiple of 8 below
+    below the 2^29 elements a 2 GiB buffer descriptor addresses (fv_forward_infer refuses more), the largest multiple of 8 below
     that otherwise."""
+    from face_vijnana_yolov3_amd.engine import Engine
     from face_vijnana_yolov3_amd.face_detection import default_eval_batch
     assert default_eval_batch(416) == 48 and default_eval_batch(320) == 48
     assert default_eval_batch(608) == 40
     for s in range(96, 4097, 32):
         b = default_eval_batch(s)
-        assert b >= 1 and (b == 1 or b * s * s * 32 <= 1 << 29)
-        assert b == 48 or (b + 8) * s * s * 32 > 1 << 29 or b < 8
+        assert b >= 1 and (b == 1 or b * s * s * 32 < 1 << 29)
+        assert b == 48 or (b + 8) * s * s * 32 >= 1 << 29 or b < 8
+        cap = Engine.max_infer_batch(s)
+        assert cap * s * s * 32 < 1 << 29 <= (cap + 1) * s * s * 32
+    # 16 x 1024^2 x 32 is exactly 2^29 elements: one image too many for the strict check of the C entry points
+    assert Engine.max_infer_batch(1024) == 15 and default_eval_batch(1024) == 8

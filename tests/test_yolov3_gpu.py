@@ -247,6 +247,35 @@ def test_three_scale_train_step_matches_oracle(out_ch, B, S):
     assert not bad, '%d tensors off: %s' % (len(bad), '; '.join(bad[:6]))
 
 
+def test_three_scale_side_stream_overlap_equals_serial():
+    """fv_set_option("overlap") in fv_yolov3_train_step: the weight-gradients on the side stream vs everything on one stream --
+    the same bucket protocol (contiguous ranges in descending offset order that cover the gradient vector exactly), the same loss
+    and the same gradients up to the float-atomic summation order inside dW (tests/test_net_gpu.py has the FaceDetector's)."""
+    from face_vijnana_yolov3_amd.yolov3 import Yolov3
+    out_ch, B, S = 18, 2, 64
+    model = Yolov3(0, out_channels=out_ch)
+    p64, s64, x, tg = _train_setup(out_ch, B, S, 31)
+    res = []
+    try:
+        for on in (True, False):
+            model.ctx.set_overlap(on)
+            model.set_params(p64.float(), s64.float())
+            buckets = []
+            loss = model.forward_backward(x.float(), [t.float() for t in tg], on_bucket=lambda o, c: buckets.append((o, c)))
+            torch.cuda.synchronize()
+            res.append((loss.item(), model.grads.clone(), list(buckets)))
+    finally:
+        model.ctx.set_overlap(True)
+    n = model.grads.numel()
+    assert res[0][2] == res[1][2]
+    ranges = res[0][2]
+    assert ranges[0][0] + ranges[0][1] == n and ranges[-1][0] == 0
+    assert all(hi[0] == lo[0] + lo[1] for hi, lo in zip(ranges, ranges[1:]))
+    assert abs(res[0][0] - res[1][0]) <= 1e-6 * abs(res[1][0])
+    d = (res[0][1] - res[1][1]).abs().max().item()
+    assert d <= 1e-5 * res[1][1].abs().max().item() + 1e-9, d
+
+
 def test_three_scale_training_reduces_the_loss():
     from face_vijnana_yolov3_amd.yolov3 import Yolov3
     model = Yolov3(0, out_channels=27)
