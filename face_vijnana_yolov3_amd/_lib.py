@@ -114,6 +114,12 @@ def _declare(L):
                                            vp, vp, vp, vp]),
         'fv_yolo_decode_nms': (i32, [vp, vp, vp, vp, i32, i32, ctypes.POINTER(f32), f32, f64, i32, i32, i32, i32, i32,
                                      vp, vp, vp, vp]),
+        'fv_fid_param_count': (i64, [i32]),
+        'fv_fid_workspace_bytes': (sz, [i32, i32, i32]),
+        'fv_fid_extract': (i32, [vp, vp, vp, vp, i32, i32, vp, sz, vp]),
+        'fv_fid_train_step': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+        'fv_fid_dense_partial_floats': (i64, [i32, i64]),
+        'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

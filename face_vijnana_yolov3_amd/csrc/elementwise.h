@@ -12,7 +12,9 @@ int fv_ew_bn_act(fv_ctx* ctx, const float* z, const float* scale, const float* s
 int fv_ew_bn_bwd_chunks(long long rows, int C);
 int fv_ew_bn_bwd(fv_ctx* ctx, const float* g, const float* z, const float* scale, const float* shift, const float* mean,
                  const float* invstd, long long rows, int C, float leaky, float* pdb, float* pdg, float* dbeta, float* dgamma,
-                 float* dz, double* slots = nullptr, int nslot = 0, bool reduced = false);
+                 float* dz, double* slots = nullptr, int nslot = 0, bool reduced = false, bool accumulate = false);
+// accumulate: d-beta / d-gamma are ADDED to what dbeta / dgamma hold (a BN layer shared by several towers of one step, net_fid.hip)
+// instead of stored
 // part != NULL: multi-workgroup form with fv_ew_mse_scratch_floats() floats of scratch (8-byte aligned); NULL: one workgroup
 int fv_ew_mse(fv_ctx* ctx, const float* yp, const float* yt, int rows, int C, int Cpad, float* loss, float* dy, float* dbias,
               double* part = nullptr, double grad_weight = 1.0);

@@ -223,7 +223,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 
 // pass 1b: reduce the chunk partials in double -> dbeta, dgamma (written into the flat grad vector)
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ pdb, const float* __restrict__ pdg,
-                                                               int chunks, int C, float* __restrict__ dbeta, float* __restrict__ dgamma) {
+                                                               int chunks, int C, float* __restrict__ dbeta, float* __restrict__ dgamma,
+                                                               int accumulate) {
     __shared__ double s1[128][9], s2[128][9];
     const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
     const int c = blockIdx.x * 8 + cl;
@@ -238,7 +239,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
         if (rl < st) { s1[rl][cl] += s1[rl + st][cl]; s2[rl][cl] += s2[rl + st][cl]; }
         __syncthreads();
     }
-    if (rl == 0 && c < C) { dbeta[c] = (float)s1[0][cl]; dgamma[c] = (float)s2[0][cl]; }
+    if (rl == 0 && c < C) {
+        if (accumulate) { dbeta[c] += (float)s1[0][cl]; dgamma[c] += (float)s2[0][cl]; }
+        else { dbeta[c] = (float)s1[0][cl]; dgamma[c] = (float)s2[0][cl]; }
+    }
 }
 
 // pass 2: dz = scale * (gy - dbeta/M - xhat * dgamma/M)
@@ -275,13 +279,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_slots_kernel(const float4* _
                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                  const double* __restrict__ slots, int nslot,
                                                                  float* __restrict__ dbeta, float* __restrict__ dgamma,
-                                                                 float inv_count, long long n4, int C, float leaky, float4* __restrict__ dz) {
+                                                                 float inv_count, long long n4, int C, float leaky, float4* __restrict__ dz,
+                                                                 int accumulate) {
     __shared__ __attribute__((aligned(16))) float s_db[1024], s_dg[1024];
     __shared__ double s_part[2][256];
     const int tid = threadIdx.x;
     auto finish = [&](int c, double a, double b) {
         s_db[c] = (float)a; s_dg[c] = (float)b;
-        if (blockIdx.x == 0) { dbeta[c] = (float)a; dgamma[c] = (float)b; }
+        if (blockIdx.x == 0) {
+            if (accumulate) { dbeta[c] += (float)a; dgamma[c] += (float)b; }
+            else { dbeta[c] = (float)a; dgamma[c] = (float)b; }
+        }
     };
     if (C >= 256) {
         for (int c = tid; c < C; c += 256) {
@@ -666,7 +674,7 @@ int fv_ew_bn_bwd_chunks(long long rows, int C) {
 
 int fv_ew_bn_bwd(fv_ctx* ctx, const float* g, const float* z, const float* scale, const float* shift, const float* mean,
                  const float* invstd, long long rows, int C, float leaky, float* pdb, float* pdg, float* dbeta, float* dgamma,
-                 float* dz, double* slots, int nslot, bool reduced) {
+                 float* dz, double* slots, int nslot, bool reduced, bool accumulate) {
     FV_REQUIRE(ctx, C % 4 == 0, "bn_bwd: C must be a multiple of 4");
     FV_REQUIRE(ctx, !reduced || slots, "bn_bwd: a reduction done elsewhere must have gone to accumulator slots");
     FV_REQUIRE(ctx, !slots || (nslot >= 1 && C <= 1024 && (C >= 256 || 256 % C == 0)), "bn_bwd: accumulator slots need C <= 1024 dividing or divided by 256");
@@ -684,11 +692,12 @@ int fv_ew_bn_bwd(fv_ctx* ctx, const float* g, const float* z, const float* scale
         FvProfScope ps(ctx, "bn_bwd_apply_slots_kernel", 0.0, 12.0 * rows * C);
         hipLaunchKernelGGL(bn_bwd_apply_slots_kernel, dim3(grid_for(n4s, 256, 256 * 4)), dim3(256), 0, ctx->stream, (const float4*)g,
                            (const float4*)z, scale, shift, mean, invstd, slots, nslot, dbeta, dgamma, (float)(1.0 / (double)rows), n4s, C,
-                           leaky, (float4*)dz);
+                           leaky, (float4*)dz, (int)accumulate);
         FV_LAUNCH_CHECK(ctx);
         return FV_OK;
     }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 7) / 8), dim3(1024), 0, ctx->stream, pdb, pdg, chunks, C, dbeta, dgamma);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 7) / 8), dim3(1024), 0, ctx->stream, pdb, pdg, chunks, C, dbeta, dgamma,
+                       (int)accumulate);
     FV_LAUNCH_CHECK(ctx);
     long long n4 = rows * C / 4;
     FvProfScope ps(ctx, "bn_bwd_apply_kernel", 0.0, 12.0 * rows * C);

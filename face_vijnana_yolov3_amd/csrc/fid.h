@@ -1,0 +1,24 @@
+// Internal launch interface of fid.hip: the FaceIdentifier's head (reference face_identification.py:318-345): Flatten ->
+// Dense(64, relu) -> l2_normalize, the triplet loss (fi.py:72-76) and the dense layer's two gradients.  All fp32 FMA on the vector
+// units, every sum in a fixed order (no atomics): the same rows give the same bits, whatever else is in the batch.
+#pragma once
+#include "common.h"
+
+constexpr int FID_DIM = 64;    // nn_arch.dense1_dim; the loss slices 0:64 / 64:128 / 128:192 are hard-coded in the reference
+constexpr int FID_KC = 256;    // F per forward partial: fixed, so a row's summation order does not depend on the batch
+
+// Rows of the dense layer's input (or of its data-gradient): row m lies at p[m / per] + (m % per) * F -- the three towers' feature
+// maps [per][F] read (written) in place, tower-major.
+struct FidRows { float* p[3]; int per; };
+
+inline long long fv_fid_chunks(long long F) { return F / FID_KC; }
+// part [F / FID_KC][M][64]: per-chunk partial products of X . W
+int fv_fid_dense_fwd(fv_ctx* ctx, FidRows X, int M, long long F, const float* W, float* part);
+// u = l2_normalize(relu(sum of the partials in chunk order + bias)); pre (may be NULL) keeps the pre-activation
+int fv_fid_dense_finish(fv_ctx* ctx, const float* part, long long chunks, int M, const float* bias, float* pre, float* u);
+// triplet loss over B triplets (rows b, B + b, 2B + b of pre / u); dE [3B][64] = dL / d pre, dbias [64] = its column sums
+int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias);
+// dX = dE . W^T, written (not added) into the rows of dX
+int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const float* W, FidRows dX);
+// dW [F][64] = X^T . dE over the M rows, stored
+int fv_fid_dense_wgrad(fv_ctx* ctx, FidRows X, const float* dE, int M, long long F, float* dW);

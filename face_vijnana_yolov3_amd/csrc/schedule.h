@@ -213,6 +213,7 @@ int kept_tensor(const Kept& k, const char* base, const fv_layer_desc& d, int l, 
 struct Train {
     fv_ctx* ctx; const Layers& L; const Kept& k; int B, S;
     const float* params; float* bn_state; float* grads;
+    bool accumulate_bn = false;   // d-beta / d-gamma are added to `grads` (towers sharing one BN layer), not stored
 };
 
 // Training forward of BN layer l: the conv adds its column sums to the fp64 accumulator slots and the normalise pass reduces
@@ -325,7 +326,7 @@ int bn_layer_backward(WgradPipe& pipe, int l, const float* g, bool reduced, cons
     float* dz = pipe.dz[pipe.slot];
     if (int rc = fv_ew_bn_bwd(t.ctx, g, t.k.z[l], t.k.scale[l], t.k.shift[l], t.k.mean[l], t.k.invstd[l], rows, d.cout, LEAKY, nullptr,
                               nullptr, t.grads + d.beta_off, t.grads + d.gamma_off, dz, t.k.bslots[l], fv_ew_bn_stat_slots(d.cout),
-                              reduced)) return rc;
+                              reduced, t.accumulate_bn)) return rc;
     if (int rc = pipe.submit(l, xin, dz, d.cout)) return rc;
     if (!g_out) return FV_OK;
     FvBnRed b;
@@ -334,8 +335,10 @@ int bn_layer_backward(WgradPipe& pipe, int l, const float* g, bool reduced, cons
 
 // Backward through the Darknet-53 base L[0, nb) from the gradient of its output in g[0]; g[1] holds the kept block gradient of a
 // residual pair.  addend_at[l] (when given): a gradient of a(l) that arrived by another route, added where dgrad(l + 1) forms
-// the gradient of a(l).
-int base_backward(WgradPipe& pipe, int nb, const float* x, float* const g[2], const std::vector<const float*>& addend_at) {
+// the gradient of a(l).  top_reduced: the top layer's d-beta / d-gamma were reduced by the launch that formed g[0] (a conv
+// data-gradient with FV_EPI_BNRED); false: its BN-backward reduces them itself (g[0] came from elsewhere, net_fid.hip's dense layer).
+int base_backward(WgradPipe& pipe, int nb, const float* x, float* const g[2], const std::vector<const float*>& addend_at,
+                  bool top_reduced = true) {
     const Train& t = pipe.t;
     int ig = 0, ires = -1;
     for (int l = nb - 1; l > 0; --l) {
@@ -345,7 +348,7 @@ int base_backward(WgradPipe& pipe, int nb, const float* x, float* const g[2], co
         const int iout = (ig == ires) ? 1 - ig : ig;
         const float* addend = d.role == 1 ? g[ires] : nullptr;
         if (!addend_at.empty() && addend_at[l - 1]) addend = addend_at[l - 1];
-        if (int rc = bn_layer_backward(pipe, l, g[ig], true, t.k.a[l - 1], g[iout], addend, l - 1)) return rc;
+        if (int rc = bn_layer_backward(pipe, l, g[ig], l < nb - 1 || top_reduced, t.k.a[l - 1], g[iout], addend, l - 1)) return rc;
         ig = iout;
         if (d.role == 1) ires = -1;
     }

@@ -1,0 +1,423 @@
+"""FaceIdentifier: facial IDs from the Darknet-53 base, trained with a triplet loss.
+
+Port of the reference's `src/space/face_identification.py` (fi.py): the model (fi.py:318-345), the facial-ID extractor
+(`_make_fid_extractor`, fi.py:378-395), `train` (fi.py:616-643) over its two triplet sequences (fi.py:1490-1601 and the VGGFace2
+variant) and `main` (fi.py:1715-1760) for the modes implemented here.  The hot path is the C ABI (fv_fid_extract, fv_fid_train_step,
+fv_adam_step); this module holds the weights and drives it.  Not ported: create_db_fi / save_extracted_face (face cropping),
+make_facial_ids_db, register_facial_ids, evaluate, test and the reconstruction model.  Differences, documented in DESIGN.md:
+the BN moving-statistics update order of the three towers (a -> p -> n) and a zero gradient at a triplet distance of exactly 0."""
+import json
+import os
+import pickle
+import platform
+import time
+from random import shuffle
+
+import numpy as np
+import torch
+
+from ._lib import Context, FvError, lib, ptr
+
+ALPHA = 0.2                     # fi.py:66
+DENSE1_DIM = 64                 # the loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76)
+NUM_BASE_LAYERS = 52
+RESOURCE_TYPE_UCCS = 'uccs'
+RESOURCE_TYPE_VGGFACE2 = 'vggface2'
+
+
+def base_layers():
+    from .engine import layer_table
+    return layer_table()[:NUM_BASE_LAYERS]
+
+
+def feature_size(image_size):
+    """Flatten() length of the base output: (S/32)^2 * 1024 (173 056 at 416)."""
+    return (int(image_size) // 32) ** 2 * 1024
+
+
+def dense_offsets(image_size):
+    """(kernel offset, bias offset) in the flat parameter vector: the dense kernel [F][64] follows the 52 base layers."""
+    d = base_layers()[-1]
+    k = d['beta_off'] + d['cout']
+    return k, k + feature_size(image_size) * DENSE1_DIM
+
+
+class FidModel(object):
+    """The device-side model: the flat parameter vector of fv_fid_param_count (base layers at their fv_layer offsets, then the
+    dense kernel and bias), the BN moving statistics (fv_state_count), the Adam state, and the calls into the library."""
+
+    def __init__(self, image_size, device=0):
+        self.image_size = int(image_size)
+        self.ctx = Context(device)
+        self.dev = torch.device('cuda', device)
+        self.layers = base_layers()
+        self.n_params = int(lib().fv_fid_param_count(self.image_size))
+        if self.n_params <= 0:
+            raise ValueError('image_size must be a positive multiple of 32')
+        self.n_state = int(lib().fv_state_count())
+        self.F = feature_size(self.image_size)
+        self.kernel_off, self.bias_off = dense_offsets(self.image_size)
+        self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros(self.n_state, dtype=torch.float32, device=self.dev)
+        self.grads = self.m = self.v = None
+        self.iterations = 0
+        self.bn_zero_debias = True      # Keras 2.2.4's zero-debiased BN update (Engine.bn_zero_debias)
+        self.bn_updates = 0             # BN moving-statistics updates applied so far: three per training step (one per tower)
+        self._ws = {}
+        self._loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
+
+    # ------------------------------------------------------------------ parameters
+    def set_base(self, params, state):
+        """The 52 base layers from a flat vector in the fv_layer layout (the detector's or a base file's) and the BN state."""
+        n = self.kernel_off
+        self.params[:n].copy_(torch.as_tensor(np.asarray(params)[:n], dtype=torch.float32))
+        self.state.copy_(torch.as_tensor(np.asarray(state), dtype=torch.float32).reshape(-1))
+
+    def init_synthetic_base(self, seed=7):
+        """Engine.init_synthetic restricted to the base: kernels ~ N(0, 2/fan_in), gamma 1, beta 0, moving mean 0 / var 1."""
+        g = torch.Generator(device='cpu').manual_seed(seed)
+        p = torch.zeros(self.kernel_off, dtype=torch.float32)
+        s = torch.zeros(self.n_state, dtype=torch.float32)
+        for d in self.layers:
+            k, cin, cout = d['ksize'], d['cin'], d['cout']
+            n = cout * k * k * cin
+            p[d['w_off']:d['w_off'] + n] = torch.randn(n, generator=g) * float(np.sqrt(2.0 / (k * k * cin)))
+            p[d['gamma_off']:d['gamma_off'] + cout] = 1.0
+            s[d['var_off']:d['var_off'] + cout] = 1.0
+        self.set_base(p.numpy(), s.numpy())
+
+    def init_dense(self, seed=0):
+        """Keras defaults of Dense(64) (fi.py:327): glorot_uniform kernel, limit sqrt(6 / (F + 64)), zero bias."""
+        g = torch.Generator().manual_seed(seed)
+        lim = float(np.sqrt(6.0 / (self.F + DENSE1_DIM)))
+        n = self.F * DENSE1_DIM
+        self.params[self.kernel_off:self.kernel_off + n] = ((torch.rand(n, generator=g) * 2 - 1) * lim).to(self.dev)
+        self.params[self.bias_off:self.bias_off + DENSE1_DIM] = 0
+
+    def dense_kernel(self):
+        return self.params[self.kernel_off:self.bias_off].view(self.F, DENSE1_DIM)
+
+    def dense_bias(self):
+        return self.params[self.bias_off:self.bias_off + DENSE1_DIM]
+
+    # ------------------------------------------------------------------ workspaces
+    def _workspace(self, batch, training):
+        key = (int(batch), bool(training))
+        if key not in self._ws:
+            n = int(lib().fv_fid_workspace_bytes(int(batch), self.image_size, 1 if training else 0))
+            if n == 0:
+                raise FvError('unsupported batch/image_size %r' % ((batch, self.image_size),))
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}   # one per mode
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
+        return self._ws[key]
+
+    def _as_input(self, x):
+        if isinstance(x, np.ndarray) and x.dtype == np.uint8:
+            x = x.astype(np.float32) / np.float32(255.0)
+        x = torch.as_tensor(x)
+        if x.dtype == torch.uint8:
+            x = x.to(torch.float32) / 255.0
+        if x.dtype != torch.float32 or x.device != self.dev:
+            x = x.to(device=self.dev, dtype=torch.float32)
+        x = x.contiguous()
+        if x.dim() != 4 or x.shape[1] != self.image_size or x.shape[2] != self.image_size or x.shape[3] != 3:
+            raise ValueError('expected images of shape (B, %d, %d, 3), got %r' % (self.image_size, self.image_size, tuple(x.shape)))
+        return x
+
+    # ------------------------------------------------------------------ extraction (fi.py:378-395)
+    def extract_device(self, x):
+        """x (B,S,S,3) in [0,1] (uint8 crops are divided by 255, fi.py:1577) -> (B,64) facial IDs, float32 CUDA tensor."""
+        from .engine import Engine
+        x = self._as_input(x)
+        B = x.shape[0]
+        cap = Engine.max_infer_batch(self.image_size)
+        if B > cap >= 1:
+            step = cap // 8 * 8 if cap >= 8 else cap
+            return torch.cat([self.extract_device(x[i:i + step]) for i in range(0, B, step)])
+        ws = self._workspace(B, False)
+        fid = torch.empty((B, DENSE1_DIM), dtype=torch.float32, device=self.dev)
+        rc = lib().fv_fid_extract(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), B, self.image_size, ptr(ws), ws.numel(),
+                                  ptr(fid))
+        self.ctx.check(rc, 'fv_fid_extract')
+        return fid
+
+    # ------------------------------------------------------------------ training
+    def ensure_optimizer(self):
+        if self.grads is None:
+            self.grads = torch.zeros_like(self.params)
+            self.m = torch.zeros_like(self.params)
+            self.v = torch.zeros_like(self.params)
+
+    def forward_backward(self, xa, xp, xn):
+        """Triplet forward + loss + backward (fv_fid_train_step): gradients in self.grads, BN moving statistics updated a -> p -> n;
+        returns the loss as a 1-element CUDA tensor (no host sync)."""
+        self.ensure_optimizer()
+        xa, xp, xn = self._as_input(xa), self._as_input(xp), self._as_input(xn)
+        B = xa.shape[0]
+        if xp.shape != xa.shape or xn.shape != xa.shape:
+            raise ValueError('anchor, positive and negative batches differ in shape')
+        ws = self._workspace(B, True)
+        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
+        rc = lib().fv_fid_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(xa), ptr(xp), ptr(xn), B, self.image_size,
+                                     ptr(ws), ws.numel(), ptr(self.grads), ptr(self._loss))
+        self.ctx.check(rc, 'fv_fid_train_step')
+        self.bn_updates += 3
+        return self._loss
+
+    def adam_step(self, lr, beta_1, beta_2, decay=0.0, eps=1e-7):
+        rc = lib().fv_adam_step(self.ctx.handle, ptr(self.params), ptr(self.grads), ptr(self.m), ptr(self.v), self.n_params,
+                                self.iterations, float(lr), float(beta_1), float(beta_2), float(eps), float(decay))
+        self.ctx.check(rc, 'fv_adam_step')
+        self.iterations += 1
+
+    def train_on_batch(self, xa, xp, xn, lr, beta_1, beta_2, decay=0.0):
+        loss = self.forward_backward(xa, xp, xn)
+        self.adam_step(lr, beta_1, beta_2, decay)
+        return loss
+
+    # ------------------------------------------------------------------ checkpoint (fi.py:643 model.save, fi.py:304 load_model)
+    def save(self, path):
+        """face_identifier.h5 in Keras' weight layout: the base as the nested model 'base', then dense1/kernel:0 [F][64] and
+        dense1/bias:0; this build's Adam state and step counts under /fv."""
+        from . import weights
+        extras = dict(iterations=np.int64(self.iterations), bn_updates=np.int64(self.bn_updates))
+        if self.m is not None:
+            extras['adam_m'] = self.m.cpu().numpy(); extras['adam_v'] = self.v.cpu().numpy()
+        p = self.params.cpu().numpy()
+        dense = [('dense1/kernel:0', p[self.kernel_off:self.bias_off].reshape(self.F, DENSE1_DIM)),
+                 ('dense1/bias:0', p[self.bias_off:self.bias_off + DENSE1_DIM])]
+        weights.write_keras_h5(path, self.layers, p, self.state.cpu().numpy(), nested='base', extras=extras,
+                               more_groups={'dense1': dense})
+
+    def load(self, path):
+        from . import weights
+        from .hdf5_lite import read_hdf5
+        datasets, _ = read_hdf5(path)
+        p, st, found = weights.from_keras_datasets(datasets, self.layers, self.n_params, self.n_state)
+        missing = sorted(set(weights.expected_keras_tensors(self.layers)) - set(found))
+        if missing:
+            raise FvError('%s lacks %d base tensors, e.g. %r' % (path, len(missing), missing[:3]))
+        kern = [k for k in datasets if k.endswith('/dense1/kernel:0')]
+        bias = [k for k in datasets if k.endswith('/dense1/bias:0')]
+        if len(kern) != 1 or len(bias) != 1:
+            raise FvError('%s holds no dense1 layer' % path)
+        K = np.asarray(datasets[kern[0]], np.float32)
+        b = np.asarray(datasets[bias[0]], np.float32)
+        if K.shape != (self.F, DENSE1_DIM) or b.shape != (DENSE1_DIM,):
+            raise FvError('%s: dense1 has shapes %r / %r, this model expects (%d, %d) / (%d,)'
+                          % (path, K.shape, b.shape, self.F, DENSE1_DIM, DENSE1_DIM))
+        p[self.kernel_off:self.bias_off] = K.reshape(-1)
+        p[self.bias_off:self.bias_off + DENSE1_DIM] = b
+        self.params.copy_(torch.from_numpy(p))
+        self.state.copy_(torch.from_numpy(st))
+        self.iterations = int(datasets['/fv/iterations']) if '/fv/iterations' in datasets else 0
+        self.bn_updates = int(datasets['/fv/bn_updates']) if '/fv/bn_updates' in datasets else 0
+        if '/fv/adam_m' in datasets and '/fv/adam_v' in datasets:
+            self.ensure_optimizer()
+            self.m.copy_(torch.from_numpy(np.asarray(datasets['/fv/adam_m'])))
+            self.v.copy_(torch.from_numpy(np.asarray(datasets['/fv/adam_v'])))
+
+
+class FidExtractor(object):
+    """fid_extractor (fi.py:378-395): base -> flatten -> dense1 -> l2_norm with inference-mode BN; `predict` as Keras (numpy)."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def predict_device(self, images):
+        return self.model.extract_device(images)
+
+    def predict(self, images):
+        return self.predict_device(images).cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- triplet sequences (fi.py:1490-1601)
+def make_triplets(db, rng=None):
+    """The reference's triplet list: for every subject (in sorted subject_id order) and every pair k < l of its images, the triplet
+    (k, l, a random image of another subject), as row labels of `db`.  rng: numpy RandomState (np.random by default)."""
+    rng = np.random if rng is None else rng
+    t_indexes = np.asarray(db.index)
+    triplets = []
+    for _sid, df in db.groupby('subject_id'):
+        own = np.asarray(df.index)
+        others = t_indexes[~np.isin(t_indexes, own)]
+        for k in range(0, own.shape[0] - 1):
+            for l in range(k + 1, own.shape[0]):
+                triplets.append((own[k], own[l], rng.choice(others, size=1)[0]))
+    return triplets
+
+
+def num_batches(n, batch_size):
+    """hps['step'] as the sequences set it: whole batches plus one short last batch."""
+    return n // batch_size + (1 if n % batch_size else 0)
+
+
+def _imread(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert('RGB'))
+
+
+class _TripletSequence(object):
+    DB_FILE = None
+    PICKLE_FILE = None
+    FACES_DIR = None
+
+    def __init__(self, raw_data_path, hps, nn_arch, load_flag=True):
+        import pandas as pd
+        self.raw_data_path = raw_data_path
+        self.hps = hps
+        self.nn_arch = nn_arch
+        self.db = pd.read_csv(self.DB_FILE).iloc[:, 1:]
+        if load_flag:
+            with open(self.PICKLE_FILE, 'rb') as f:
+                self.img_triplet_pairs = pickle.load(f)
+        else:
+            self.img_triplet_pairs = make_triplets(self.db)
+            shuffle(self.img_triplet_pairs)
+            with open(self.PICKLE_FILE, 'wb') as f:
+                pickle.dump(self.img_triplet_pairs, f)
+        self.batch_size = int(self.hps['batch_size'])
+        self.hps['step'] = num_batches(len(self.img_triplet_pairs), self.batch_size)
+
+    def __len__(self):
+        return self.hps['step']
+
+    def _image(self, label):
+        img = _imread(os.path.join(self.raw_data_path, self.FACES_DIR, self.db.loc[label, 'face_file']))
+        return img.astype(np.float32) / np.float32(255.0)
+
+    def __getitem__(self, index):
+        end = len(self.img_triplet_pairs) if index == self.hps['step'] - 1 else (index + 1) * self.batch_size
+        rows = self.img_triplet_pairs[index * self.batch_size:end]
+        xa = np.asarray([self._image(t[0]) for t in rows])
+        xp = np.asarray([self._image(t[1]) for t in rows])
+        xn = np.asarray([self._image(t[2]) for t in rows])
+        return {'input_a': xa, 'input_p': xp, 'input_n': xn}, {'output': np.zeros((len(rows), 3 * DENSE1_DIM))}
+
+
+class TrainingSequence(_TripletSequence):
+    """UCCS crops: subject_image_db.csv, <raw_data_path>/subject_faces/, img_triplet_pairs.pickle (fi.py:1490-1601)."""
+    DB_FILE = 'subject_image_db.csv'
+    PICKLE_FILE = 'img_triplet_pairs.pickle'
+    FACES_DIR = 'subject_faces'
+
+
+class TrainingSequenceVGGFace2(_TripletSequence):
+    """VGGFace2 crops: subject_image_vggface2_db.csv, <raw_data_path>/subject_faces_vggface2/, img_triplet_pairs_vggface2.pickle."""
+    DB_FILE = 'subject_image_vggface2_db.csv'
+    PICKLE_FILE = 'img_triplet_pairs_vggface2.pickle'
+    FACES_DIR = 'subject_faces_vggface2'
+
+
+# ----------------------------------------------------------------------------- FaceIdentifier (fi.py:288-643)
+class FaceIdentifier(object):
+    """Face identifier on the Darknet-53 base of YOLOv3."""
+
+    MODEL_PATH = 'face_identifier.h5'
+    BASE_MODEL_PATH = 'yolov3_base.h5'
+    DARKNET_WEIGHTS_PATH = 'yolov3.weights'
+
+    TrainingSequence = TrainingSequence
+    TrainingSequenceVGGFace2 = TrainingSequenceVGGFace2
+
+    def __init__(self, conf, device=None):
+        self._full_conf = conf
+        self.conf = conf['fi_conf']
+        self.raw_data_path = self.conf['raw_data_path']
+        self.hps = self.conf['hps']
+        self.nn_arch = self.conf['nn_arch']
+        self.model_loading = self.conf['model_loading']
+        self.image_size = int(self.nn_arch['image_size'])
+        if self.image_size % 32 or self.image_size < 32:
+            raise ValueError('image_size must be a positive multiple of 32 (network stride)')
+        if int(self.nn_arch['dense1_dim']) != DENSE1_DIM:
+            raise ValueError('dense1_dim must be %d: the triplet loss slices 0:64 / 64:128 / 128:192 (reference triplet_loss)'
+                             % DENSE1_DIM)
+        if device is None:
+            device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
+        self.model = FidModel(self.image_size, device)
+        self.model.bn_zero_debias = bool(self.conf.get('bn_zero_debias', True))
+        if self.model_loading:
+            self.model.load(self.MODEL_PATH)
+        else:
+            self._load_base()
+            self.model.init_dense()
+        self._fd = None
+        self.fid_extractor = FidExtractor(self.model)
+
+    @property
+    def fd(self):
+        """The FaceDetector of fd_conf (fi.py:374), created on first use."""
+        if self._fd is None:
+            from .face_detection import FaceDetector
+            self._fd = FaceDetector(self._full_conf['fd_conf'])
+        return self._fd
+
+    def _load_base(self):
+        """YOLOV3Base (fi.py:398-614), as FaceDetector._load_base: yolov3_base.h5 when yolov3_base_model_load is set, else the
+        Darknet file (then yolov3_base.h5 is written, fi.py:612), else synthetic weights (announced)."""
+        from . import weights
+        m = self.model
+        if self.conf.get('yolov3_base_model_load') and os.path.exists(self.BASE_MODEL_PATH):
+            from .hdf5_lite import is_hdf5, read_hdf5
+            if is_hdf5(self.BASE_MODEL_PATH):
+                p, st, _found = weights.from_keras_datasets(read_hdf5(self.BASE_MODEL_PATH)[0], m.layers, m.kernel_off, m.n_state)
+            else:
+                with open(self.BASE_MODEL_PATH, 'rb') as f:
+                    d = np.load(f)
+                    p, st = d['params'], d['state']
+            m.set_base(p, st)
+        elif os.path.exists(self.DARKNET_WEIGHTS_PATH):
+            p, st = weights.read_darknet_base(self.DARKNET_WEIGHTS_PATH, m.layers, m.kernel_off, m.n_state)
+            m.set_base(p, st)
+            weights.write_keras_h5(self.BASE_MODEL_PATH, m.layers, p, st, nested=None)
+        else:
+            print('FaceIdentifier: neither %s nor %s found; using synthetic base weights'
+                  % (self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH))
+            m.init_synthetic_base(seed=7)
+
+    def train_on_batch(self, xa, xp, xn):
+        """One Keras train_on_batch of the triplet model: fv_fid_train_step, then Adam with fi_conf.hps.  Returns the loss (float)."""
+        h = self.hps
+        loss = self.model.train_on_batch(xa, xp, xn, h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0))
+        return float(loss.item())
+
+    def train(self):
+        """fi.py:616-643: fit_generator over the triplet sequence (batch order shuffled every epoch, as Keras does for a Sequence),
+        hps['epochs'] epochs of hps['step'] steps (the sequence sets hps['step'] to its batch count), then save face_identifier.h5."""
+        if self.conf['resource_type'] == RESOURCE_TYPE_UCCS:
+            tr_gen = self.TrainingSequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=False)
+        elif self.conf['resource_type'] == RESOURCE_TYPE_VGGFACE2:
+            tr_gen = self.TrainingSequenceVGGFace2(self.raw_data_path, self.hps, self.nn_arch, load_flag=False)
+        else:
+            raise ValueError('resource type is not valid.')
+        steps = int(self.hps['step'])
+        for e in range(int(self.hps['epochs'])):
+            losses = []
+            for i in np.random.permutation(len(tr_gen))[:steps]:
+                x, _ = tr_gen[int(i)]
+                losses.append(self.train_on_batch(x['input_a'], x['input_p'], x['input_n']))
+            print('Epoch %d/%d - loss: %.4f' % (e + 1, int(self.hps['epochs']), float(np.mean(losses)) if losses else float('nan')))
+        print('Save the model.')
+        self.model.save(self.MODEL_PATH)
+
+
+def main():
+    """Reads ./face_vijnana_yolov3.json (Windows: _win) and dispatches on fi_conf.mode (fi.py:1715-1760).  'train' trains and saves
+    face_identifier.h5; the facial-ID database steps the reference runs after it (make_facial_ids_db, register_facial_ids) and
+    every other mode are not implemented here."""
+    name = 'face_vijnana_yolov3_win.json' if platform.system() == 'Windows' else 'face_vijnana_yolov3.json'
+    with open(name, 'r') as f:
+        conf = json.load(f)
+    mode = conf['fi_conf']['mode']
+    if mode != 'train':
+        raise NotImplementedError('fi_conf.mode %r is not implemented (available: train)' % mode)
+    fi = FaceIdentifier(conf)
+    ts = time.time()
+    fi.train()
+    print('Elasped time: {0:f}s'.format(time.time() - ts))
+
+
+if __name__ == '__main__':
+    main()

@@ -162,10 +162,11 @@ def read_keras_h5(path, layers, n_params, n_state, require_all=True):
     return params, state, extras
 
 
-def write_keras_h5(path, layers, params, state, nested='model_1', extras=None):
+def write_keras_h5(path, layers, params, state, nested='model_1', extras=None, more_groups=None):
     """Flat vectors -> an HDF5 file in Keras' weight layout (readable by h5py / `model.load_weights`; no `model_config`, so not by
     `load_model`).  nested: name of the nested-Model layer that holds every BN layer (face_detector.h5), or None for one group per
-    Keras layer (yolov3_base.h5).  extras: {name: array} stored under /fv (this build's Adam state)."""
+    Keras layer (yolov3_base.h5).  extras: {name: array} stored under /fv (this build's Adam state).  more_groups: {layer: [(weight
+    name, array)]} of layers outside `layers`, written after them (face_identifier.h5's dense1)."""
     from .hdf5_lite import write_hdf5
     kw = keras_weights(layers, params, state)
     data, attrs = {}, {}
@@ -186,6 +187,7 @@ def write_keras_h5(path, layers, params, state, nested='model_1', extras=None):
             kern = np.asarray(params)[d['w_off']:d['w_off'] + cout * k * k * cin].reshape(cout, k, k, cin).transpose(1, 2, 3, 0)
             bias = np.asarray(params)[d['beta_off']:d['beta_off'] + cout]
             groups[name] = [('%s/kernel:0' % name, kern), ('%s/bias:0' % name, bias)]
+    groups.update(more_groups or {})
     names = (['input1'] if nested else []) + list(groups)
     fixed = lambda xs: np.array([x.encode('utf8') for x in xs]) if xs else np.zeros((0,), 'S1')
     attrs['/'] = {'keras_version': b'2.2.4', 'backend': b'tensorflow'}

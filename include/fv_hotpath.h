@@ -177,7 +177,7 @@ int fv_forward_infer(fv_ctx* ctx, const float* params, const float* bn_state, co
                      int image_size, void* workspace, size_t workspace_bytes, float* y);
 /* The model `FaceDetector.YOLOV3Base` returns (fd.py:384-600): the Darknet-53 base alone, input -> the output of the last
  * residual add (add_23), feat [batch][S/32][S/32][1024] float32 -- the tensor the head conv reads (fd.py:344-352) and the
- * backbone output FaceIdentifier builds on (face_identification.py:323, 397-614).  Same kernels, same arithmetic and the same
+ * backbone output FaceIdentifier builds on (face_identification.py:323, 397-614; fv_fid_extract).  Same kernels, same arithmetic and the same
  * workspace as fv_forward_infer; y (may be NULL) additionally receives the head output of the same pass. */
 int fv_forward_base(fv_ctx* ctx, const float* params, const float* bn_state, const float* x, int batch,
                     int image_size, void* workspace, size_t workspace_bytes, float* feat, float* y);
@@ -335,6 +335,44 @@ int64_t fv_jpeg_plane_bytes(const fv_jpeg_info* info);
 /* coefs, descs, planes (scratch), rgb: device; max_blocks / max_pixels: the largest block / pixel count of one image (grid size) */
 int fv_jpeg_reconstruct_batch(fv_ctx* ctx, const int16_t* coefs, const fv_jpeg_desc* descs, int n, uint8_t* planes, uint8_t* rgb,
                               int64_t max_blocks, int64_t max_pixels);
+
+/* ------------------------------------------------------------------ FaceIdentifier (facial IDs, triplet loss)
+ * The reference's second model (face_identification.py = fi.py): FaceIdentifier (fi.py:288-376) runs ONE shared Darknet-53 base
+ * (the 52 BN layers of fv_layer(0..51), weights as FaceDetector.YOLOV3Base) over three inputs, then Flatten (NHWC row-major,
+ * F = (S/32)^2 * 1024 = 173 056 at 416), Dense(64, relu) and K.l2_normalize (x * rsqrt(max(sum x^2, 1e-12)): an all-zero ReLU row
+ * stays zero); the facial-ID extractor (_make_fid_extractor, fi.py:378-395) is the same chain for one input with inference BN.
+ * Flat parameter layout: the 52 base layers exactly at their fv_layer offsets (first 40 584 928 floats), then the dense kernel
+ * [F][64] (Keras layout), then the bias [64] -- 51 660 576 floats at 416.  BN moving statistics: the fv_state_count() vector.
+ * dense1_dim is fixed at 64: the reference's loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76). */
+int64_t fv_fid_param_count(int image_size);   /* 0 unless image_size is a positive multiple of 32 */
+/* training = 0: fv_fid_extract, != 0: fv_fid_train_step (three towers' kept tensors). */
+size_t fv_fid_workspace_bytes(int batch, int image_size, int training);
+/* Replaces fid_extractor.predict (fi.py:378-395): x [batch][S][S][3] in [0,1] -> fid [batch][64], inference-mode BN.  Runs
+ * fv_forward_base (feature map kept in the workspace), then the dense layer split over F in fixed chunks whose partials are
+ * summed in chunk order (no atomics): bit-reproducible, and an image's ID does not depend on the rest of the batch.  Batch bound as
+ * fv_forward_infer. */
+int fv_fid_extract(fv_ctx* ctx, const float* params, const float* bn_state, const float* x, int batch, int image_size,
+                   void* workspace, size_t workspace_bytes, float* fid);
+/* One step of model.fit_generator with loss=triplet_loss (fi.py:616-643, 72-76): forward of the towers a, p, n (xa / xp / xn,
+ * [batch][S][S][3] each) through the shared base in training-mode BN, each tower normalising with ITS OWN batch statistics; the
+ * dense layer and l2_normalize over the 3*batch rows; loss = mean_b max(|ua - up| - |ua - un| + 0.2, 0) (device float); the
+ * gradient of every parameter of the fv_fid_param_count layout into `grads` (overwritten).  Follow with fv_adam_step over the
+ * whole vector.  This build's definitions where the reference's stack leaves the result open (Keras is not importable here, so
+ * they are not pinned against it):
+ *  - BN moving statistics: each tower applies its own update (Keras calls the shared base three times), in the order a -> p -> n.
+ *    With fv_set_bn_zero_debias_step(ctx, k) before the call, the three updates are the zero-debiased updates k, k + 1, k + 2 of
+ *    the model's life (the host passes k = 3 * steps so far + 1); with 0 all three are the plain EMA.
+ *  - a distance of exactly 0 contributes gradient 0 (TF's sqrt gradient is NaN there and would poison every weight); the hinge
+ *    passes the gradient where its argument is >= 0 (TF's MaximumGrad), ReLU where the pre-activation is > 0 (ReluGrad).
+ * Reproducibility as fv_train_step (float atomics in the conv weight-gradients).  No bucket callback: data-parallel FI training
+ * is not provided. */
+int fv_fid_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* xa, const float* xp, const float* xn,
+                      int batch, int image_size, void* workspace, size_t workspace_bytes, float* grads, float* loss);
+/* The dense head on its own (operator parity tests): x [rows][F] -> out [rows][64] = l2_normalize(relu(x . w + bias)),
+ * w [F][64]; pre (may be NULL) receives x . w + bias.  F % 256 == 0; partial: fv_fid_dense_partial_floats(rows, F) floats. */
+int64_t fv_fid_dense_partial_floats(int rows, int64_t F);
+int fv_fid_dense_l2(fv_ctx* ctx, const float* x, int rows, int64_t F, const float* w, const float* bias, float* partial,
+                    float* pre, float* out);
 
 /* ------------------------------------------------------------------ secondary: three-scale YOLOv3
  * (SURVEY 8a-17/18).  The reference builds this graph in make_yolov3_model (yd.py:217-311) and
