@@ -101,6 +101,8 @@ def _declare(L):
         'fv_letterbox': (i32, [vp, vp, i32, i32, i32, vp, ctypes.POINTER(ctypes.c_int32)]),
         'fv_letterbox_batch': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32, i32, vp,
                                     ctypes.POINTER(ctypes.c_int32)]),
+        'fv_letterbox_crops': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
+                                    ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_yolov3_num_layers': (i32, []),
         'fv_yolov3_layer': (i32, [i32, i32, ctypes.POINTER(LayerDesc)]),
         'fv_yolov3_param_count': (i64, [i32]),
@@ -120,6 +122,7 @@ def _declare(L):
         'fv_fid_train_step': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
         'fv_fid_dense_partial_floats': (i64, [i32, i64]),
         'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
+        'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -92,6 +92,49 @@ __global__ __launch_bounds__(256) void letterbox_batch_kernel(const unsigned cha
     o[0] = r; o[1] = g; o[2] = bl;
 }
 
+// many crops (sub-rectangles of the packed images) in one launch: blockIdx.z = crop.  Crop c starts at byte t.off[c] of `packed`
+// (its image's offset plus its top-left pixel) and advances t.pitch[c] bytes per row; everything else is letterbox_kernel for a
+// contiguous h x w image -- the same expressions in the same order, the border replicated at the CROP's edges (what cv.resize
+// sees after the reference's slice), so the pixels are bit-identical to fv_letterbox of a contiguous copy of the crop.
+constexpr int LBC_MAX = 64;    // crops per launch: the table travels in the kernel arguments (64 x 36 B); longer lists are chunked
+struct LbcTable { long long off[LBC_MAX]; int pitch[LBC_MAX], h[LBC_MAX], w[LBC_MAX], w_p[LBC_MAX], h_p[LBC_MAX], pad_t[LBC_MAX],
+                  pad_l[LBC_MAX]; };
+
+__global__ __launch_bounds__(256) void letterbox_crops_kernel(const unsigned char* __restrict__ packed, LbcTable t, int S,
+                                                              float* __restrict__ dst) {
+    const int c = blockIdx.z;
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= S || y >= S) return;
+    const unsigned char* __restrict__ src = packed + t.off[c];
+    const int h = t.h[c], w = t.w[c], w_p = t.w_p[c], h_p = t.h_p[c], pitch = t.pitch[c];
+    float r = 0.f, g = 0.f, b = 0.f;
+    const int xi = x - t.pad_l[c], yi = y - t.pad_t[c];
+    if (xi >= 0 && xi < w_p && yi >= 0 && yi < h_p) {
+        const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
+        const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
+        const int sx = (int)floor(fx), sy = (int)floor(fy);
+        float wx[4], wy[4];
+        cubic_w((float)(fx - sx), wx);
+        cubic_w((float)(fy - sy), wy);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int yy = min(max(sy - 1 + j, 0), h - 1);
+            float rr = 0.f, gg = 0.f, bb = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int xx = min(max(sx - 1 + i, 0), w - 1);
+                const unsigned char* p = src + (size_t)yy * pitch + (size_t)xx * 3;
+                rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
+            }
+            r += wy[j] * rr; g += wy[j] * gg; b += wy[j] * bb;
+        }
+        r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); b *= (1.0f / 255.0f);
+    }
+    float* o = dst + (((size_t)c * S + y) * S + x) * 3;
+    o[0] = r; o[1] = g; o[2] = b;
+}
+
 bool lb_geometry(int h, int w, int S, int* g) {
     int w_p, h_p, pad_t = 0, pad_b = 0, pad_l = 0, pad_r = 0;
     if (w >= h) {   // face_detection.py:120-133
@@ -128,6 +171,45 @@ extern "C" int fv_letterbox_batch(fv_ctx* ctx, const uint8_t* packed, const int6
         FvProfScope ps(ctx, "letterbox_batch_kernel", 0.0, bytes);
         hipLaunchKernelGGL(letterbox_batch_kernel, dim3((S + 15) / 16, (S + 15) / 16, nb), dim3(256), 0, ctx->stream, packed, t, S,
                            dst + (size_t)b0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+extern "C" int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                                  const int32_t* crops, int n, int image_size, float* dst) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, packed && offsets && hw && crops && dst && n_img >= 1 && n >= 1 && image_size >= 1, "letterbox_crops: bad arguments");
+    const int S = image_size;
+    // validate every crop before anything is enqueued: a bad record leaves dst untouched
+    for (int c = 0; c < n; ++c) {
+        const int* r = crops + 5 * c;
+        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
+        FV_REQUIRE(ctx, im >= 0 && im < n_img, "letterbox_crops: crop %d names image %d of %d", c, im, n_img);
+        const int H = hw[2 * im], W = hw[2 * im + 1];
+        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "letterbox_crops: bad image %d", im);
+        FV_REQUIRE(ctx, h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
+                   "letterbox_crops: crop %d (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", c, y0, x0, h, w, im, H, W);
+        int g[6];
+        FV_REQUIRE(ctx, lb_geometry(h, w, S, g), "letterbox_crops: crop %d (%d x %d) too elongated for image_size %d", c, h, w, S);
+    }
+    for (int c0 = 0; c0 < n; c0 += LBC_MAX) {
+        const int nc = n - c0 < LBC_MAX ? n - c0 : LBC_MAX;
+        LbcTable t{};
+        double bytes = 0.0;
+        for (int i = 0; i < nc; ++i) {
+            const int* r = crops + 5 * (c0 + i);
+            const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
+            const int W = hw[2 * im + 1];
+            int g[6];
+            lb_geometry(h, w, S, g);
+            t.off[i] = offsets[im] + ((long long)y0 * W + x0) * 3; t.pitch[i] = W * 3;
+            t.h[i] = h; t.w[i] = w; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
+            bytes += (double)h * w * 3 + 12.0 * S * S;
+        }
+        FvProfScope ps(ctx, "letterbox_crops_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_crops_kernel, dim3((S + 15) / 16, (S + 15) / 16, nc), dim3(256), 0, ctx->stream, packed, t, S,
+                           dst + (size_t)c0 * S * S * 3);
         FV_LAUNCH_CHECK(ctx);
     }
     return FV_OK;

@@ -1,5 +1,6 @@
 """Detection accuracy of FaceDetector.evaluate's output: the reference's `cal_mAP_fd`
-(evaluate.py:27-127) and the IoU-threshold sweep of its `main` (evaluate.py:337-355).
+(evaluate.py:27-127) and the IoU-threshold sweep of its `main` (evaluate.py:337-355); identification accuracy of
+FaceIdentifier.test's output: `cal_acc_fi` (evaluate.py:225-329) and its sweep (evaluate.py:362-387).
 
 Host code, as in the reference (pandas/NumPy/SciPy on a few thousand boxes); not part of the device
 hot path.  What it restates, line by line:
@@ -157,6 +158,82 @@ def cal_mAP_sweep(gt_path, sol_path, iou_ths=None):
     return res, float(np.mean([m for _, m in res])) if res else 0.0
 
 
+def acc_fi_image(gt_sids, gt_boxes, det_sids, det_boxes):
+    """The greedy assignment of one ground-truth image that has detections (evaluate.py:246-304): pairs with IoU > 0, taken in
+    descending IoU order (ties: gt, then detection order), each gt and detection at most once -> (assigned [(i, j, iou)],
+    unassigned gt indices, unassigned detection indices), or None when no pair overlaps (the image then counts nothing,
+    evaluate.py:275).  gt_sids / det_sids: subject ids (-1 = unknown); boxes (n,4) as x, y, w, h."""
+    pairs = []
+    for i, g in enumerate(gt_boxes):
+        gb = (g[0], g[1], g[0] + g[2], g[1] + g[3])
+        for j, d in enumerate(det_boxes):
+            iou = bbox_iou_xyxy(gb, (d[0], d[1], d[0] + d[2], d[1] + d[3]))
+            if iou > 0.:
+                pairs.append((i, j, iou))
+    if not pairs:
+        return None
+    pairs.sort(key=lambda t: -t[2])          # stable
+    used_g, used_d, assigned = set(), set(), []
+    for i, j, iou in pairs:
+        if i in used_g or j in used_d:
+            continue
+        assigned.append((i, j, iou))
+        used_g.add(i); used_d.add(j)
+    return assigned, [i for i in range(len(gt_boxes)) if i not in used_g], [j for j in range(len(det_boxes)) if j not in used_d]
+
+
+def cal_acc_fi(gt_path, sol_path, iou_th):
+    """The reference's cal_acc_fi (evaluate.py:225-329) -> (tp, fp, tn, fn, acc), acc = (tp + tn) / (tp + tn + fp + fn).
+    Solution csv (no header): FILE, SUBJECT_ID, x, y, w, h, score (FaceIdentifier.test); ground truth as cal_mAP_fd.  Per
+    ground-truth image (sorted): without detections every gt row is tn (SUBJECT_ID -1) or fn; otherwise the greedy assignment of
+    acc_fi_image, an assigned pair counting tp when IoU >= iou_th and both ids are the same known subject, fp when IoU >= iou_th,
+    the detection is known and the ids differ, else tn when the gt is unknown, else fn.  Detections on images outside the
+    ground truth are not counted."""
+    import pandas as pd
+    sol_df = pd.read_csv(sol_path, header=None)
+    gt_df = pd.read_csv(gt_path)
+    sol_groups = {k: v for k, v in sol_df.groupby(0, sort=True)}
+    tp = fp = tn = fn = 0
+    for image_id, df in gt_df.groupby('FILE', sort=True):
+        g_sid = df.iloc[:, 2].to_numpy()
+        rel = sol_groups.get(image_id)
+        if rel is None:
+            tn += int(np.sum(g_sid == -1)); fn += int(np.sum(g_sid != -1))
+            continue
+        d_sid = rel.iloc[:, 1].to_numpy()
+        res = acc_fi_image(g_sid, df.iloc[:, 3:7].to_numpy(dtype=np.float64), d_sid, rel.iloc[:, 2:6].to_numpy(dtype=np.float64))
+        if res is None:
+            continue
+        assigned, free_g, free_d = res
+        for i, j, iou in assigned:
+            if iou >= iou_th and g_sid[i] != -1 and d_sid[j] != -1 and g_sid[i] == d_sid[j]:
+                tp += 1
+            elif iou >= iou_th and d_sid[j] != -1 and g_sid[i] != d_sid[j]:
+                fp += 1
+            elif g_sid[i] == -1:
+                tn += 1
+            else:
+                fn += 1
+        for i in free_g:
+            if g_sid[i] == -1:
+                tn += 1
+            else:
+                fn += 1
+        for j in free_d:
+            if d_sid[j] == -1:
+                tn += 1
+            else:
+                fp += 1
+    acc = (tp + tn) / (tp + tn + fp + fn)
+    return tp, fp, tn, fn, acc
+
+
+def cal_acc_fi_sweep(gt_path, sol_path, iou_ths=None):
+    """The sweep of evaluate.py:362-387 (IoU 0.50 ... 0.95): -> list of (iou_th, tp, fp, tn, fn, acc)."""
+    iou_ths = np.arange(0.5, 1.0, 0.05) if iou_ths is None else iou_ths
+    return [(float(th),) + tuple(cal_acc_fi(gt_path, sol_path, th)) for th in iou_ths]
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description='mAP of a FaceDetector.evaluate solution file (reference evaluate.py cal_map_fd)')
@@ -164,8 +241,18 @@ def main(argv=None):
     ap.add_argument('--gt_path', required=True)
     ap.add_argument('--sol_path', required=True)
     a = ap.parse_args(argv)
+    if a.mode == 'cal_acc_fi':
+        from .hdf5_lite import write_hdf5
+        res = cal_acc_fi_sweep(a.gt_path, a.sol_path)
+        for r in res:
+            print('{0:1.2f}'.format(r[0]), r[1], r[2], r[3], r[4], r[5])
+        cols = np.asarray([r[1:] for r in res], dtype=np.float64).reshape(-1, 5)
+        write_hdf5('fi_acc.h5', {'/tp_ls': cols[:, 0].astype(np.int64), '/fp_ls': cols[:, 1].astype(np.int64),
+                                 '/tn_ls': cols[:, 2].astype(np.int64), '/fn_ls': cols[:, 3].astype(np.int64),
+                                 '/acc_ls': cols[:, 4]})          # evaluate.py:382-387
+        return
     if a.mode != 'cal_map_fd':
-        raise SystemExit('only cal_map_fd is part of the FaceDetector path (SURVEY 8f)')
+        raise SystemExit('only cal_map_fd and cal_acc_fi are implemented here')
     res, mean = cal_mAP_sweep(a.gt_path, a.sol_path)
     for th, m in res:
         print('{0:1.2f}'.format(th), m)

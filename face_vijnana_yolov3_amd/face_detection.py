@@ -331,13 +331,15 @@ class FaceDetector(object):
         names = sorted(glob.glob(os.path.join(test_path, '*.jpg')))
         return shard_files(names, self.world, self.rank) if self.world > 1 else names
 
-    def _detect_files(self, files, need_raw=True):
+    def _detect_files(self, files, need_raw=True, _with_images=False):
         """Yield (file_name, raw image, boxes in image coordinates) in file order.  The reference's evaluate()/test() loops
         (fd.py:632-883) decode, letterbox and predict one image at a time; here a thread pool decodes batch k+1 (PIL releases
         the GIL) while batch k is letterboxed in one launch (fv_letterbox_batch) and runs ONE forward + ONE decode/NMS launch
         -- batch 1 is the slowest operating point of the network (1.3 ms/img against 0.4 at batch 16+).  Two deep: the loader
         thread fills a reused pinned buffer (PinnedRing) with batch k+1 while batch k is in the device queue and the host turns
-        batch k-1's result into BoundBoxes and rows."""
+        batch k-1's result into BoundBoxes and rows.  _with_images (FaceIdentifier.test): every item gains a fourth element
+        ((device uint8 buffer, offsets, hw), index) -- the batch's decoded images as fv_letterbox_batch read them, kept alive and
+        usable on the current stream."""
         bs = max(1, int(self.hps.get('eval_batch_size', default_eval_batch(self.image_size))))
         chunks = [files[i:i + bs] for i in range(0, len(files), bs)]
         if not chunks:
@@ -370,10 +372,13 @@ class FaceDetector(object):
                 raws = list(pool.map(data._pil_loader, chunk))
                 return raws, pack_images(raws, ring=ring)
             def finish(done):
-                chunk_, raws_, geoms_, launched = done
+                chunk_, raws_, geoms_, launched, imgs_ = done
                 for i, (name, boxes, geom) in enumerate(zip(chunk_, self._detect_collect(launched), geoms_)):
                     self._project_back(boxes, geom)
-                    yield name, (raws_[i] if raws_ is not None else None), boxes
+                    if _with_images:
+                        yield name, (raws_[i] if raws_ is not None else None), boxes, (imgs_, i)
+                    else:
+                        yield name, (raws_[i] if raws_ is not None else None), boxes
             # The device half of the input path (H2D copy of the batch -- 70 MB of JPEG coefficients at 32 images: ~3 ms of PCIe time --,
             # fv_jpeg_reconstruct_batch, fv_letterbox_batch) runs on its OWN stream: batch k+1 is staged while batch k's forward computes
             # (on one stream the copy sat in front of every forward: 16.7 ms per batch of 32 where the forward takes 12.8).
@@ -386,16 +391,17 @@ class FaceDetector(object):
 
             def stage(loaded):
                 raws, packed = loaded
+                keep = [] if _with_images else None
                 with torch.cuda.stream(side):
                     self.model.ctx.set_stream(side.cuda_stream)
                     try:
-                        x, geoms = letterbox_batch_device(self.model.ctx, raws, self.image_size, dev, packed=packed)
+                        x, geoms = letterbox_batch_device(self.model.ctx, raws, self.image_size, dev, packed=packed, keep=keep)
                     finally:
                         self.model.ctx.set_stream(main.cuda_stream)
                     ring.copied(packed[1] if isinstance(packed[0], str) else packed[0])   # event on the staging stream: the pinned slot is free after it
                     ev = torch.cuda.Event()
                     ev.record(side)
-                return raws, geoms, x, ev
+                return raws, geoms, x, ev, (keep[0] if keep else None)
 
             prev = None
             pending = one.submit(load, chunks[0])
@@ -403,10 +409,12 @@ class FaceDetector(object):
             if len(chunks) > 1:
                 pending = one.submit(load, chunks[1])
             for k, chunk in enumerate(chunks):
-                raws, geoms, x, ev = staged
+                raws, geoms, x, ev, imgs = staged
                 main.wait_event(ev)
                 x.record_stream(main)              # allocated on the staging stream, consumed on the compute stream
-                cur = (chunk, raws, geoms, self._detect_launch(x))
+                if imgs is not None:
+                    imgs[0].record_stream(main)
+                cur = (chunk, raws, geoms, self._detect_launch(x), imgs)
                 if k + 1 < len(chunks):            # the host waits for the decode of k+1 while the GPU runs batch k, then stages it beside it
                     loaded = pending.result()
                     if k + 2 < len(chunks):

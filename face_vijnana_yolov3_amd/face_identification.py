@@ -1,11 +1,14 @@
-"""FaceIdentifier: facial IDs from the Darknet-53 base, trained with a triplet loss.
+"""FaceIdentifier: facial IDs from the Darknet-53 base, trained with a triplet loss, and face identification against them.
 
 Port of the reference's `src/space/face_identification.py` (fi.py): the model (fi.py:318-345), the facial-ID extractor
 (`_make_fid_extractor`, fi.py:378-395), `train` (fi.py:616-643) over its two triplet sequences (fi.py:1490-1601 and the VGGFace2
-variant) and `main` (fi.py:1715-1760) for the modes implemented here.  The hot path is the C ABI (fv_fid_extract, fv_fid_train_step,
-fv_adam_step); this module holds the weights and drives it.  Not ported: create_db_fi / save_extracted_face (face cropping),
-make_facial_ids_db, register_facial_ids, evaluate, test and the reconstruction model.  Differences, documented in DESIGN.md:
-the BN moving-statistics update order of the three towers (a -> p -> n) and a zero gradient at a triplet distance of exactly 0."""
+variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `test` (fi.py:994-1153) and `main`
+(fi.py:1715-1760) for the modes implemented here.  The hot path is the C ABI (fv_fid_extract, fv_fid_train_step, fv_adam_step,
+fv_letterbox_crops, fv_fid_match); this module holds the weights and drives it.  Not ported: create_db_fi / save_extracted_face
+(the data mode), evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN moving-statistics update
+order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test() batching its frames and crops
+(same rows), fp64 match distances, and crops whose letterboxed side rounds to 0 being skipped (the reference's cv.resize raises)."""
+import glob
 import json
 import os
 import pickle
@@ -310,6 +313,126 @@ class TrainingSequenceVGGFace2(_TripletSequence):
     FACES_DIR = 'subject_faces_vggface2'
 
 
+# ----------------------------------------------------------------------------- identification helpers (fi.py:645-770, 994-1153)
+MAX_ROWS_PER_IMAGE = 60          # test() writes at most 60 rows per image (fi.py:1057-1058)
+
+
+def db_files(resource_type):
+    """(subject db csv, faces directory, facial-ID h5, registry pickle) of a resource type (fi.py:647-700, 702-770)."""
+    if resource_type == RESOURCE_TYPE_UCCS:
+        return 'subject_image_db.csv', 'subject_faces', 'subject_facial_ids.h5', 'ref_facial_id_db.pickle'
+    if resource_type == RESOURCE_TYPE_VGGFACE2:
+        return ('subject_image_vggface2_db.csv', 'subject_faces_vggface2', 'subject_facial_vggface2_ids.h5',
+                'ref_facial_id_vggface2_db.pickle')
+    raise ValueError('resource type is not valid.')
+
+
+def lb_side_ok(h, w, image_size):
+    """False when the letterboxed crop's short side rounds to 0 (int(h / w * S) as fi.py:1071-1093 computes it): cv.resize
+    would reject it; fv_letterbox_crops does."""
+    S = int(image_size)
+    return (int(h / w * S) if w >= h else int(w / h * S)) >= 1
+
+
+def crop_rect(box, h, w):
+    """The face crop of test() (fi.py:1061-1063): `image_o[(t - 1):(b - 1), (l - 1):(r - 1)]` with l, t, r, b = int() of the
+    projected box, Python slice semantics on an h x w image (a start of -1 -- a box on the top or left edge -- counts from the end
+    and leaves the crop empty).  -> (y0, x0, rows, cols), or None for an empty crop (the reference skips it, fi.py:1072-1073)."""
+    l, t, r, b = int(box.xmin), int(box.ymin), int(box.xmax), int(box.ymax)
+    ys = range(*slice(t - 1, b - 1).indices(int(h)))
+    xs = range(*slice(l - 1, r - 1).indices(int(w)))
+    if len(ys) == 0 or len(xs) == 0:
+        return None
+    return ys.start, xs.start, len(ys), len(xs)
+
+
+def crop_rects(boxes, h, w, image_size):
+    """crop_rect of every box, None also where the letterboxed side would round to 0 (a deviation: the reference's cv.resize
+    raises there)."""
+    out = []
+    for box in boxes:
+        c = crop_rect(box, h, w)
+        out.append(c if c is not None and lb_side_ok(c[2], c[3], image_size) else None)
+    return out
+
+
+def identification_rows(file_name, boxes, rects, best_index, best_dist, subject_ids, sim_th, limit=MAX_ROWS_PER_IMAGE):
+    """The rows test() writes for one image (fi.py:1057-1148): boxes in detector order, those without a crop skipped, a match
+    farther than sim_th skipped, at most `limit` rows written.  best_index / best_dist: per box (read only where a row can still be
+    written).  -> csv text, `str()` of each value exactly as fi.py:1143-1148."""
+    base = file_name.split('\\')[-1] if platform.system() == 'Windows' else file_name.split('/')[-1]
+    out = []
+    count = 1
+    for k, box in enumerate(boxes):
+        if count > limit:
+            break
+        if rects[k] is None:
+            continue
+        if best_dist[k] > sim_th:
+            continue
+        subject_id = subject_ids[int(best_index[k])]
+        out.append(base + ',' + str(subject_id) + ',' + str(box.xmin) + ',' + str(box.ymin) + ',')
+        out.append(str(box.xmax - box.xmin) + ',' + str(box.ymax - box.ymin) + ',' + str(box.get_score()) + '\n')
+        count += 1
+    return ''.join(out)
+
+
+def subject_mean(facial_ids):
+    """A subject's registered facial ID exactly as register_facial_ids computes it (fi.py:727): the pandas column mean."""
+    import pandas as pd
+    return np.asarray(pd.DataFrame(facial_ids).mean())
+
+
+def write_facial_ids_h5(path, names, facial_ids, subject_ids):
+    """subject_facial_ids.h5 (fi.py:650-668): one root dataset per face file (float32 (64,)) with attribute subject_id."""
+    from .hdf5_lite import write_hdf5
+    datasets, attrs = {}, {}
+    for name, fid, sid in zip(names, facial_ids, subject_ids):
+        datasets['/' + name] = np.asarray(fid, np.float32)
+        attrs['/' + name] = {'subject_id': np.int64(sid)}
+    write_hdf5(path, datasets, attrs)
+
+
+def read_facial_ids_h5(path):
+    """-> {face file: (facial ID, subject_id)} of write_facial_ids_h5's file."""
+    from .hdf5_lite import read_hdf5
+    data, attrs = read_hdf5(path)
+    return {k[1:]: (np.asarray(v), int(np.asarray(attrs[k]['subject_id']).reshape(-1)[0])) for k, v in data.items()}
+
+
+def fid_match(ctx, queries, registry):
+    """fv_fid_match: queries (n, 64), registry (m, 64) float32 CUDA tensors -> (best index int32, best distance float64) CUDA
+    tensors of n (stream-ordered)."""
+    q = queries.contiguous()
+    r = registry.contiguous()
+    n, m = int(q.shape[0]), int(r.shape[0])
+    idx = torch.empty(n, dtype=torch.int32, device=q.device)
+    dist = torch.empty(n, dtype=torch.float64, device=q.device)
+    if n == 0:
+        return idx, dist
+    if q.dtype != torch.float32 or r.dtype != torch.float32 or q.shape[1:] != (DENSE1_DIM,) or r.shape[1:] != (DENSE1_DIM,):
+        raise ValueError('fid_match expects float32 (n, 64) queries and (m, 64) registry')
+    ctx.check(lib().fv_fid_match(ctx.handle, ptr(q), n, ptr(r), m, ptr(idx), ptr(dist)), 'fv_fid_match')
+    return idx, dist
+
+
+def letterbox_crops(ctx, images, crops, image_size, out=None):
+    """fv_letterbox_crops: images = (device uint8 buffer, offsets, hw) of a batch (letterbox_batch_device's `keep`), crops = list
+    of (image index, y0, x0, rows, cols) -> (n, S, S, 3) float32 CUDA tensor."""
+    import ctypes
+    dbuf, offs, hw = images
+    n, ni, S = len(crops), len(offs), int(image_size)
+    if out is None:
+        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=dbuf.device)
+    if n == 0:
+        return out
+    flat = [int(v) for c in crops for v in c]
+    rc = lib().fv_letterbox_crops(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni,
+                                  (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
+    ctx.check(rc, 'fv_letterbox_crops')
+    return out
+
+
 # ----------------------------------------------------------------------------- FaceIdentifier (fi.py:288-643)
 class FaceIdentifier(object):
     """Face identifier on the Darknet-53 base of YOLOv3."""
@@ -402,20 +525,132 @@ class FaceIdentifier(object):
         print('Save the model.')
         self.model.save(self.MODEL_PATH)
 
+    # ------------------------------------------------------------------ facial-ID database (fi.py:645-770)
+    def _extract_db(self):
+        """Facial IDs of every face crop of the subject db (subject -1 skipped), in groupby order -> (names, subject ids, IDs).
+        The crops go through the extractor in chunks of at most Engine.max_infer_batch(S) images, mixed across subjects: an
+        image's ID does not depend on the rest of its batch (fv_fid_extract), so this equals the reference's one predict per
+        subject."""
+        import pandas as pd
+        from .engine import Engine
+        db_file, faces_dir, _h5, _pk = db_files(self.conf['resource_type'])
+        db = pd.read_csv(db_file).iloc[:, 1:]
+        names, sids = [], []
+        for subject_id, df in db.groupby('subject_id'):
+            if subject_id == -1:
+                continue
+            for ff in list(df.iloc[:, 1]):
+                names.append(ff); sids.append(subject_id)
+        step = max(1, Engine.max_infer_batch(self.image_size))
+        ids = []
+        for i in range(0, len(names), step):
+            x = np.asarray([_imread(os.path.join(self.raw_data_path, faces_dir, ff)) for ff in names[i:i + step]])
+            ids.append(self.fid_extractor.predict(x))
+        ids = np.concatenate(ids) if ids else np.zeros((0, DENSE1_DIM), np.float32)
+        self._db_cache = (names, sids, ids)
+        return names, sids, ids
+
+    def make_facial_ids_db(self):
+        """fi.py:645-700: subject_facial_ids.h5 (vggface2: subject_facial_vggface2_ids.h5), one dataset per face file."""
+        names, sids, ids = self._extract_db()
+        write_facial_ids_h5(db_files(self.conf['resource_type'])[2], names, ids, sids)
+
+    def register_facial_ids(self):
+        """fi.py:702-770: every subject's mean facial ID, pickled as {subject_id: vector} (keys in groupby order) to
+        ref_facial_id_db.pickle (vggface2: ref_facial_id_vggface2_db.pickle).  Right after make_facial_ids_db in the same process
+        the IDs it extracted are reused."""
+        names, sids, ids = self._db_cache if getattr(self, '_db_cache', None) is not None else self._extract_db()
+        self._db_cache = None
+        reg, order = {}, []
+        for k, sid in enumerate(sids):
+            if sid not in reg:
+                reg[sid] = []; order.append(sid)
+            reg[sid].append(ids[k])
+        db = {sid: subject_mean(np.asarray(reg[sid])) for sid in order}
+        with open(db_files(self.conf['resource_type'])[3], 'wb') as f:
+            pickle.dump(db, f)
+
+    # ------------------------------------------------------------------ test (fi.py:994-1153)
+    def test(self):
+        """Detect faces in every <test_path>/*.jpg (sorted), identify each against ref_facial_id_db.pickle and write
+        `name,subject_id,xmin,ymin,w,h,score` rows to output_file_path.  The detector's pipelined loop (FaceDetector._detect_files)
+        runs the frames in batches; per batch the face crops are cut and letterboxed on the device from the batch's decoded images
+        (fv_letterbox_crops), extracted in chunks of at most Engine.max_infer_batch(S) (fv_fid_extract) and matched against the
+        registry in one launch (fv_fid_match).  Rows, order and text as the reference's per-crop loop."""
+        from .engine import Engine
+        fd_size = int(self._full_conf['fd_conf']['nn_arch']['image_size'])
+        if fd_size != self.image_size:
+            raise ValueError('fd_conf.nn_arch.image_size (%d) must equal fi_conf.nn_arch.image_size (%d): the reference letterboxes '
+                             'the frames with the identifier\'s size for the detector' % (fd_size, self.image_size))
+        test_path = self.conf['test_path']
+        out_path = self.conf['output_file_path']
+        with open('ref_facial_id_db.pickle', 'rb') as f:
+            db = pickle.load(f)
+        subject_ids = list(db.keys())
+        if not subject_ids:
+            raise ValueError('ref_facial_id_db.pickle holds no registered facial IDs')
+        m = self.model
+        registry = torch.from_numpy(np.asarray([db[k] for k in subject_ids], np.float32)).to(m.dev)   # uploaded once
+        sim_th = self.hps['sim_th']
+        S = self.image_size
+        step = max(1, Engine.max_infer_batch(S))
+        files = sorted(glob.glob(os.path.join(test_path, '*.jpg')))
+
+        def flush(group, f):
+            images = group[0][3][0]
+            hw = images[2]
+            rects = [crop_rects(it[2], hw[2 * it[3][1]], hw[2 * it[3][1] + 1], S) for it in group]
+            crops = [(it[3][1],) + r for it, rs in zip(group, rects) for r in rs if r is not None]
+            ids = []
+            for c0 in range(0, len(crops), step):
+                x = letterbox_crops(m.ctx, images, crops[c0:c0 + step], S)
+                ids.append(m.extract_device(x))
+            if crops:
+                bi, bd = fid_match(m.ctx, torch.cat(ids), registry)
+                bi, bd = bi.cpu().numpy(), bd.cpu().numpy()
+            k = 0
+            for it, rs in zip(group, rects):
+                idx = np.full(len(rs), -1, np.int64); dist = np.full(len(rs), np.inf)
+                for j, r in enumerate(rs):
+                    if r is not None:
+                        idx[j], dist[j] = bi[k], bd[k]; k += 1
+                f.write(identification_rows(it[0], it[2], rs, idx, dist, subject_ids, sim_th))
+
+        with open(out_path, 'w') as f:
+            group = []
+            for item in self.fd._detect_files(files, need_raw=False, _with_images=True):
+                if group and group[0][3][0] is not item[3][0]:
+                    flush(group, f); group = []
+                group.append(item)
+            if group:
+                flush(group, f)
+
 
 def main():
-    """Reads ./face_vijnana_yolov3.json (Windows: _win) and dispatches on fi_conf.mode (fi.py:1715-1760).  'train' trains and saves
-    face_identifier.h5; the facial-ID database steps the reference runs after it (make_facial_ids_db, register_facial_ids) and
-    every other mode are not implemented here."""
+    """Reads ./face_vijnana_yolov3.json (Windows: _win) and dispatches on fi_conf.mode (fi.py:1715-1760):
+      train   trains and saves face_identifier.h5, then builds the facial-ID database (make_facial_ids_db, register_facial_ids),
+              as fi.py:1734-1743 does;
+      fid_db  make_facial_ids_db, then register_facial_ids -- the reference leaves the second call commented out, but nothing else
+              would register the IDs of a loaded model, and test() reads the registry;
+      test    test() -> output_file_path.
+    'evaluate' and 'data' are not implemented here."""
     name = 'face_vijnana_yolov3_win.json' if platform.system() == 'Windows' else 'face_vijnana_yolov3.json'
     with open(name, 'r') as f:
         conf = json.load(f)
     mode = conf['fi_conf']['mode']
-    if mode != 'train':
-        raise NotImplementedError('fi_conf.mode %r is not implemented (available: train)' % mode)
+    if mode not in ('train', 'fid_db', 'test'):
+        raise NotImplementedError('fi_conf.mode %r is not implemented (available: train, fid_db, test)' % mode)
     fi = FaceIdentifier(conf)
     ts = time.time()
-    fi.train()
+    if mode == 'train':
+        fi.train()
+        fi.make_facial_ids_db()
+        fi.register_facial_ids()
+    elif mode == 'fid_db':
+        fi.make_facial_ids_db()
+        fi.register_facial_ids()
+    else:
+        fi.test()
     print('Elasped time: {0:f}s'.format(time.time() - ts))
 
 

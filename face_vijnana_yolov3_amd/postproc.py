@@ -148,9 +148,10 @@ def pack_images(raws, pin=True, ring=None):
     return buf, offs, hw
 
 
-def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None):
+def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None, keep=None):
     """list of uint8 HxWx3 arrays -> ((n,S,S,3) float32 CUDA tensor, [geometry tuples]) in ONE launch
-    (fv_letterbox_batch); `packed` = the result of pack_images when a loader thread prepared it."""
+    (fv_letterbox_batch); `packed` = the result of pack_images when a loader thread prepared it.  keep: a list that receives
+    (device uint8 buffer, offsets, hw) -- the batch's decoded images on the device, for a later fv_letterbox_crops."""
     import ctypes
     import torch
     if packed is not None and isinstance(packed[0], str) and packed[0] == 'jpeg':
@@ -170,5 +171,7 @@ def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None)
     geom = (ctypes.c_int32 * (6 * n))()
     rc = lib().fv_letterbox_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, ptr(out), geom)
     ctx.check(rc, 'fv_letterbox_batch')
+    if keep is not None:
+        keep.append((dbuf, list(offs), list(hw)))
     geoms = [(hw[2 * i], hw[2 * i + 1], geom[6 * i + 2], geom[6 * i + 3], geom[6 * i + 4], geom[6 * i + 5]) for i in range(n)]
     return out, geoms

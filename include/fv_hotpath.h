@@ -305,6 +305,15 @@ int fv_letterbox(fv_ctx* ctx, const uint8_t* src, int h, int w, int image_size, 
  * n calls of fv_letterbox. */
 int fv_letterbox_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
                        int image_size, float* dst, int32_t* geom);
+/* Crop + letterbox of many face rectangles in one call (FaceIdentifier.test, fi.py:1061-1101: `image_o[(t-1):(b-1), (l-1):(r-1)]`,
+ * /255, cv.resize(INTER_CUBIC), cv.copyMakeBorder).  packed / offsets / hw: the batch's n_img decoded images as for
+ * fv_letterbox_batch.  crops: HOST int32 [n][5] records (image index, y0, x0, h, w), each inside its image.  dst [n][S][S][3].
+ * Crop c is letterboxed as fv_letterbox would letterbox a contiguous copy of those h x w pixels -- same geometry, same bicubic
+ * weights, same fp64 source coordinates, the border replicated at the crop's edges: bit-identical to that call.  Any number of
+ * crops (chunked inside the call).  A crop outside its image, or one whose letterboxed side rounds to 0, is FV_ERR_INVALID and
+ * nothing is enqueued. */
+int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                       const int32_t* crops, int n, int image_size, float* dst);
 
 /* ------------------------------------------------------------------ JPEG decode, split host / device
  * (replaces `imread` of fd.py:112, 656, 798 for baseline / extended-sequential Huffman JPEGs with 1 or 3
@@ -373,6 +382,13 @@ int fv_fid_train_step(fv_ctx* ctx, const float* params, float* bn_state, const f
 int64_t fv_fid_dense_partial_floats(int rows, int64_t F);
 int fv_fid_dense_l2(fv_ctx* ctx, const float* x, int rows, int64_t F, const float* w, const float* bias, float* partial,
                     float* pre, float* out);
+/* Nearest registered facial ID (FaceIdentifier.test, fi.py:1117-1127: `norm(anchor - reg)` per subject, then np.argmin):
+ * queries [n][64] and registry [m][64] float32 (device; registry 16-byte aligned) -> best_index int32 [n] and best_dist
+ * float64 [n] (device).  Distance: sqrt of the fp64 sum, in dimension order 0..63, of the squared fp64 differences.  The
+ * winner is the lexicographic minimum of (distance, index) -- equal distances go to the lowest index, as np.argmin -- so the
+ * result does not depend on n, on the rest of the batch or on how the work is split: any split of the queries gives the same
+ * bits.  No atomics.  m == 0 is FV_ERR_INVALID.  The similarity threshold (hps.sim_th) is applied by the caller. */
+int fv_fid_match(fv_ctx* ctx, const float* queries, int n, const float* registry, int m, int32_t* best_index, double* best_dist);
 
 /* ------------------------------------------------------------------ secondary: three-scale YOLOv3
  * (SURVEY 8a-17/18).  The reference builds this graph in make_yolov3_model (yd.py:217-311) and
