@@ -2,12 +2,16 @@
 """Headline benchmark: FaceDetector training images/sec at 416x416, 40 images per GPU
 (BASELINE.json configs[1]; N GPUs -> global batch 40*N, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = forward (training-mode BN) + MSE + backward + (N>1: RCCL all-reduce of the 40.64 M fp32
 gradients, bucketed and overlapped with backward) + Keras-formula Adam, on synthetic inputs that
 are already resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line:
+`value`, `ms_per_step`, the median and the step's TFLOP/s.  Everything below runs only with --full,
+after the timed steps, and adds its keys to the same line.
 
 `roofline`: the dominant kernel FAMILY is the 128x128-tile fp32-MFMA implicit-GEMM conv -- forward and data-gradient of every layer
 with >= 128 output channels, 92 launches per step: conv_kernel<128,2,4,false> (8 waves per workgroup; <128,2,2,false> under option
@@ -74,15 +78,17 @@ def parse():
     ap.add_argument('--rendezvous-only', action='store_true', help='ranks only rendezvous, all-reduce one number and exit (launcher rehearsal)')
     ap.add_argument('--batch', type=int, default=PER_GPU_BATCH, help='per-GPU batch (default 40 = BASELINE config)')
     ap.add_argument('--image-size', type=int, default=IMAGE_SIZE)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every other section of the line (the options below select among them)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-batch', type=int, default=8)
-    ap.add_argument('--profile-steps', type=int, default=2)
+    ap.add_argument('--profile-steps', type=int, default=2, help='--full: instrumented steps for the roofline and per-kernel tables')
     ap.add_argument('--no-overlap', action='store_true', help='serialise wgrad on the main stream (A/B aid)')
     ap.add_argument('--no-tail-split', action='store_true', help='conv launches without the tail split (A/B aid)')
-    ap.add_argument('--no-detect', action='store_true', help='skip the detect-path measurement (PMC passes)')
-    ap.add_argument('--no-rccl-rehearsal', action='store_true', help='N=1: skip the world-size-1 RCCL group rehearsal')
-    ap.add_argument('--no-loader', action='store_true', help='skip the loader-inclusive measurement')
-    ap.add_argument('--no-three-scale', action='store_true', help='skip the three-scale training measurement')
+    ap.add_argument('--no-detect', action='store_true', help='--full: skip the detect-path measurement (PMC passes)')
+    ap.add_argument('--no-rccl-rehearsal', action='store_true', help='--full, N=1: skip the world-size-1 RCCL group rehearsal')
+    ap.add_argument('--no-loader', action='store_true', help='--full: skip the loader-inclusive measurement')
+    ap.add_argument('--no-three-scale', action='store_true', help='--full: skip the three-scale training measurement')
     ap.add_argument('--loader-steps', type=int, default=16)
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)')
@@ -683,6 +689,41 @@ def main():
         dump_outputs(args.dump_outputs, eng, loss)   # before any later section steps the weights again
     initial = None
 
+    out = None
+    if rank == 0:
+        train_flops = train_flops_per_image(S)       # fwd + wgrad(all) + dgrad(all but conv_0)
+        ips = world * B * args.steps / dt
+        out = {
+            'metric': 'training images/sec (%dx%d bs=%d per GPU)' % (S, S, B), 'value': round(ips, 2), 'unit': 'images/sec',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
+            'median_ms_per_step': round(median_ms, 3), 'images_per_sec_at_median': round(world * B / (median_ms * 1e-3), 2),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'config': {'workload': 'FaceDetector mode=train image_size=%d batch_size=%d per GPU, synthetic UCCS-shaped '
+                                   'batch, random-init Darknet-53 base + %dx%dx6 head, MSE, Adam lr 1e-4 b1=b2=0.99' % (S, B, S // 32, S // 32),
+                       'global_batch': world * B, 'parallelism': 'dp%d' % world},
+            'loss': loss_v,
+            'step_tflops_per_gpu': round(train_flops * B * args.steps / dt / 1e12, 2),
+            'step_frac_of_fp32_mfma_peak': round(train_flops * B * args.steps / dt / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
+        }
+    if args.full:
+        more = full_sections(args, eng, trainer, step, x, y, dt, median_ms, world, rank, local_rank)
+        if rank == 0:
+            out.update(more)
+    trainer.shutdown()
+    if rank == 0:
+        sys.stdout.flush()
+        os.write(result_fd, (json.dumps(out) + '\n').encode())
+
+
+def full_sections(args, eng, trainer, step, x, y, dt, median_ms, world, rank, local_rank):
+    """--full: everything the line reports beside the headline, measured after the timed steps (and after --dump-outputs has
+    written them).  Every rank calls it: the communication diagnostics and the instrumented steps contain collectives.
+    Returns rank 0's keys of the line, None on the other ranks."""
+    import torch
+    import torch.distributed as dist
+    from face_vijnana_yolov3_amd.parallel import DataParallelTrainer
+    B, S = args.batch, args.image_size
+
     # ---- N > 1: what the communication costs (every rank measures, rank 0 reports all of them)
     multi = None
     if world > 1:
@@ -805,19 +846,7 @@ def main():
                            tflops=round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 2) if v['flops'] and v['ms'] else None,
                            gbps=round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['ms'] else None)
                    for k, v in sorted(prof.items(), key=lambda kv: -kv[1]['ms'])}
-        train_flops = train_flops_per_image(S)       # fwd + wgrad(all) + dgrad(all but conv_0)
-        ips = world * B * args.steps / dt
         out = {
-            'metric': 'training images/sec (%dx%d bs=%d per GPU)' % (S, S, B), 'value': round(ips, 2), 'unit': 'images/sec',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
-            'median_ms_per_step': round(median_ms, 3), 'images_per_sec_at_median': round(world * B / (median_ms * 1e-3), 2),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': 'FaceDetector mode=train image_size=%d batch_size=%d per GPU, synthetic UCCS-shaped '
-                                   'batch, random-init Darknet-53 base + %dx%dx6 head, MSE, Adam lr 1e-4 b1=b2=0.99' % (S, B, S // 32, S // 32),
-                       'global_batch': world * B, 'parallelism': 'dp%d' % world},
-            'loss': loss_v,
-            'step_tflops_per_gpu': round(train_flops * B * args.steps / dt / 1e12, 2),
-            'step_frac_of_fp32_mfma_peak': round(train_flops * B * args.steps / dt / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
             'roofline': roofline,
             'roofline_overlapped': (lambda d: None if not d or not d['ms'] else dict(
                 achieved=round(d['flops'] / (d['ms'] * 1e-3) / 1e12, 2), avg_launch_ms=round(d['ms'] / d['launches'], 4)))(dominant(prof_ov)[1]),
@@ -838,10 +867,7 @@ def main():
             out['cpu_baseline'] = cpu_baseline(args.cpu_batch, S)
         else:
             out['cpu_baseline'] = None
-    trainer.shutdown()
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(result_fd, (json.dumps(out) + '\n').encode())
+    return out
 
 
 if __name__ == '__main__':

@@ -2,7 +2,7 @@
 DataParallelTrainer's bucket path -- fv_bucket_fn callbacks -> event -> communication stream -> dist.all_reduce (RCCL) -> wait ->
 Adam -- and must reproduce the plain single-GPU step (reference behaviour replaced: keras.utils.multi_gpu_model,
 face_detection.py:358-371, 612-619).  Runs in a child process so that the group does not outlive the test; also `bench.py
---gpus 1 --spawn` (the self-launcher with real devices) must print the driver's JSON line with `multi_gpu.rccl_ranks` == 1."""
+--gpus 1 --spawn --full` (the self-launcher with real devices) must print the driver's JSON line with `multi_gpu.rccl_ranks` == 1."""
 import json
 import os
 import subprocess
@@ -119,7 +119,7 @@ def test_world_size_one_nccl_group_runs_the_bucketed_all_reduce():
 def test_bench_through_its_own_launcher_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--spawn', '--steps', '3', '--warmup', '1', '--batch', '8',
-                        '--image-size', '224', '--no-cpu-baseline', '--no-detect', '--no-loader', '--no-three-scale', '--profile-steps', '1'],
+                        '--image-size', '224', '--full', '--no-cpu-baseline', '--no-detect', '--no-loader', '--no-three-scale', '--profile-steps', '1'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
