@@ -129,53 +129,27 @@ class FaceDetector(object):
         self.model.bn_zero_debias = bool(conf.get('bn_zero_debias', True))
         if self.model_loading:
             self.model.load(self.MODEL_PATH)
-        elif self.three_scale:
-            self._load_base_three_scale()
         else:
             self._load_base()
-            self._init_head()
+            if not self.three_scale:
+                self._init_head()
 
     # ------------------------------------------------------------------ model construction
     def _load_base(self):
-        """YOLOV3Base (fd.py:384-600): cached base file, else Darknet weights, else -- because
-        neither can be downloaded offline -- synthetic initialisation (announced)."""
-        from . import weights
-        eng = self.model
-        if self.conf.get('yolov3_base_model_load') and os.path.exists(self.BASE_MODEL_PATH):
-            eng.load(self.BASE_MODEL_PATH, require_all=False)        # the base file holds no head (fd.py:393-396)
-        elif os.path.exists(self.DARKNET_WEIGHTS_PATH):
-            p, s = weights.read_darknet_base(self.DARKNET_WEIGHTS_PATH, eng.layers, eng.n_params, eng.n_state)
-            eng.set_params(p, s)
-            if self.rank == 0:                                       # base.save('yolov3_base.h5') (fd.py:596-598)
-                weights.write_keras_h5(self.BASE_MODEL_PATH, eng.layers[:-1], p, s, nested=None)
-        else:
-            print('FaceDetector: neither %s nor %s found; using synthetic base weights'
-                  % (self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH))
-            eng.init_synthetic(seed=7)
-
-    def _load_base_three_scale(self):
-        """Three-scale model: layers 75..105 random-init (BN layers ~ N(0, 2/fan_in), detection convs glorot-uniform, zero
-        bias), the 52 base layers from the cached base file / the Darknet file when present (same flat layout as Engine)."""
+        """YOLOV3Base (fd.py:384-600): cached base file, else Darknet weights (then rank 0 writes the base file, fd.py:596-598),
+        else -- because neither can be downloaded offline -- synthetic initialisation (announced).  The three-scale model
+        random-initialises its layers 75..105 first (BN layers ~ N(0, 2/fan_in), detection convs glorot-uniform, zero bias), lays
+        the base over them when one is found, and writes no base file."""
         from . import weights
         m = self.model
-        m.init_synthetic(seed=7)
-        base = m.layers[:52]
-        n_p = base[-1]['beta_off'] + base[-1]['cout']; n_s = base[-1]['var_off'] + base[-1]['cout']
-        if self.conf.get('yolov3_base_model_load') and os.path.exists(self.BASE_MODEL_PATH):
-            from .hdf5_lite import is_hdf5, read_hdf5
-            if is_hdf5(self.BASE_MODEL_PATH):
-                p, st, _found = weights.from_keras_datasets(read_hdf5(self.BASE_MODEL_PATH)[0], base, n_p, n_s)
-                m.load_base(p, st)
-            else:
-                with open(self.BASE_MODEL_PATH, 'rb') as f:
-                    d = np.load(f)
-                    m.load_base(d['params'][:n_p], d['state'][:n_s])
-        elif os.path.exists(self.DARKNET_WEIGHTS_PATH):
-            p, st = weights.read_darknet_base(self.DARKNET_WEIGHTS_PATH, base, n_p, n_s)
-            m.load_base(p, st)
-        else:
-            print('FaceDetector: neither %s nor %s found; using synthetic base weights'
-                  % (self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH))
+        if self.three_scale:
+            m.init_synthetic(seed=7)
+        base = weights.load_base('FaceDetector', m.layers, self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH,
+                                 self.conf.get('yolov3_base_model_load'), save_base=not self.three_scale and self.rank == 0)
+        if base is not None:
+            m.set_base(*base)
+        elif not self.three_scale:
+            m.init_synthetic(seed=7)
 
     @property
     def YOLOV3Base(self):
@@ -191,9 +165,7 @@ class FaceDetector(object):
             eng = getattr(self, '_base_engine', None)
             if eng is None:
                 eng = self._base_engine = Engine(self.model.ctx.device)     # one Engine, reused: only the weights are refreshed per access
-            nb = eng.layers[-2]
-            n_p, n_s = nb['beta_off'] + nb['cout'], nb['var_off'] + nb['cout']
-            eng.params[:n_p].copy_(self.model.params[:n_p]); eng.state[:n_s].copy_(self.model.state[:n_s])
+            eng.set_base(self.model.params, self.model.state)
             return YoloV3BaseModel(eng)
         return YoloV3BaseModel(self.model)
 

@@ -19,11 +19,13 @@ from random import shuffle
 import numpy as np
 import torch
 
+from . import weights
 from ._lib import Context, FvError, lib, ptr
+from .model import Model
+from .weights import NUM_BASE_LAYERS
 
 ALPHA = 0.2                     # fi.py:66
 DENSE1_DIM = 64                 # the loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76)
-NUM_BASE_LAYERS = 52
 RESOURCE_TYPE_UCCS = 'uccs'
 RESOURCE_TYPE_VGGFACE2 = 'vggface2'
 
@@ -45,50 +47,23 @@ def dense_offsets(image_size):
     return k, k + feature_size(image_size) * DENSE1_DIM
 
 
-class FidModel(object):
+class FidModel(Model):
     """The device-side model: the flat parameter vector of fv_fid_param_count (base layers at their fv_layer offsets, then the
     dense kernel and bias), the BN moving statistics (fv_state_count), the Adam state, and the calls into the library."""
 
+    BN_UPDATES_PER_STEP = 3         # one per tower
+
     def __init__(self, image_size, device=0):
         self.image_size = int(image_size)
-        self.ctx = Context(device)
-        self.dev = torch.device('cuda', device)
-        self.layers = base_layers()
-        self.n_params = int(lib().fv_fid_param_count(self.image_size))
-        if self.n_params <= 0:
+        n_params = int(lib().fv_fid_param_count(self.image_size))
+        if n_params <= 0:
             raise ValueError('image_size must be a positive multiple of 32')
-        self.n_state = int(lib().fv_state_count())
+        super(FidModel, self).__init__(Context(device), base_layers(), n_params, lib().fv_state_count())
         self.F = feature_size(self.image_size)
         self.kernel_off, self.bias_off = dense_offsets(self.image_size)
-        self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.dev)
-        self.state = torch.zeros(self.n_state, dtype=torch.float32, device=self.dev)
-        self.grads = self.m = self.v = None
-        self.iterations = 0
         self.bn_zero_debias = True      # Keras 2.2.4's zero-debiased BN update (Engine.bn_zero_debias)
-        self.bn_updates = 0             # BN moving-statistics updates applied so far: three per training step (one per tower)
-        self._ws = {}
-        self._loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
 
     # ------------------------------------------------------------------ parameters
-    def set_base(self, params, state):
-        """The 52 base layers from a flat vector in the fv_layer layout (the detector's or a base file's) and the BN state."""
-        n = self.kernel_off
-        self.params[:n].copy_(torch.as_tensor(np.asarray(params)[:n], dtype=torch.float32))
-        self.state.copy_(torch.as_tensor(np.asarray(state), dtype=torch.float32).reshape(-1))
-
-    def init_synthetic_base(self, seed=7):
-        """Engine.init_synthetic restricted to the base: kernels ~ N(0, 2/fan_in), gamma 1, beta 0, moving mean 0 / var 1."""
-        g = torch.Generator(device='cpu').manual_seed(seed)
-        p = torch.zeros(self.kernel_off, dtype=torch.float32)
-        s = torch.zeros(self.n_state, dtype=torch.float32)
-        for d in self.layers:
-            k, cin, cout = d['ksize'], d['cin'], d['cout']
-            n = cout * k * k * cin
-            p[d['w_off']:d['w_off'] + n] = torch.randn(n, generator=g) * float(np.sqrt(2.0 / (k * k * cin)))
-            p[d['gamma_off']:d['gamma_off'] + cout] = 1.0
-            s[d['var_off']:d['var_off'] + cout] = 1.0
-        self.set_base(p.numpy(), s.numpy())
-
     def init_dense(self, seed=0):
         """Keras defaults of Dense(64) (fi.py:327): glorot_uniform kernel, limit sqrt(6 / (F + 64)), zero bias."""
         g = torch.Generator().manual_seed(seed)
@@ -103,16 +78,8 @@ class FidModel(object):
     def dense_bias(self):
         return self.params[self.bias_off:self.bias_off + DENSE1_DIM]
 
-    # ------------------------------------------------------------------ workspaces
-    def _workspace(self, batch, training):
-        key = (int(batch), bool(training))
-        if key not in self._ws:
-            n = int(lib().fv_fid_workspace_bytes(int(batch), self.image_size, 1 if training else 0))
-            if n == 0:
-                raise FvError('unsupported batch/image_size %r' % ((batch, self.image_size),))
-            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}   # one per mode
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        return self._ws[key]
+    def _workspace_bytes(self, batch, image_size, training):
+        return lib().fv_fid_workspace_bytes(batch, image_size, training)
 
     def _as_input(self, x):
         if isinstance(x, np.ndarray) and x.dtype == np.uint8:
@@ -130,14 +97,11 @@ class FidModel(object):
     # ------------------------------------------------------------------ extraction (fi.py:378-395)
     def extract_device(self, x):
         """x (B,S,S,3) in [0,1] (uint8 crops are divided by 255, fi.py:1577) -> (B,64) facial IDs, float32 CUDA tensor."""
-        from .engine import Engine
-        x = self._as_input(x)
+        return self._in_parts(self._extract, self._as_input(x))
+
+    def _extract(self, x):
         B = x.shape[0]
-        cap = Engine.max_infer_batch(self.image_size)
-        if B > cap >= 1:
-            step = cap // 8 * 8 if cap >= 8 else cap
-            return torch.cat([self.extract_device(x[i:i + step]) for i in range(0, B, step)])
-        ws = self._workspace(B, False)
+        ws = self._workspace(B, self.image_size, False)
         fid = torch.empty((B, DENSE1_DIM), dtype=torch.float32, device=self.dev)
         rc = lib().fv_fid_extract(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), B, self.image_size, ptr(ws), ws.numel(),
                                   ptr(fid))
@@ -145,12 +109,6 @@ class FidModel(object):
         return fid
 
     # ------------------------------------------------------------------ training
-    def ensure_optimizer(self):
-        if self.grads is None:
-            self.grads = torch.zeros_like(self.params)
-            self.m = torch.zeros_like(self.params)
-            self.v = torch.zeros_like(self.params)
-
     def forward_backward(self, xa, xp, xn):
         """Triplet forward + loss + backward (fv_fid_train_step): gradients in self.grads, BN moving statistics updated a -> p -> n;
         returns the loss as a 1-element CUDA tensor (no host sync)."""
@@ -159,19 +117,9 @@ class FidModel(object):
         B = xa.shape[0]
         if xp.shape != xa.shape or xn.shape != xa.shape:
             raise ValueError('anchor, positive and negative batches differ in shape')
-        ws = self._workspace(B, True)
-        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
-        rc = lib().fv_fid_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(xa), ptr(xp), ptr(xn), B, self.image_size,
-                                     ptr(ws), ws.numel(), ptr(self.grads), ptr(self._loss))
-        self.ctx.check(rc, 'fv_fid_train_step')
-        self.bn_updates += 3
-        return self._loss
-
-    def adam_step(self, lr, beta_1, beta_2, decay=0.0, eps=1e-7):
-        rc = lib().fv_adam_step(self.ctx.handle, ptr(self.params), ptr(self.grads), ptr(self.m), ptr(self.v), self.n_params,
-                                self.iterations, float(lr), float(beta_1), float(beta_2), float(eps), float(decay))
-        self.ctx.check(rc, 'fv_adam_step')
-        self.iterations += 1
+        ws = self._workspace(B, self.image_size, True)
+        return self._train_call('fv_fid_train_step', ptr(xa), ptr(xp), ptr(xn), B, self.image_size, ptr(ws), ws.numel(),
+                                ptr(self.grads), ptr(self._loss))
 
     def train_on_batch(self, xa, xp, xn, lr, beta_1, beta_2, decay=0.0):
         loss = self.forward_backward(xa, xp, xn)
@@ -182,24 +130,14 @@ class FidModel(object):
     def save(self, path):
         """face_identifier.h5 in Keras' weight layout: the base as the nested model 'base', then dense1/kernel:0 [F][64] and
         dense1/bias:0; this build's Adam state and step counts under /fv."""
-        from . import weights
-        extras = dict(iterations=np.int64(self.iterations), bn_updates=np.int64(self.bn_updates))
-        if self.m is not None:
-            extras['adam_m'] = self.m.cpu().numpy(); extras['adam_v'] = self.v.cpu().numpy()
-        p = self.params.cpu().numpy()
-        dense = [('dense1/kernel:0', p[self.kernel_off:self.bias_off].reshape(self.F, DENSE1_DIM)),
-                 ('dense1/bias:0', p[self.bias_off:self.bias_off + DENSE1_DIM])]
-        weights.write_keras_h5(path, self.layers, p, self.state.cpu().numpy(), nested='base', extras=extras,
-                               more_groups={'dense1': dense})
+        dense = [('dense1/kernel:0', self.dense_kernel().cpu().numpy()), ('dense1/bias:0', self.dense_bias().cpu().numpy())]
+        self._save_h5(path, 'base', {'dense1': dense}, bn_updates=np.int64(self.bn_updates))
 
     def load(self, path):
-        from . import weights
-        from .hdf5_lite import read_hdf5
-        datasets, _ = read_hdf5(path)
-        p, st, found = weights.from_keras_datasets(datasets, self.layers, self.n_params, self.n_state)
-        missing = sorted(set(weights.expected_keras_tensors(self.layers)) - set(found))
-        if missing:
-            raise FvError('%s lacks %d base tensors, e.g. %r' % (path, len(missing), missing[:3]))
+        fv = self._load(path, read_more=self._read_dense)
+        self.bn_updates = int(fv.get('bn_updates', 0))
+
+    def _read_dense(self, path, datasets, p):
         kern = [k for k in datasets if k.endswith('/dense1/kernel:0')]
         bias = [k for k in datasets if k.endswith('/dense1/bias:0')]
         if len(kern) != 1 or len(bias) != 1:
@@ -211,14 +149,6 @@ class FidModel(object):
                           % (path, K.shape, b.shape, self.F, DENSE1_DIM, DENSE1_DIM))
         p[self.kernel_off:self.bias_off] = K.reshape(-1)
         p[self.bias_off:self.bias_off + DENSE1_DIM] = b
-        self.params.copy_(torch.from_numpy(p))
-        self.state.copy_(torch.from_numpy(st))
-        self.iterations = int(datasets['/fv/iterations']) if '/fv/iterations' in datasets else 0
-        self.bn_updates = int(datasets['/fv/bn_updates']) if '/fv/bn_updates' in datasets else 0
-        if '/fv/adam_m' in datasets and '/fv/adam_v' in datasets:
-            self.ensure_optimizer()
-            self.m.copy_(torch.from_numpy(np.asarray(datasets['/fv/adam_m'])))
-            self.v.copy_(torch.from_numpy(np.asarray(datasets['/fv/adam_v'])))
 
 
 class FidExtractor(object):
@@ -480,25 +410,12 @@ class FaceIdentifier(object):
     def _load_base(self):
         """YOLOV3Base (fi.py:398-614), as FaceDetector._load_base: yolov3_base.h5 when yolov3_base_model_load is set, else the
         Darknet file (then yolov3_base.h5 is written, fi.py:612), else synthetic weights (announced)."""
-        from . import weights
-        m = self.model
-        if self.conf.get('yolov3_base_model_load') and os.path.exists(self.BASE_MODEL_PATH):
-            from .hdf5_lite import is_hdf5, read_hdf5
-            if is_hdf5(self.BASE_MODEL_PATH):
-                p, st, _found = weights.from_keras_datasets(read_hdf5(self.BASE_MODEL_PATH)[0], m.layers, m.kernel_off, m.n_state)
-            else:
-                with open(self.BASE_MODEL_PATH, 'rb') as f:
-                    d = np.load(f)
-                    p, st = d['params'], d['state']
-            m.set_base(p, st)
-        elif os.path.exists(self.DARKNET_WEIGHTS_PATH):
-            p, st = weights.read_darknet_base(self.DARKNET_WEIGHTS_PATH, m.layers, m.kernel_off, m.n_state)
-            m.set_base(p, st)
-            weights.write_keras_h5(self.BASE_MODEL_PATH, m.layers, p, st, nested=None)
+        base = weights.load_base('FaceIdentifier', self.model.layers, self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH,
+                                 self.conf.get('yolov3_base_model_load'), save_base=True)
+        if base is None:
+            self.model.init_synthetic(seed=7)
         else:
-            print('FaceIdentifier: neither %s nor %s found; using synthetic base weights'
-                  % (self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH))
-            m.init_synthetic_base(seed=7)
+            self.model.set_base(*base)
 
     def train_on_batch(self, xa, xp, xn):
         """One Keras train_on_batch of the triplet model: fv_fid_train_step, then Adam with fi_conf.hps.  Returns the loss (float)."""

@@ -5,9 +5,12 @@ major, minor, revision, then 8 more bytes if major*10+minor >= 2 (both < 1000) e
 float32 stream; per conv in index order: [beta, gamma, mean, var] (BN layers) or [bias], then the
 kernel stored (cout, cin, kh, kw).  FaceDetector only consumes convs 0..73 (the Darknet-53 base).
 Our flat layout stores kernels OHWI; BN moving stats go to the state vector."""
+import os
 import struct
 
 import numpy as np
+
+NUM_BASE_LAYERS = 52            # the Darknet-53 base: the first layers of every model's table, at the same flat offsets
 
 
 def header_len(buf):
@@ -41,6 +44,29 @@ def read_darknet_base(path_or_bytes, layers, n_params, n_state):
         state[d['mean_off']:d['mean_off'] + cout] = mean
         state[d['var_off']:d['var_off'] + cout] = var
     return params, state
+
+
+def load_base(who, layers, base_path, darknet_path, use_base_file, save_base):
+    """YOLOV3Base (fd.py:384-600, fi.py:398-614): (params, state) of the 52 base layers of `layers` from the base file when
+    use_base_file is set and it exists (`.h5` or `.npz`), else from the Darknet file (then written to base_path as the
+    yolov3_base.h5 layout when save_base is set); None -- announced -- when neither exists."""
+    base = layers[:NUM_BASE_LAYERS]
+    n_p, n_s = base[-1]['beta_off'] + base[-1]['cout'], base[-1]['var_off'] + base[-1]['cout']
+    if use_base_file and os.path.exists(base_path):
+        from .hdf5_lite import is_hdf5, read_hdf5
+        if is_hdf5(base_path):
+            p, s, _found = from_keras_datasets(read_hdf5(base_path)[0], base, n_p, n_s)
+            return p, s
+        with open(base_path, 'rb') as f:
+            d = np.load(f)
+            return d['params'][:n_p], d['state'][:n_s]
+    if os.path.exists(darknet_path):
+        p, s = read_darknet_base(darknet_path, base, n_p, n_s)
+        if save_base:
+            write_keras_h5(base_path, base, p, s, nested=None)
+        return p, s
+    print('%s: neither %s nor %s found; using synthetic base weights' % (who, base_path, darknet_path))
+    return None
 
 
 def write_darknet_base(path, layers, params, state, major=0, minor=2, revision=0, seen=0):

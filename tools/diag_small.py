@@ -24,7 +24,7 @@ def setup(out_ch, B, S, seed):
 
 
 def wtensor(model, B, S, l, code):
-    ws = model._train_ws(B, S)
+    ws = model._workspace(B, S, True)
     off, cnt = ctypes.c_size_t(0), ctypes.c_int64(0)
     assert lib().fv_yolov3_train_workspace_tensor(B, S, model.out_channels, l, code, ctypes.byref(off), ctypes.byref(cnt)) == 0
     return ws[off.value:off.value + 4 * cnt.value].view(torch.float32)

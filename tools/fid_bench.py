@@ -47,7 +47,7 @@ def main():
     ap.add_argument('--iters', type=int, default=5)
     args = ap.parse_args()
     m = FidModel(S, 0)
-    m.init_synthetic_base(seed=7)
+    m.init_synthetic(seed=7)
     m.init_dense()
     g = torch.Generator(device='cuda').manual_seed(0)
     out = dict(image_size=S)

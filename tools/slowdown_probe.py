@@ -166,7 +166,7 @@ def main():
     measure('others deleted (cache kept)')
     torch.cuda.empty_cache()
     measure('torch cache emptied')
-    m._tws = {}; e1._ws = {}
+    m._ws = {}; e1._ws = {}
     torch.cuda.empty_cache()
     measure('own workspaces re-allocated')
     compare('fresh', 'own workspaces re-allocated')
