@@ -55,6 +55,12 @@ class ProfileRec(ctypes.Structure):
                 ('flops_total', ctypes.c_double), ('bytes_total', ctypes.c_double)]
 
 
+class PairBlock(ctypes.Structure):
+    """fv_pair_block of include/fv_hotpath.h."""
+    _fields_ = [('a0', ctypes.c_int64), ('na', ctypes.c_int64), ('b0', ctypes.c_int64), ('nb', ctypes.c_int64),
+                ('out_off', ctypes.c_int64), ('kind', ctypes.c_int32), ('pad', ctypes.c_int32)]
+
+
 BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64)
 
 
@@ -123,6 +129,7 @@ def _declare(L):
         'fv_fid_dense_partial_floats': (i64, [i32, i64]),
         'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
         'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),
+        'fv_fid_pair_dists': (i32, [vp, vp, i64, ctypes.POINTER(PairBlock), i32, ctypes.POINTER(f32), i32, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

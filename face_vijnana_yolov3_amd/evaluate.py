@@ -1,9 +1,11 @@
 """Detection accuracy of FaceDetector.evaluate's output: the reference's `cal_mAP_fd`
 (evaluate.py:27-127) and the IoU-threshold sweep of its `main` (evaluate.py:337-355); identification accuracy of
-FaceIdentifier.test's output: `cal_acc_fi` (evaluate.py:225-329) and its sweep (evaluate.py:362-387).
+FaceIdentifier.test's output: `cal_acc_fi` (evaluate.py:225-329) and its sweep (evaluate.py:362-387); face verification:
+`cal_face_pairs_dists` and `cal_VAL_FAR` (evaluate.py:129-223), whose pair distances run on the device (fv_fid_pair_dists,
+DESIGN.md section 15).
 
-Host code, as in the reference (pandas/NumPy/SciPy on a few thousand boxes); not part of the device
-hot path.  What it restates, line by line:
+The detection / identification metrics are host code, as in the reference (pandas/NumPy/SciPy on a few thousand boxes).
+What they restate, line by line:
 
 * solution csv (no header): FILE, x, y, w, h, confidence  -- what `FaceDetector.evaluate` writes
   (face_detection.py:733-737); ground truth csv (header): FACE_ID, FILE, SUBJECT_ID, FACE_X,
@@ -234,13 +236,164 @@ def cal_acc_fi_sweep(gt_path, sol_path, iou_ths=None):
     return [(float(th),) + tuple(cal_acc_fi(gt_path, sol_path, th)) for th in iou_ths]
 
 
+# ----------------------------------------------------------------------------- face verification (evaluate.py:129-223)
+SIM_TH_RANGE = np.arange(0.1, 1.1, 0.1)      # main's cal_VAL_FAR thresholds (evaluate.py:359)
+
+
+def face_pairs(db_csv=None, resource_type='uccs'):
+    """The pair sets of cal_face_pairs_dists (evaluate.py:129-194) as a block table over one facial-ID matrix.  Reads the subject
+    db (default: db_files(resource_type)'s csv), groups it by subject_id (sorted keys, -1 included in the list the random draw
+    indexes) and draws the different-identity subject pairs with np.random.choice(range(S), size=(S // 2, 2), replace=False) from
+    NumPy's global RandomState, exactly as the reference.  -> dict:
+      names    face files in matrix-row order: every known subject's files (csv order), subjects in key order;
+      blocks   (k, 6) int64 rows (a0, na, b0, nb, out_off, kind) for fv_fid_pair_dists: one i < j triangle per subject with >= 2
+               files (out_off into same_dists), then one rectangle per drawn pair without -1 (out_off into diff_dists, offset by
+               n_same: one buffer holds both);
+      n_same, n_diff, subject_ids, draw (the (S // 2, 2) array np.random.choice returned)."""
+    import pandas as pd
+    from .face_identification import PAIR_RECTANGLE, PAIR_TRIANGLE, db_files
+    db = pd.read_csv(db_files(resource_type)[0] if db_csv is None else db_csv).iloc[:, 1:]
+    groups = {k: list(df.iloc[:, 1]) for k, df in db.groupby('subject_id')}
+    subject_ids = list(groups.keys())
+    names, start = [], {}
+    for sid in subject_ids:
+        if sid == -1:
+            continue
+        start[sid] = len(names)
+        names += groups[sid]
+    blocks, off = [], 0
+    for sid in subject_ids:                           # evaluate.py:143-159
+        n = len(groups[sid])
+        if sid == -1 or n < 2:
+            continue
+        blocks.append((start[sid], n, start[sid], n, off, PAIR_TRIANGLE))
+        off += n * (n - 1) // 2
+    n_same = off
+    draw = np.random.choice(range(len(subject_ids)), size=(len(subject_ids) // 2, 2), replace=False)   # evaluate.py:164-166
+    for k, l in draw:                                 # evaluate.py:170-187
+        sk, sl = subject_ids[k], subject_ids[l]
+        if sk == -1 or sl == -1:
+            continue
+        nk, nl = len(groups[sk]), len(groups[sl])
+        blocks.append((start[sk], nk, start[sl], nl, off, PAIR_RECTANGLE))
+        off += nk * nl
+    return {'names': names, 'blocks': np.asarray(blocks, np.int64).reshape(-1, 6), 'n_same': n_same, 'n_diff': off - n_same,
+            'subject_ids': subject_ids, 'draw': draw}
+
+
+def gather_facial_ids(names, h5_path):
+    """The float32 (len(names), 64) matrix of the facial IDs of subject_facial_ids.h5 (FaceIdentifier.make_facial_ids_db), in
+    `names` order; a file missing from the h5 raises KeyError, as the reference's f[name] does."""
+    from .face_identification import DENSE1_DIM, read_facial_ids_h5
+    fids = read_facial_ids_h5(h5_path)
+    out = np.zeros((len(names), DENSE1_DIM), np.float32)
+    for r, name in enumerate(names):
+        out[r] = fids[name][0]
+    return out
+
+
+def face_pair_dists_device(pairs, ids, thresholds, materialise=True, ctx=None):
+    """One fv_fid_pair_dists launch over face_pairs()'s table: -> (same_dists, diff_dists) float32 arrays (None, None when not
+    materialise: no distance buffer exists on the device or the host) and counts (2, n_th) int64, counts[0][t] / counts[1][t] the
+    same / different pairs with float32 distance <= thresholds[t] (ascending float32)."""
+    import torch
+    from ._lib import Context
+    from .face_identification import fid_pair_dists
+    n_same, n_diff = pairs['n_same'], pairs['n_diff']
+    th = np.asarray(thresholds, np.float32).reshape(-1)
+    if n_same + n_diff == 0:
+        empty = np.zeros(0, np.float32)
+        return (empty, empty) if materialise else (None, None), np.zeros((2, len(th)), np.int64)
+    ctx = ctx if ctx is not None else Context(0)
+    x = torch.from_numpy(np.ascontiguousarray(ids, np.float32)).to(torch.device('cuda', ctx.device))
+    d, c = fid_pair_dists(ctx, x, pairs['blocks'], th, n_dists=(n_same + n_diff) if materialise else None)
+    counts = c.cpu().numpy()
+    if not materialise:
+        return (None, None), counts
+    d = d.cpu().numpy()
+    return (d[:n_same].copy(), d[n_same:].copy()), counts
+
+
+def _run_pairs(resource_type, thresholds, materialise, ctx):
+    from .face_identification import db_files
+    db_csv, _faces, h5, _pickle = db_files(resource_type)
+    pairs = face_pairs(db_csv)
+    ids = gather_facial_ids(pairs['names'], h5)
+    return pairs, face_pair_dists_device(pairs, ids, thresholds, materialise, ctx)
+
+
+def write_face_pairs_dists(path, same_dists, diff_dists):
+    """face_pairs_dists.h5 (evaluate.py:191-193): float32 same_dists and diff_dists."""
+    from .hdf5_lite import write_hdf5
+    write_hdf5(path, {'/same_dists': np.asarray(same_dists, np.float32), '/diff_dists': np.asarray(diff_dists, np.float32)})
+
+
+def cal_face_pairs_dists(resource_type='uccs', ctx=None):
+    """The reference's cal_face_pairs_dists (evaluate.py:129-194) in the current directory: subject_image_db.csv and
+    subject_facial_ids.h5 (vggface2: db_files' names) -> every same-identity pair and the different-identity pairs of the random
+    subject draw, on the device (fv_fid_pair_dists); writes face_pairs_dists.h5 and returns (same_dists, diff_dists), float32 in
+    the reference's order.  Distances are fp64 sums rounded once to float32 (the reference: scipy.linalg.norm of the float32
+    difference, snrm2), within 1 float32 ulp of it."""
+    _pairs, ((same, diff), _counts) = _run_pairs(resource_type, [np.inf], True, ctx)
+    write_face_pairs_dists('face_pairs_dists.h5', same, diff)
+    return same, diff
+
+
+def val_far(counts, n_same, n_diff):
+    """VAL and FAR of evaluate.py:205-214 from pair counts: count / number of pairs, float64 (NaN for an empty pair set)."""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return (np.asarray(counts[0], np.float64) / np.float64(n_same), np.asarray(counts[1], np.float64) / np.float64(n_diff))
+
+
+def cal_VAL_FAR(sim_th_range, counts_only=False, resource_type='uccs', ctx=None):
+    """The reference's cal_VAL_FAR (evaluate.py:196-223) -> (sim_ths, vals, fars) float64: VAL / FAR = share of the same /
+    different pairs with float32(distance) <= float32(threshold) (what `float32 array <= float64 scalar` compares under NumPy < 2),
+    the counts taken from the launch that computes the distances.  Writes face_pairs_dists.h5 (as cal_face_pairs_dists) and
+    val_far.h5 (sim_ths, vals, fars -- the reference writes the builtin `vars` as vals, a bug not reproduced).  counts_only: no
+    distance array anywhere and no face_pairs_dists.h5 (the path for VGGFace2, where the two arrays are several GB)."""
+    from .hdf5_lite import write_hdf5
+    sim_ths = np.asarray(list(sim_th_range), np.float64).reshape(-1)
+    th32 = sim_ths.astype(np.float32)
+    uniq = np.unique(th32[~np.isnan(th32)])                # the kernel takes ascending thresholds; NaN counts nothing
+    if len(uniq) > 4096:
+        raise ValueError('cal_VAL_FAR takes at most 4096 distinct float32 thresholds, got %d' % len(uniq))
+    pairs, ((same, diff), counts) = _run_pairs(resource_type, uniq if len(uniq) else [np.inf], not counts_only, ctx)
+    if not counts_only:
+        write_face_pairs_dists('face_pairs_dists.h5', same, diff)
+    full = np.zeros((2, len(sim_ths)), np.int64)
+    ok = ~np.isnan(th32)
+    full[:, ok] = counts[:, np.searchsorted(uniq, th32[ok])]
+    vals, fars = val_far(full, pairs['n_same'], pairs['n_diff'])
+    write_hdf5('val_far.h5', {'/sim_ths': sim_ths, '/vals': vals, '/fars': fars})
+    return sim_ths, vals, fars
+
+
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(description='mAP of a FaceDetector.evaluate solution file (reference evaluate.py cal_map_fd)')
-    ap.add_argument('--mode', default='cal_map_fd')
-    ap.add_argument('--gt_path', required=True)
-    ap.add_argument('--sol_path', required=True)
+    ap = argparse.ArgumentParser(description='Face detection / identification / verification metrics (reference evaluate.py)')
+    ap.add_argument('--mode', default='cal_map_fd', help='cal_map_fd, cal_acc_fi, cal_face_pairs_dists or cal_VAL_FAR')
+    ap.add_argument('--gt_path', help='ground-truth csv (cal_map_fd, cal_acc_fi)')
+    ap.add_argument('--sol_path', help='solution csv (cal_map_fd, cal_acc_fi)')
+    ap.add_argument('--seed', type=int, default=None, help='np.random.seed before the random subject draw (verification modes)')
+    ap.add_argument('--resource_type', default='uccs', help='uccs or vggface2: which subject db / facial-ID h5 (verification modes)')
+    ap.add_argument('--counts_only', action='store_true', help='cal_VAL_FAR without the distance arrays (no face_pairs_dists.h5)')
     a = ap.parse_args(argv)
+    if a.mode in ('cal_face_pairs_dists', 'cal_VAL_FAR'):
+        if a.seed is not None:
+            np.random.seed(a.seed)
+        if a.mode == 'cal_face_pairs_dists':
+            same, diff = cal_face_pairs_dists(a.resource_type)
+            print('same pairs', len(same), 'different pairs', len(diff))
+            return
+        sim_ths, vals, fars = cal_VAL_FAR(SIM_TH_RANGE, counts_only=a.counts_only, resource_type=a.resource_type)
+        for th, v, f in zip(sim_ths, vals, fars):
+            print('{0:1.2f}'.format(th), v, f)
+        return
+    if a.mode not in ('cal_map_fd', 'cal_acc_fi'):
+        raise SystemExit('unknown mode %r: cal_map_fd, cal_acc_fi, cal_face_pairs_dists and cal_VAL_FAR are implemented here'
+                         % a.mode)
+    if a.gt_path is None or a.sol_path is None:
+        ap.error('--gt_path and --sol_path are required for --mode %s' % a.mode)
     if a.mode == 'cal_acc_fi':
         from .hdf5_lite import write_hdf5
         res = cal_acc_fi_sweep(a.gt_path, a.sol_path)
@@ -251,8 +404,6 @@ def main(argv=None):
                                  '/tn_ls': cols[:, 2].astype(np.int64), '/fn_ls': cols[:, 3].astype(np.int64),
                                  '/acc_ls': cols[:, 4]})          # evaluate.py:382-387
         return
-    if a.mode != 'cal_map_fd':
-        raise SystemExit('only cal_map_fd and cal_acc_fi are implemented here')
     res, mean = cal_mAP_sweep(a.gt_path, a.sol_path)
     for th, m in res:
         print('{0:1.2f}'.format(th), m)

@@ -4,10 +4,12 @@ Port of the reference's `src/space/face_identification.py` (fi.py): the model (f
 (`_make_fid_extractor`, fi.py:378-395), `train` (fi.py:616-643) over its two triplet sequences (fi.py:1490-1601 and the VGGFace2
 variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `test` (fi.py:994-1153) and `main`
 (fi.py:1715-1760) for the modes implemented here.  The hot path is the C ABI (fv_fid_extract, fv_fid_train_step, fv_adam_step,
-fv_letterbox_crops, fv_fid_match); this module holds the weights and drives it.  Not ported: create_db_fi / save_extracted_face
-(the data mode), evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN moving-statistics update
-order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test() batching its frames and crops
-(same rows), fp64 match distances, and crops whose letterboxed side rounds to 0 being skipped (the reference's cv.resize raises)."""
+fv_letterbox_crops, fv_fid_match, fv_fid_pair_dists); this module holds the weights and drives it.  Not ported: create_db_fi /
+save_extracted_face (the data mode), evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
+moving-statistics update order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test()
+batching its frames and crops (same rows), fp64 match distances, and crops whose letterboxed side rounds to 0 being skipped (the
+reference's cv.resize raises)."""
+import ctypes
 import glob
 import json
 import os
@@ -344,6 +346,56 @@ def fid_match(ctx, queries, registry):
         raise ValueError('fid_match expects float32 (n, 64) queries and (m, 64) registry')
     ctx.check(lib().fv_fid_match(ctx.handle, ptr(q), n, ptr(r), m, ptr(idx), ptr(dist)), 'fv_fid_match')
     return idx, dist
+
+
+PAIR_TRIANGLE, PAIR_RECTANGLE = 0, 1     # fv_pair_block.kind
+
+
+def pair_block_pairs(blocks):
+    """Pairs of each row of a block table (k, 6) int64 (a0, na, b0, nb, out_off, kind): na(na-1)/2 or na*nb."""
+    b = np.asarray(blocks, np.int64).reshape(-1, 6)
+    return np.where(b[:, 5] == PAIR_TRIANGLE, b[:, 1] * (b[:, 1] - 1) // 2, b[:, 1] * b[:, 3])
+
+
+def expand_pair_blocks(blocks):
+    """Host expansion of a block table: -> (a rows, b rows) int64, one entry per pair in dists order (a block's pairs at
+    out_off + rank, fv_fid_pair_dists' contract); slots no block writes are -1."""
+    b = np.asarray(blocks, np.int64).reshape(-1, 6)
+    pairs = pair_block_pairs(b)
+    n = int((b[:, 4] + pairs).max()) if len(b) else 0
+    ra, rb = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+    for (a0, na, b0, nb, off, kind), m in zip(b.tolist(), pairs.tolist()):
+        if kind == PAIR_TRIANGLE:
+            i, j = np.triu_indices(na, 1)              # row-major i < j
+        else:
+            i, j = np.divmod(np.arange(m, dtype=np.int64), max(nb, 1))
+        ra[off:off + m] = a0 + i
+        rb[off:off + m] = b0 + j
+    return ra, rb
+
+
+def fid_pair_dists(ctx, ids, blocks, thresholds, n_dists=None, counts=None):
+    """fv_fid_pair_dists: ids (n, 64) float32 CUDA tensor, blocks (k, 6) int64 rows (a0, na, b0, nb, out_off, kind), thresholds
+    ascending float32 (1..4096) -> (dists float32 CUDA tensor of n_dists, or None, counts int64 CUDA tensor (2, n_th)), stream-
+    ordered.  n_dists None: counts only (no distance buffer is allocated); otherwise the length of the distance buffer.  counts: an
+    int64 CUDA tensor (2, n_th) to overwrite instead of a new one."""
+    from ._lib import PairBlock
+    x = ids.contiguous()
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != DENSE1_DIM:
+        raise ValueError('fid_pair_dists expects float32 (n, 64) ids')
+    b = np.ascontiguousarray(np.asarray(blocks, np.int64).reshape(-1, 6))
+    th = np.ascontiguousarray(np.asarray(thresholds, np.float32).reshape(-1))
+    table = (PairBlock * max(1, len(b)))()
+    for k, (a0, na, b0, nb, off, kind) in enumerate(b.tolist()):
+        table[k] = PairBlock(a0, na, b0, nb, off, kind, 0)
+    if counts is None:
+        counts = torch.empty((2, len(th)), dtype=torch.int64, device=x.device)
+    dists = None if n_dists is None else torch.empty(max(1, int(n_dists)), dtype=torch.float32, device=x.device)
+    ctx.check(lib().fv_fid_pair_dists(ctx.handle, ptr(x), int(x.shape[0]), table, len(b),
+                                      th.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(th),
+                                      None if dists is None else ptr(dists), 0 if n_dists is None else int(n_dists), ptr(counts)),
+              'fv_fid_pair_dists')
+    return (None if dists is None else dists[:int(n_dists)]), counts
 
 
 def letterbox_crops(ctx, images, crops, image_size, out=None):

@@ -389,6 +389,23 @@ int fv_fid_dense_l2(fv_ctx* ctx, const float* x, int rows, int64_t F, const floa
  * result does not depend on n, on the rest of the batch or on how the work is split: any split of the queries gives the same
  * bits.  No atomics.  m == 0 is FV_ERR_INVALID.  The similarity threshold (hps.sim_th) is applied by the caller. */
 int fv_fid_match(fv_ctx* ctx, const float* queries, int n, const float* registry, int m, int32_t* best_index, double* best_dist);
+/* Face-verification pair distances (evaluate.py:129-194 cal_face_pairs_dists, 196-223 cal_VAL_FAR): one block per subject or
+ * subject pair over the rows of ids [n_ids][64] float32 (device, 16-byte aligned).  kind 0: the i < j triangle of rows
+ * a0..a0+na-1 (b0 == a0, nb == na; the same-identity pairs of evaluate.py:143-159); kind 1: the na x nb rectangle of rows
+ * a0.. and b0.. (the different-identity pairs of evaluate.py:166-187, k's file outer).  A pair's distance goes to
+ * dists[out_off + rank] -- rank i*na - i*(i+1)/2 + (j-i-1) in a triangle, i*nb + j in a rectangle: the reference's append order --
+ * and is sqrt of the fp64 sum, in dimension order 0..63, of the squared fp64 differences, rounded to float32 (fv_fid_match's
+ * numerics), whatever the block order or launch split.  counts [2][n_th] int64 (device, overwritten): counts[kind][t] = pairs of
+ * that kind with float32 distance <= thresholds[t] (host, ascending, 1 <= n_th <= 4096; NaN counts nowhere); integer sums, so
+ * deterministic.  dists == NULL: counts only (n_dists ignored).  The whole table is checked before anything is enqueued: a row
+ * range outside n_ids, a bad kind or triangle shape, out_off + pairs > n_dists or unsorted thresholds is FV_ERR_INVALID and
+ * leaves dists and counts untouched.  Returns after the table has been uploaded (the call waits for the stream once). */
+typedef struct {
+    int64_t a0, na, b0, nb, out_off;
+    int32_t kind, pad;
+} fv_pair_block;
+int fv_fid_pair_dists(fv_ctx* ctx, const float* ids, int64_t n_ids, const fv_pair_block* blocks, int n_blocks,
+                      const float* thresholds, int n_th, float* dists, int64_t n_dists, int64_t* counts);
 
 /* ------------------------------------------------------------------ secondary: three-scale YOLOv3
  * (SURVEY 8a-17/18).  The reference builds this graph in make_yolov3_model (yd.py:217-311) and
