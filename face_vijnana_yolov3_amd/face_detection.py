@@ -260,7 +260,9 @@ class FaceDetector(object):
         """Image b of a decoded batch -> detect()'s own tail (fd.py:942-947): boxes in network pixels, score > 0, ascending score, at
         most num_cands.  The selection runs on the arrays (BoundBox.get_score: the probability of the arg-max class, capped at 1);
         only the <= num_cands survivors become BoundBox objects -- a frame can hold thousands of candidates."""
+        from .yolov3 import check_candidate_count
         n = int(host['count'][b])
+        check_candidate_count(n, int(host['boxes'].shape[1]), self.image_size // 32)     # never a silently shortened list
         bx = host['boxes'][b, :n].numpy().astype(np.int64); ob = host['objness'][b, :n].numpy(); cl = host['classes'][b, :n].numpy()
         if n == 0:
             return []

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import model
-from ._lib import Context, lib, ptr
+from ._lib import Context, FvError, lib, ptr
 
 COCO_ANCHORS = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]]  # yd.py:560
 
@@ -104,12 +104,30 @@ class Yolov3(model.Model):
             raise ValueError('%s holds a model with %d output channels, this one has %d' % (path, int(fv['out_channels']), self.out_channels))
 
 
+MAX_CANDIDATES = 8192   # fv_yolo_decode_nms: the per-class sort of one image runs in the LDS of one workgroup
+
+
+def candidate_slots(g):
+    """Candidate slots of one image at grid g: kept anchors 1 @g, 2 @2g, 1 @4g (the reference's skip list) = 25 g^2."""
+    return g * g + 2 * (2 * g) * (2 * g) + (4 * g) * (4 * g)
+
+
+def check_candidate_count(count, capacity, g):
+    """The wrappers pass capacity = min(slots, MAX_CANDIDATES).  From grid 19 (608 input, 9025 slots) on an image can hold
+    more candidates than the kernel sorts; it then reports count == capacity < slots and the list is cut short.  That is an
+    error here, never a shortened result (a frame with exactly MAX_CANDIDATES candidates is refused with it)."""
+    if count >= capacity and capacity < candidate_slots(g):
+        raise FvError('three-scale decode: an image holds at least %d candidates above the objectness threshold, the kernel handles '
+                      '%d (grid %d has %d slots): raise the threshold' % (count, MAX_CANDIDATES, g, candidate_slots(g)))
+
+
 def decode_nms(ctx, y13, y26, y52, image_hw, net_hw=(416, 416), anchors=COCO_ANCHORS, obj_thresh=0.5, nms_thresh=0.45):
     """One image: three (g,g,3*(5+nclass)) float32 CUDA tensors -> dict(boxes (n,4) int32 image
-    pixels, objness (n,), classes (n,nclass) with suppressed entries zeroed), reference list order."""
+    pixels, objness (n,), classes (n,nclass) with suppressed entries zeroed), reference list order.
+    Any grid: up to MAX_CANDIDATES candidates per image; more raise FvError (check_candidate_count)."""
     g = int(y13.shape[-3])
     nclass = int(y13.shape[-1]) // 3 - 5
-    cap = g * g + 2 * (2 * g) * (2 * g) + (4 * g) * (4 * g)   # kept anchors: 1 @g, 2 @2g, 1 @4g (skip list)
+    cap = min(candidate_slots(g), MAX_CANDIDATES)
     dev = y13.device
     boxes = torch.empty((cap, 4), dtype=torch.int32, device=dev)
     obj = torch.empty((cap,), dtype=torch.float32, device=dev)
@@ -121,16 +139,18 @@ def decode_nms(ctx, y13, y26, y52, image_hw, net_hw=(416, 416), anchors=COCO_ANC
                                   int(image_hw[1]), cap, ptr(boxes), ptr(obj), ptr(cls), ptr(cnt))
     ctx.check(rc, 'fv_yolo_decode_nms')
     n = int(cnt.item())
+    check_candidate_count(n, cap, g)
     return dict(boxes=boxes[:n], objness=obj[:n], classes=cls[:n])
 
 
 def decode_nms_batch(ctx, y13, y26, y52, image_hw, net_hw=(416, 416), anchors=COCO_ANCHORS, obj_thresh=0.5, nms_thresh=0.45):
     """A batch of images of one size: three (B,g,g,3*(5+nclass)) float32 CUDA tensors -> dict of CUDA tensors boxes (B,cap,4)
     int32, objness (B,cap), classes (B,cap,nclass), count (B,) -- ONE launch pair for the batch, no host sync (the caller
-    copies the tensors out and reads count[b] entries of image b)."""
+    copies the tensors out and reads count[b] entries of image b).  cap = min(slots, MAX_CANDIDATES): where the caller reads
+    count on the host it passes each count[b] to check_candidate_count(count[b], cap, g), which refuses a saturated image."""
     B, g = int(y13.shape[0]), int(y13.shape[-3])
     nclass = int(y13.shape[-1]) // 3 - 5
-    cap = g * g + 2 * (2 * g) * (2 * g) + (4 * g) * (4 * g)
+    cap = min(candidate_slots(g), MAX_CANDIDATES)
     dev = y13.device
     boxes = torch.empty((B, cap, 4), dtype=torch.int32, device=dev)
     obj = torch.empty((B, cap), dtype=torch.float32, device=dev)

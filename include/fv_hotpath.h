@@ -447,8 +447,13 @@ int fv_yolov3_train_workspace_tensor(int batch, int image_size, int out_channels
  * (yd.py:389-404) and do_nms (yd.py:426-444) for ONE image: outputs in the reference's list order;
  * boxes [capacity][4] int32 xmin,ymin,xmax,ymax in image pixels, objness [capacity],
  * classes [capacity][nclass] (suppressed entries zeroed), count (device int).  anchors18: host
- * floats, scale 0 first.  capacity <= 8192.  A zero-area pair (ZeroDivisionError in the reference)
- * does not suppress. */
+ * floats, scale 0 first.  A zero-area pair (ZeroDivisionError in the reference) does not suppress.
+ * capacity: 1..8192 rows of the output buffers (the per-class sort of one image runs in the LDS of one
+ * workgroup), for ANY grid0; FV_ERR_INVALID outside that range, outputs untouched.  An image has 25 grid0^2
+ * candidate slots: 4225 at grid 13, 8100 at 18, 9025 at 19 (608 input).  With more candidates than capacity the
+ * first `capacity` of the list are written, count = capacity, and the NMS runs over those rows only; so
+ * count == capacity < 25 grid0^2 tells the caller that the list may have been cut.  The Python wrappers pass
+ * min(25 grid0^2, 8192) and raise on that condition instead of returning a shortened list. */
 int fv_yolo_decode_nms(fv_ctx* ctx, const float* y13, const float* y26, const float* y52, int grid0, int nclass,
                        const float* anchors18, float obj_thresh, double nms_thresh, int net_h, int net_w,
                        int image_h, int image_w, int capacity, int32_t* boxes, float* objness, float* classes,

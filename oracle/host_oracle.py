@@ -187,13 +187,21 @@ def _sig64(x):
     return 1.0 / (1.0 + math.exp(-x))
 
 
-def decode_netout(netout, anchors, anchor_idx, obj_thresh, net_h, net_w):
+def exp_rounded(a):
+    """The correctly rounded float32 exponential, (float)exp((double)x): what the device kernels compute.  NumPy's own
+    float32 exp is a SIMD routine that differs from it by 1 ulp on a large share of inputs."""
+    with np.errstate(over='ignore', under='ignore'):
+        return np.exp(np.asarray(a).astype(np.float64)).astype(np.float32)
+
+
+def decode_netout(netout, anchors, anchor_idx, obj_thresh, net_h, net_w, exp=np.exp):
     """yolov3_detect.py:335-387 (anchor skip list yd.py:354-362).  float32 sigmoid on the
     array as the reference does (np.exp on float32); returns rows
-    [xmin,ymin,xmax,ymax,objness,classes...] (relative units)."""
+    [xmin,ymin,xmax,ymax,objness,classes...] (relative units).
+    exp: the float32 exponential; the default is the reference's (pinned by the goldens), exp_rounded is the device's."""
     gh, gw = netout.shape[:2]
     no = netout.reshape(gh, gw, 3, -1).astype(np.float32).copy()
-    sig = lambda a: (np.float32(1.) / (np.float32(1.) + np.exp(-a))).astype(np.float32)
+    sig = lambda a: (np.float32(1.) / (np.float32(1.) + exp(-a))).astype(np.float32)
     no[..., :2] = sig(no[..., :2]); no[..., 4:] = sig(no[..., 4:])
     keep = {0: (1,), 1: (0, 2), 2: (1,)}[anchor_idx]
     rows = []
@@ -205,7 +213,7 @@ def decode_netout(netout, anchors, anchor_idx, obj_thresh, net_h, net_w):
                 continue
             x, y, w, h = no[r, c, b, :4]
             x = (c + x) / gw; y = (r + y) / gh
-            w = anchors[2 * b] * np.exp(w) / net_w; h = anchors[2 * b + 1] * np.exp(h) / net_h
+            w = anchors[2 * b] * exp(w) / net_w; h = anchors[2 * b + 1] * exp(h) / net_h
             rows.append([x - w / 2, y - h / 2, x + w / 2, y + h / 2, conf] + list(no[r, c, b, 5:]))
     return rows
 
@@ -247,3 +255,113 @@ def do_nms(rows, nms_thresh):
                 uni = (A[2] - A[0]) * (A[3] - A[1]) + (B[2] - B[0]) * (B[3] - B[1]) - inter
                 if float(inter) / uni >= nms_thresh:
                     B[5 + c] = 0
+
+
+# ----------------------------------------------------------------------------- the same chain on arrays
+_KEPT_ANCHORS = ((1,), (0, 2), (1,))     # yd.py:354-362, by scale
+
+
+def _overlap_v(x1, x2, x3, x4):
+    lo = np.minimum(x2, x4)
+    return np.where(x3 < x1, np.where(x4 < x1, 0, lo - x1), np.where(x2 < x3, 0, lo - x3))
+
+
+def box_iou_int(a, b):
+    """(inter, union) of integer boxes a (4,) or (n,4) against b (n,4), with the reference's overlap rules (yd.py:165-194)."""
+    a = np.asarray(a, np.int64); b = np.asarray(b, np.int64)
+    inter = _overlap_v(a[..., 0], a[..., 2], b[..., 0], b[..., 2]) * _overlap_v(a[..., 1], a[..., 3], b[..., 1], b[..., 3])
+    uni = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1]) + (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1]) - inter
+    return inter, uni
+
+
+def suppresses(inter, uni, nms_thresh):
+    """float(inter) / union >= nms_thresh in float64; a pair whose union is 0 does not suppress (the reference raises
+    ZeroDivisionError there: the documented deviation of fv_yolo_decode_nms)."""
+    ok = uni != 0
+    q = np.divide(inter.astype(np.float64), uni.astype(np.float64), out=np.zeros(np.shape(inter), np.float64), where=ok)
+    return ok & (q >= nms_thresh)
+
+
+def do_nms_arrays(boxes, classes, nms_thresh):
+    """do_nms on arrays: boxes (n,4) integers, classes (n,ncls) float32, modified in place (suppression = class prob := 0).
+    Per class one greedy pass in stable order of descending probability (ties: lower index first); the current survivor is
+    tested against all candidates still alive behind it at once.  Same semantics as do_nms (the Python triple loop) except
+    the zero-union pair, which does not suppress here and raises there."""
+    boxes = np.asarray(boxes, np.int64)
+    for c in range(classes.shape[1]):
+        p = classes[:, c]
+        rem = np.argsort(-p, kind='stable')
+        rem = rem[p[rem] > 0]                       # zero entries neither suppress nor can be suppressed any further
+        while len(rem) > 1:
+            a, rest = rem[0], rem[1:]
+            inter, uni = box_iou_int(boxes[a], boxes[rest])
+            dead = suppresses(inter, uni, nms_thresh)
+            p[rest[dead]] = 0
+            rem = rest[~dead]
+
+
+def decode_frame(netouts, anchors, obj_thresh, nms_thresh, net_hw, image_hw, exp=exp_rounded, capacity=None, nms=True):
+    """decode_netout x3 -> correct_yolo_boxes -> do_nms for one image, on arrays, in float32 with the reference's operation
+    order (NumPy 2 scalar rules: a Python number next to a float32 stays float32).  netouts: three (g,g,3*(5+ncls)) float32
+    arrays, scale 0 first.  Returns dict(boxes (n,4) int64, objness (n,) float32, classes (n,ncls) float32) in the
+    reference's list order.  capacity: keep the first `capacity` candidates only (fv_yolo_decode_nms's truncation)."""
+    net_h, net_w = net_hw; image_h, image_w = image_hw
+    f32 = np.float32
+    parts = []
+    for s, netout in enumerate(netouts):
+        gh, gw = netout.shape[:2]
+        no = np.asarray(netout, f32).reshape(gh * gw, 3, -1)[:, _KEPT_ANCHORS[s], :]      # (cells, kept, 5+ncls): list order
+        nk = no.shape[1]
+        sig = lambda a: (f32(1.) / (f32(1.) + exp(-a))).astype(f32)
+        conf = sig(no[..., 4])
+        keep = ~(conf < f32(obj_thresh))
+        cell = np.repeat(np.arange(gh * gw), nk).reshape(gh * gw, nk)
+        anc = np.asarray(anchors[s], f32).reshape(3, 2)[list(_KEPT_ANCHORS[s])]
+        aw = np.broadcast_to(anc[:, 0], keep.shape)[keep]; ah = np.broadcast_to(anc[:, 1], keep.shape)[keep]
+        t = no[keep]
+        col = (cell[keep] % gw).astype(f32); row = (cell[keep] // gw).astype(f32)
+        with np.errstate(over='ignore'):
+            x = (col + sig(t[:, 0])) / f32(gw); y = (row + sig(t[:, 1])) / f32(gh)
+            w = aw * exp(t[:, 2]) / f32(net_w); h = ah * exp(t[:, 3]) / f32(net_h)
+            cls = sig(t[:, 5:])
+        parts.append((x - w / f32(2), y - h / f32(2), x + w / f32(2), y + h / f32(2), conf[keep], cls))
+    xmin, ymin, xmax, ymax, obj = [np.concatenate([p[k] for p in parts]) for k in range(5)]
+    cls = np.concatenate([p[5] for p in parts], 0)
+    if (float(net_w) / image_w) < (float(net_h) / image_h):
+        new_w = net_w; new_h = (image_h * net_w) / image_w
+    else:
+        new_h = net_w; new_w = (image_w * net_h) / image_h
+    x_off, x_sc = f32((net_w - new_w) / 2. / net_w), f32(float(new_w) / net_w)
+    y_off, y_sc = f32((net_h - new_h) / 2. / net_h), f32(float(new_h) / net_h)
+    tr = lambda v, off, sc, n: ((v - off) / sc * f32(n)).astype(np.float64).astype(np.int64)     # int(): towards zero
+    boxes = np.stack([tr(xmin, x_off, x_sc, image_w), tr(ymin, y_off, y_sc, image_h),
+                      tr(xmax, x_off, x_sc, image_w), tr(ymax, y_off, y_sc, image_h)], 1)
+    if capacity is not None:
+        boxes, obj, cls = boxes[:capacity], obj[:capacity], cls[:capacity]
+    cls = np.ascontiguousarray(cls)
+    if nms:
+        do_nms_arrays(boxes, cls, nms_thresh)
+    return dict(boxes=boxes, objness=obj, classes=cls)
+
+
+def fragile(netouts, obj_thresh, ulps=4):
+    """Whether a 1-ulp difference between two float64 exp routines (the device's and the host's) could reach a float32 result
+    of this frame: True iff some value that feeds the candidate list -- the objectness logit of every kept-anchor slot (it
+    decides membership), every other logit of the slots that pass obj_thresh -- has a float64 exponential within `ulps`
+    float64 ulps of the midpoint of two neighbouring float32 numbers, where (float)exp((double)x) rounds.  Exponentials
+    beyond float32's range round to inf either way; results below its normal range count as fragile."""
+    args = []
+    for s, netout in enumerate(netouts):
+        gh, gw = netout.shape[:2]
+        no = np.asarray(netout, np.float32).reshape(gh * gw, 3, -1)[:, _KEPT_ANCHORS[s], :].astype(np.float64)
+        conf = exp_rounded(-no[..., 4].astype(np.float32))
+        keep = ~((np.float32(1.) / (np.float32(1.) + conf)) < np.float32(obj_thresh))
+        t = no[keep]
+        args += [-no[..., 4].ravel(), -t[:, :2].ravel(), t[:, 2:4].ravel(), -t[:, 5:].ravel()]
+    with np.errstate(over='ignore', under='ignore'):
+        e = np.exp(np.concatenate(args))
+    e = e[e <= float(np.finfo(np.float32).max) * 2]            # rounds to inf (or is inf) in both routines
+    if np.any(e < float(np.finfo(np.float32).tiny)):
+        return True
+    low = e.view(np.uint64) & np.uint64((1 << 29) - 1)            # float64 bits below float32's last place
+    return bool(np.any(np.abs(low.astype(np.int64) - (1 << 28)) <= ulps))

@@ -14,6 +14,7 @@ Outputs (data only -- inputs and expected outputs; no reference source text):
   tests/golden/weight_reader.npz   WeightReader         (yd.py:67-124)
   tests/golden/decode_netout.npz   decode_netout/do_nms/correct_yolo_boxes (yd.py:335-444)
   tests/golden/decode_netout_coco80.npz  the same on 80 classes and a small image (more int() boundary cases)
+  tests/golden/decode_netout_else.npz  the same for a portrait and a square image (the `else` branch of correct_yolo_boxes)
   tests/golden/test_csv.npz        FaceDetector.test() csv rows: letterbox geometry, detect,
                                    back-projection and str() formatting (fd.py:783-883)
 
@@ -494,8 +495,55 @@ def mint_decode_netout_coco80():
     print('decode_netout_coco80:', pre.shape, 'suppressed entries', int(((pre[:, 5:] != 0) & (post[:, 5:] == 0)).sum()))
 
 
+def mint_decode_netout_else():
+    """Third decode_netout fixture: the `else` branch of correct_yolo_boxes (yd.py:396-398, with its `new_h = net_w`), which
+    neither landscape fixture reaches: one set of head outputs on a 416 net, corrected for a PORTRAIT image (1920 high x 1440
+    wide) and for a SQUARE one (416 x 416: the call FaceDetector's three-scale head makes), NMS at 0.45.  20 classes, sparse
+    storage as in decode_netout_coco80; `pre` (before the correction) is shared by the two images."""
+    rng = np.random.default_rng(91)
+    anchors = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]]
+    ncls = 20
+    net_h = net_w = 416
+    nms_thresh = 0.45
+    sparse = {}
+    netouts = []
+    for s, (g, nhot) in enumerate(((13, 70), (26, 130), (52, 200))):
+        no = np.zeros((g, g, 3 * (5 + ncls)), np.float32)
+        no.reshape(g, g, 3, -1)[..., 4] = -12.0
+        centres = rng.integers(1, g - 1, (nhot // 5, 2))
+        cells = np.unique(np.clip(np.repeat(centres, 5, 0) + rng.integers(-1, 2, (nhot // 5 * 5, 2)), 0, g - 1), axis=0)
+        vals = rng.normal(0, 1.0, (len(cells), 3, 5 + ncls)).astype(np.float32)
+        vals[..., 4] += 1.0; vals[..., 2:4] = vals[..., 2:4] * 0.25 + 0.5
+        vals[..., 5:] -= 2.0
+        fav = rng.integers(0, ncls, len(cells))
+        for k in range(len(cells)):
+            vals[k, :, 5 + fav[k] % 5] += 4.0
+        vals = vals.reshape(len(cells), -1)
+        no[cells[:, 0], cells[:, 1]] = vals
+        sparse['cells_%d' % s] = cells.astype(np.int32); sparse['vals_%d' % s] = vals
+        netouts.append(no)
+    out = {}
+    for tag, (image_h, image_w) in (('portrait', (1920, 1440)), ('square', (416, 416))):
+        boxes = []
+        for s in range(3):
+            boxes += yd.decode_netout(netouts[s].copy(), anchors[s], s, 0.5, net_h, net_w)
+        pre = np.array([[b.xmin, b.ymin, b.xmax, b.ymax, b.objness] + list(b.classes) for b in boxes], np.float64)
+        yd.correct_yolo_boxes(boxes, image_h, image_w, net_h, net_w)
+        assert all(b.xmax > b.xmin and b.ymax > b.ymin for b in boxes), 'zero-area box: redraw'
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            yd.do_nms(boxes, nms_thresh)
+        post = np.array([[b.xmin, b.ymin, b.xmax, b.ymax, b.objness] + list(b.classes) for b in boxes], np.float64)
+        assert 'pre' not in out or np.array_equal(out['pre'], pre)
+        out['pre'] = pre; out['post_' + tag] = post; out['image_hw_' + tag] = np.array([image_h, image_w], np.int32)
+        print('decode_netout_else', tag, pre.shape, 'suppressed entries', int(((pre[:, 5:] != 0) & (post[:, 5:] == 0)).sum()))
+    np.savez_compressed(os.path.join(HERE, 'decode_netout_else.npz'), anchors=np.array(anchors, np.int32),
+                        nms_thresh=np.float64(nms_thresh), background_obj=np.float32(-12.0), **sparse, **out)
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['detect', 'iou', 'gt', 'weight_reader', 'decode_netout', 'test_csv', 'decode_netout_coco80']
+    which = sys.argv[1:] or ['detect', 'iou', 'gt', 'weight_reader', 'decode_netout', 'test_csv', 'decode_netout_coco80', 'decode_netout_else']
     for name in which:
         {'detect': mint_detect, 'iou': mint_iou, 'gt': mint_gt, 'weight_reader': mint_weight_reader,
-         'decode_netout': mint_decode_netout, 'test_csv': mint_test_csv, 'decode_netout_coco80': mint_decode_netout_coco80}[name]()
+         'decode_netout': mint_decode_netout, 'test_csv': mint_test_csv, 'decode_netout_coco80': mint_decode_netout_coco80,
+         'decode_netout_else': mint_decode_netout_else}[name]()

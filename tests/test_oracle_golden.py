@@ -97,21 +97,34 @@ def coco80_netouts(g):
     return outs
 
 
-@pytest.mark.parametrize('fixture', ['decode_netout.npz', 'decode_netout_coco80.npz'])
+# the portrait and the square image of decode_netout_else.npz take the `else` branch of correct_yolo_boxes
+GOLDEN_CASES = ['decode_netout.npz', 'decode_netout_coco80.npz', 'decode_netout_else.npz:portrait', 'decode_netout_else.npz:square']
+
+
+def load_decode_case(golden_dir, fixture):
+    """-> (netouts, golden, image_h, image_w, post, nms_thresh) of one decode_netout golden case."""
+    name, _, tag = fixture.partition(':')
+    g = _load(golden_dir, name)
+    netouts = coco80_netouts(g) if 'vals_0' in g else [g['netout_%d' % s] for s in range(3)]
+    ih, iw = [int(v) for v in g['image_hw_' + tag if tag else 'image_hw']]
+    return netouts, g, ih, iw, g['post_' + tag if tag else 'post'], float(g['nms_thresh']) if 'nms_thresh' in g else 0.5
+
+
+@pytest.mark.parametrize('fixture', GOLDEN_CASES)
 def test_decode_netout_and_nms_secondary(golden_dir, fixture):
-    g = _load(golden_dir, fixture)
-    netouts = coco80_netouts(g) if 'coco80' in fixture else [g['netout_%d' % s] for s in range(3)]
+    netouts, g, ih, iw, gpost, nms_thresh = load_decode_case(golden_dir, fixture)
     rows = []
     for s in range(3):
         rows += host_oracle.decode_netout(netouts[s], list(g['anchors'][s]), s, 0.5, 416, 416)
     pre = np.array(rows, np.float64)
     assert pre.shape == g['pre'].shape
     np.testing.assert_allclose(pre, g['pre'], rtol=1e-6, atol=1e-7)
-    ih, iw = [int(v) for v in g['image_hw']]
     host_oracle.correct_yolo_boxes(rows, ih, iw, 416, 416)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        host_oracle.do_nms(rows, 0.5)
+        host_oracle.do_nms(rows, nms_thresh)
     post = np.array(rows, np.float64)
-    np.testing.assert_array_equal(post[:, :4], g['post'][:, :4])
-    np.testing.assert_array_equal(post[:, 5:] == 0, g['post'][:, 5:] == 0)
+    np.testing.assert_array_equal(post[:, :4], gpost[:, :4])
+    np.testing.assert_array_equal(post[:, 5:] == 0, gpost[:, 5:] == 0)
+    if ':' in fixture:      # the branch this fixture is there for
+        assert not (416.0 / iw) < (416.0 / ih)

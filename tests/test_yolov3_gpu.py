@@ -1,7 +1,6 @@
 """Secondary path on the GPU: the full three-scale YOLOv3 forward against the
 torch-CPU oracle, and decode_netout + correct_yolo_boxes + do_nms against the golden vectors minted
 from the reference's own functions (tests/golden/decode_netout.npz)."""
-import os
 
 import numpy as np
 import pytest
@@ -69,21 +68,12 @@ def test_darknet_full_weights_roundtrip(model, tmp_path):
     assert np.array_equal(model.params.cpu().numpy(), p) and np.array_equal(model.state.cpu().numpy(), s)
 
 
-def _coco80_netouts(g):
-    outs = []
-    for s, gsz in enumerate((13, 26, 52)):
-        no = np.zeros((gsz, gsz, g['vals_%d' % s].shape[1]), np.float32)
-        no.reshape(gsz, gsz, 3, -1)[..., 4] = g['background_obj']
-        c = g['cells_%d' % s]
-        no[c[:, 0], c[:, 1]] = g['vals_%d' % s]
-        outs.append(no)
-    return outs
-
-
-@pytest.mark.parametrize('fixture', ['decode_netout.npz', 'decode_netout_coco80.npz'])
+@pytest.mark.parametrize('fixture', ['decode_netout.npz', 'decode_netout_coco80.npz', 'decode_netout_else.npz:portrait',
+                                     'decode_netout_else.npz:square'])
 def test_decode_nms_matches_reference_golden(model, golden_dir, fixture):
     """fv_yolo_decode_nms against vectors minted by the reference's decode_netout / correct_yolo_boxes /
-    do_nms (4 classes on a 1440x1920 image; 80 classes on a 375x500 image).  Candidate set, order and
+    do_nms (4 classes on a 1440x1920 image; 80 classes on a 375x500 image; 20 classes on a 1920x1440 and a
+    416x416 image with NMS at 0.45: the `else` branch of correct_yolo_boxes).  Candidate set, order and
     objectness: exact.  Integer corners: exact, except where the reference's own pre-truncation value --
     recomputed here from the golden's float corners -- sits within a few float32 ulps of an integer: the
     kernel's exp is the correctly rounded one, NumPy's SIMD float32 exp may differ by 1 ulp, and int()
@@ -92,12 +82,11 @@ def test_decode_nms_matches_reference_golden(model, golden_dir, fixture):
     gives on the DEVICE's integer boxes -- so a corner that moved is the only way it can differ."""
     from face_vijnana_yolov3_amd.yolov3 import decode_nms
     from oracle import host_oracle
-    g = np.load(os.path.join(golden_dir, fixture))
-    netouts = _coco80_netouts(g) if 'coco80' in fixture else [g['netout_%d' % s] for s in range(3)]
+    from test_oracle_golden import load_decode_case
+    netouts, g, ih, iw, post, nms_thresh = load_decode_case(golden_dir, fixture)
     ys = [torch.from_numpy(a).cuda() for a in netouts]
-    ih, iw = [int(v) for v in g['image_hw']]
-    res = decode_nms(model.ctx, ys[0], ys[1], ys[2], (ih, iw), (416, 416), g['anchors'].tolist(), 0.5, 0.5)
-    pre, post = g['pre'], g['post']
+    res = decode_nms(model.ctx, ys[0], ys[1], ys[2], (ih, iw), (416, 416), g['anchors'].tolist(), 0.5, nms_thresh)
+    pre = g['pre']
     n = post.shape[0]
     assert res['boxes'].shape[0] == n                                   # same candidates, same order
     np.testing.assert_allclose(res['objness'].cpu().numpy(), post[:, 4], rtol=3e-7, atol=0)
@@ -124,7 +113,7 @@ def test_decode_nms_matches_reference_golden(model, golden_dir, fixture):
     assert len(bad) <= max(2, 0.005 * 4 * n)
     # suppression pattern == the reference's NMS run on the device's integer boxes and the reference's probabilities
     rows = [list(got[i]) + [float(pre[i, 4])] + [float(c) for c in pre[i, 5:]] for i in range(n)]
-    host_oracle.do_nms(rows, 0.5)
+    host_oracle.do_nms(rows, nms_thresh)
     exp_zero = np.array([r[5:] for r in rows]) == 0
     cls = res['classes'].cpu().numpy()
     assert np.array_equal(cls == 0, exp_zero)
