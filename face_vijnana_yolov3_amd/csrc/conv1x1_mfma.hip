@@ -12,8 +12,8 @@
 //  * the two workgroups of a CU fall out of phase after their first tile (one wins the matrix pipe) and stay so:
 //    one multiplies while the other stores;
 //  * addressing is linear (row m of the lattice = row m of x and of out): no divisions, no row-offset table.
-// Same tile shape, same K order, same MFMA sequence per output element as conv_kernel<BN, ...>: bit-identical results
-// (tests/test_ops_gpu.py).  Tiles are dealt round-robin (workgroup b takes b, b + G, ...; the XCD remap keeps the N tiles of one
+// The K step, the accumulator helpers and the store epilogue are the ones conv_kernel<BN, ...> uses (conv_tile.h), so the results
+// are bit-identical (tests/test_ops_gpu.py).  Tiles are dealt round-robin (workgroup b takes b, b + G, ...; the XCD remap keeps the N tiles of one
 // A panel on one L2 at the same time).
 #include <string>
 #include <type_traits>
@@ -48,110 +48,46 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 4) void conv1x1_persist_ker
     const int NT = (a.Nout + BN - 1) / BN;
     const int nk = a.Cin / BK;
 
-    constexpr unsigned OOB = 0x80000000u;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)((unsigned)a.M * a.Cin * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (int)((unsigned)a.Nout * a.Cin * 4u), 0x00020000);
-    const int col4 = (tid & 7) * 4;
+    const int col4 = (tid & 7) * 4, r0 = tid >> 3;
     unsigned a_off[APT], b_row[BL];
-    u32x4 ra[APT], rb[BL], ra2[APT], rb2[BL];
+    OperandRegs<APT, BL> regs0, regs1;         // even / odd K steps
 
     auto set_tile = [&](int w, int& mt, int& nt) {
         const int tile = xcd_remap(w, ntiles);
         mt = tile / NT; nt = tile - mt * NT;
 #pragma unroll
         for (int p = 0; p < APT; ++p) {
-            const int m = mt * BM + (tid >> 3) + RSTEP * p;
+            const int m = mt * BM + r0 + RSTEP * p;
             a_off[p] = m < a.M ? (unsigned)(m * a.Cin + col4) * 4u : OOB;
         }
 #pragma unroll
         for (int p = 0; p < BL; ++p) {
-            const int n = nt * BN + (tid >> 3) + RSTEP * p;
+            const int n = nt * BN + r0 + RSTEP * p;
             b_row[p] = n < a.Nout ? (unsigned)(n * a.Cin + col4) * 4u : OOB;
         }
     };
-    auto load = [&](int step) {
-        const int c0b = step * BK * 4;
-#pragma unroll
-        for (int p = 0; p < APT; ++p) ra[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, a_off[p], c0b, 0);
-#pragma unroll
-        for (int p = 0; p < BL; ++p) rb[p] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_row[p], c0b, 0);
-    };
-    auto load2 = [&](int step) {
-        const int c0b = step * BK * 4;
-#pragma unroll
-        for (int p = 0; p < APT; ++p) ra2[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, a_off[p], c0b, 0);
-#pragma unroll
-        for (int p = 0; p < BL; ++p) rb2[p] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_row[p], c0b, 0);
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < APT; ++p) *reinterpret_cast<u32x4*>(&As[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = ra[p];
-#pragma unroll
-        for (int p = 0; p < BL; ++p) *reinterpret_cast<u32x4*>(&Bs[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = rb[p];
-    };
-    auto stage2 = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < APT; ++p) *reinterpret_cast<u32x4*>(&As[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = ra2[p];
-#pragma unroll
-        for (int p = 0; p < BL; ++p) *reinterpret_cast<u32x4*>(&Bs[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = rb2[p];
-    };
+    auto load = [&](OperandRegs<APT, BL>& regs, int step) { regs.load(xr, wr, a_off, b_row, step * BK * 4, step * BK * 4); };
     const int arow = (wm * WTM + (lane & 31)) * LDT + (lane >> 5) * 4;
     const int brow = (wn * WTN + (lane & 31)) * LDT + (lane >> 5) * 4;
-    auto readfrag = [&](const float* __restrict__ Asm, const float* __restrict__ Bsm, int kc, float4 (&af)[MB], float4 (&bf)[NB]) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i) af[i] = *reinterpret_cast<const float4*>(&Asm[arow + i * 32 * LDT + kc * 8]);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) bf[j] = *reinterpret_cast<const float4*>(&Bsm[brow + j * 32 * LDT + kc * 8]);
-    };
 
     int w = blockIdx.x, mt, nt;
     set_tile(w, mt, nt);
-    load(0);
-    if (nk > 1) load2(1);
+    load(regs0, 0);
+    if (nk > 1) load(regs1, 1);
 
     for (;;) {
         f32x16 acc[MB][NB];
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-        auto mfma_chunk = [&](const float4 (&af)[MB], const float4 (&bf)[NB]) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < MB; ++i)
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) {
-                        const float av = e == 0 ? af[i].x : e == 1 ? af[i].y : e == 2 ? af[i].z : af[i].w;
-                        const float bv = e == 0 ? bf[j].x : e == 1 ? bf[j].y : e == 2 ? bf[j].z : bf[j].w;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-        };
-        stage(0);                 // K step 0 of this tile: loaded before the previous tile's epilogue (or above)
+        acc_zero(acc);
+        regs0.template stage<RSTEP>(As[0], Bs[0], r0, col4);      // K step 0 of this tile: loaded before the previous tile's epilogue (or above)
         __syncthreads();
-        auto body = [&](int s, auto odd) {     // the K step of conv_kernel: same chunk order, same MFMA sequence
-            constexpr bool ODD = decltype(odd)::value;
-            const float* Ac = As[ODD ? 1 : 0]; const float* Bc = Bs[ODD ? 1 : 0];
-            if (s + 2 < nk) { if constexpr (ODD) load2(s + 2); else load(s + 2); }
-            float4 af0[MB], bf0[NB], af1[MB], bf1[NB];
-            readfrag(Ac, Bc, 0, af0, bf0);
-            readfrag(Ac, Bc, 1, af1, bf1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(af0, bf0);
-            __builtin_amdgcn_sched_barrier(0);
-            readfrag(Ac, Bc, 2, af0, bf0);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(af1, bf1);
-            __builtin_amdgcn_sched_barrier(0);
-            readfrag(Ac, Bc, 3, af1, bf1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(af0, bf0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 1 < nk) { if constexpr (ODD) stage(0); else stage2(1); }
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(af1, bf1);
+        auto body = [&](int s, auto odd) {
+            constexpr int ODD = decltype(odd)::value;
+            if (s + 2 < nk) load(ODD ? regs1 : regs0, s + 2);
+            k_step(acc, As[ODD], Bs[ODD], arow, brow, [&] {
+                if (s + 1 < nk) (ODD ? regs0 : regs1).template stage<RSTEP>(As[1 - ODD], Bs[1 - ODD], r0, col4);
+            });
             __syncthreads();
         };
         for (int s = 0; s < nk; s += 2) {
@@ -165,8 +101,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 4) void conv1x1_persist_ker
         const bool more = wnext < ntiles;
         if (more) {
             set_tile(wnext, mt, nt);
-            if constexpr (PF >= 1) load(0);
-            if constexpr (PF >= 2) { if (nk > 1) load2(1); }
+            if constexpr (PF >= 1) load(regs0, 0);
+            if constexpr (PF >= 2) { if (nk > 1) load(regs1, 1); }
         }
 
         // ------------------------------------------------------------------ epilogue of tile (mt_c, nt_c)
@@ -178,87 +114,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 4) void conv1x1_persist_ker
         asm volatile("" : "+v"(te));
         const int lane_e = te & 63, half_e = lane_e >> 5, lc_e = lane_e & 31, wave_e = te >> 6;
         const int wm_e = wave_e / WAVES_N, wn_e = wave_e % WAVES_N;
-        if (a.epi & FV_EPI_STATS) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                float s = 0.f, q = 0.f;
-#pragma unroll
-                for (int i = 0; i < MB; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { float v = acc[i][j][r]; s += v; q += v * v; }
-                s += __shfl_xor(s, 32);
-                q += __shfl_xor(q, 32);
-                if (half_e == 0) { red[0][wm_e][wn_e * WTN + j * 32 + lc_e] = s; red[1][wm_e][wn_e * WTN + j * 32 + lc_e] = q; }
-            }
-            __syncthreads();
-            if (te < BN && n0 + te < a.Nout) {
-                float s = 0.f, q = 0.f;
-#pragma unroll
-                for (int ww = 0; ww < WAVES_M; ++ww) { s += red[0][ww][te]; q += red[1][ww][te]; }
-                stat_store(a, mt_c, n0 + te, s, q);
-            }
-        }
+        if (a.epi & FV_EPI_STATS) tile_stats(a, acc, red, wm_e, wn_e * WTN, half_e, lc_e, te, n0, mt_c);
         float* Cs = smem;
-        constexpr int C4 = BN / 4;
-        constexpr int NP = BM * C4 / NTH, GP = NP < 4 ? NP : 4;
-        static_assert(NP % GP == 0, "epilogue grouping");
-        constexpr bool bnred = BNRED;
-        const bool addon = (a.epi & FV_EPI_ADD) != 0;
         __syncthreads();         // (the K loop's last barrier already separates the operand reads from these writes; kept for the `red` reads above)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Cs[(wm_e * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half_e) * BN + wn_e * WTN + j * 32 + lc_e] = acc[i][j][r];
+        acc_to_lds<BN>(Cs, acc, wm_e * WTM, wn_e * WTN, half_e, lc_e);
         __syncthreads();
-        BnRedAcc br;
-        br.init(a, n0 + (te % C4) * 4, bnred && n0 + (te % C4) * 4 < a.Nout);
-#pragma unroll
-        for (int p0 = 0; p0 < NP; p0 += GP) {
-            int offn[GP]; bool okp[GP];
-            float4 zq[GP], aq[GP];
-#pragma unroll
-            for (int q = 0; q < GP; ++q) {
-                const int f = te + NTH * (p0 + q), row = f / C4, c4 = (f % C4) * 4;
-                const int m = m0 + row, n = n0 + c4;
-                okp[q] = m < a.M && n < a.Nout;
-                offn[q] = okp[q] ? m * a.Nout + n : 0;
-            }
-            if (bnred) {
-#pragma unroll
-                for (int q = 0; q < GP; ++q) zq[q] = *reinterpret_cast<const float4*>(a.bn_z + offn[q]);
-            }
-            if (addon) {
-#pragma unroll
-                for (int q = 0; q < GP; ++q) aq[q] = *reinterpret_cast<const float4*>(a.addend + offn[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < GP; ++q) {
-                const int f = te + NTH * (p0 + q), row = f / C4, c4 = (f % C4) * 4;
-                const int n = n0 + c4;
-                if (okp[q]) {
-                    float4 v = *reinterpret_cast<const float4*>(&Cs[row * BN + c4]);
-                    if (a.epi & FV_EPI_AFFINE) {
-                        if (a.scale) { const float4 s = *reinterpret_cast<const float4*>(a.scale + n); v.x *= s.x; v.y *= s.y; v.z *= s.z; v.w *= s.w; }
-                        if (a.shift) { const float4 s = *reinterpret_cast<const float4*>(a.shift + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-                    }
-                    if (a.epi & FV_EPI_LEAKY) {
-                        v.x = v.x > 0.f ? v.x : v.x * a.leaky; v.y = v.y > 0.f ? v.y : v.y * a.leaky;
-                        v.z = v.z > 0.f ? v.z : v.z * a.leaky; v.w = v.w > 0.f ? v.w : v.w * a.leaky;
-                    }
-                    if (addon) { v.x += aq[q].x; v.y += aq[q].y; v.z += aq[q].z; v.w += aq[q].w; }
-                    *reinterpret_cast<float4*>(a.out + offn[q]) = v;
-                    if (bnred) br.add(v, zq[q], a.bn_leaky);
-                }
-            }
-        }
-        if (bnred) bnred_flush<BN, NTH>(a, br, smem + BM * BN, n0, mt_c, te);
+        wide_store<BM, BN, NTH>(a, Cs, a.out, RowLinear{m0, a.M, a.Nout}, n0, mt_c, te, BNRED);
         if (!more) break;
         w = wnext;
-        if constexpr (PF < 1) load(0);
-        if constexpr (PF < 2) { if (nk > 1) load2(1); }
+        if constexpr (PF < 1) load(regs0, 0);
+        if constexpr (PF < 2) { if (nk > 1) load(regs1, 1); }
         __syncthreads();         // the output tile (and the reduction scratch behind it) has been read: the operand buffers are free again
     }
 }

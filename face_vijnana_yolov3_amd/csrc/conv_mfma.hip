@@ -6,7 +6,9 @@
 // k-ordered fmaf chain, so the numerics equal a scalar fp32 convolution.
 //
 // GEMM view: M = output pixels of the lattice, N = output channels, K = taps x Cin.
-//  * block = 256 threads (4 waves), tile 128 x BN (BN = 128/64/32), K step 32
+//  * block = 512 threads (8 waves: 2 x 4 for the 128-wide tile, 4 x 2 for the 64-wide one), tile 128 x BN (BN = 128/64/32; 64 x 128
+//    for some small-M launches), K step 32.  The 4-wave form (256 threads) survives in the 32-wide tile (4 x 1), in the first-layer
+//    gather path (2 x 2, 4 x 1) and as the conv_waves8 = 0 fallback (2 x 2)
 //  * A (pixels x channels) and B (out-channels x channels) tiles are both K-contiguous in HBM
 //    (NHWC activations, OHWI weights): 16-byte loads, register-staged into a double-buffered
 //    LDS image [row][32+4] whose 36-dword row stride makes the ds_read_b128 fragment reads
@@ -16,6 +18,8 @@
 //  * epilogue: optional per-channel affine (+LeakyReLU, +residual add) for inference, or raw
 //    store + deterministic per-tile column sums / sums of squares for training-mode BatchNorm
 //  * XCD-aware bijective remap of blockIdx so tiles that share an A panel land on one L2
+// The K step, the accumulator helpers and the store epilogue are the shared parts of conv_tile.h; this file holds the policy of
+// the one-tile-per-workgroup kernel (tail split, K split, two-register-set prefetch) and the launch code.
 #include <string>
 #include <type_traits>
 #include "conv_tile.h"
@@ -89,22 +93,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_kernel(const F
     const int HWl = a.Hl * a.Wl;
 
     // output row offsets (in elements) for the epilogue, -1 = row outside the problem
-    if (tid < BM) {
-        int m = m0 + tid, off = -1;
-        if (m < a.M) {
-            int b = m / HWl, rem = m - b * HWl, oh = rem / a.Wl, ow = rem - oh * a.Wl;
-            off = ((b * a.Hout + oh * a.os + a.oph[cls]) * a.Wout + ow * a.os + a.opw[cls]) * a.Nout;
-        }
-        rowoff[tid] = off;
-    }
+    if (tid < BM) rowoff[tid] = lattice_rowoff(a, cls, m0 + tid, HWl);
 
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    acc_zero(acc);
 
     auto compute = [&](const float* __restrict__ Asm, const float* __restrict__ Bsm) {
 #pragma unroll
@@ -161,29 +153,17 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_kernel(const F
         __syncthreads();
         compute(As[0], Bs[0]);
     } else {
-        // Operand rows come through buffer descriptors: an out-of-range offset (row outside the
-        // image / the problem) returns zeros in hardware, so the K loop has no per-load branches.
-        constexpr unsigned OOB = 0x80000000u;  // >= num_records for every tensor we accept (< 2^31 bytes)
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
             (void*)a.x, 0, (int)((unsigned)a.B * a.Hin * a.Win * a.Cin * 4u), 0x00020000);
         const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
             (void*)a.w, 0, (int)((unsigned)a.Nout * a.Tw * a.Cin * 4u), 0x00020000);
-        const int col4 = (tid & 7) * 4;
-        int a_pix[APT], a_oh[APT], a_ow[APT];
-#pragma unroll
-        for (int p = 0; p < APT; ++p) {
-            int m = m0 + (tid >> 3) + RSTEP * p;
-            if (m < a.M) {
-                int b = m / HWl, rem = m - b * HWl, oh = rem / a.Wl, ow = rem - oh * a.Wl;
-                a_pix[p] = b * a.Hin; a_oh[p] = oh * a.is; a_ow[p] = ow * a.is;
-            } else {
-                a_pix[p] = 0; a_oh[p] = -(1 << 28); a_ow[p] = 0;
-            }
-        }
+        const int col4 = (tid & 7) * 4, r0 = tid >> 3;
+        LatticeRows<APT> rows;
+        rows.init(a, m0 + r0, RSTEP, HWl);
         unsigned b_row[BL];
 #pragma unroll
         for (int p = 0; p < BL; ++p) {
-            int n = n0 + (tid >> 3) + RSTEP * p;
+            int n = n0 + r0 + RSTEP * p;
             b_row[p] = n < a.Nout ? (unsigned)(n * a.Tw * a.Cin + col4) * 4u : OOB;
         }
 
@@ -201,225 +181,60 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_kernel(const F
         // ms per step of conv_kernel<128,2,4>): one set, rolled loop 28.9; one set, unrolled 28.8; this form 28.2; the same with
         // branch-free (always issued, range-masked) loads and stores, which lets the loads of step s + 2 stay in flight across
         // the staging point, 28.8 -- DESIGN.md 4.1.
-        u32x4 ra[APT], rb[BL], ra2[APT], rb2[BL];
-        unsigned a_off[APT];
+        OperandRegs<APT, BL> regs0, regs1;     // even / odd steps (counted from s_begin)
         int t = s_begin / cpk, ci = s_begin - t * cpk;
-        auto set_tap = [&](int tp) {
-            const int dh = taps.dh[tp], dw = taps.dw[tp];
-#pragma unroll
-            for (int p = 0; p < APT; ++p) {
-                int ih = a_oh[p] + dh, iw = a_ow[p] + dw;
-                bool ok = (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
-                a_off[p] = ok ? (unsigned)(((a_pix[p] + ih) * a.Win + iw) * a.Cin + col4) * 4u : OOB;
-            }
-        };
-        auto load = [&]() {
+        auto load = [&](OperandRegs<APT, BL>& regs) {       // the next K step in order, then advance (tap, channel chunk)
             const int c0b = ci * BK * 4;
             const int wofs = (taps.wslot[t] * a.Cin) * 4 + c0b;
-#pragma unroll
-            for (int p = 0; p < APT; ++p) ra[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, a_off[p], c0b, 0);
-#pragma unroll
-            for (int p = 0; p < BL; ++p) rb[p] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_row[p], wofs, 0);
+            regs.load(xr, wr, rows.off, b_row, c0b, wofs);
+            if (++ci == cpk) { ci = 0; ++t; if (t < taps.n) rows.set_tap(a, taps, t, col4); }
         };
-        auto stage = [&](int buf) {
-#pragma unroll
-            for (int p = 0; p < APT; ++p)
-                *reinterpret_cast<u32x4*>(&As[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = ra[p];
-#pragma unroll
-            for (int p = 0; p < BL; ++p)
-                *reinterpret_cast<u32x4*>(&Bs[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = rb[p];
-        };
-        auto advance = [&]() {
-            if (++ci == cpk) { ci = 0; ++t; if (t < taps.n) set_tap(t); }
-        };
-        auto load2 = [&]() {      // second register set
-            const int c0b = ci * BK * 4;
-            const int wofs = (taps.wslot[t] * a.Cin) * 4 + c0b;
-#pragma unroll
-            for (int p = 0; p < APT; ++p) ra2[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, a_off[p], c0b, 0);
-#pragma unroll
-            for (int p = 0; p < BL; ++p) rb2[p] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_row[p], wofs, 0);
-        };
-        auto stage2 = [&](int buf) {
-#pragma unroll
-            for (int p = 0; p < APT; ++p)
-                *reinterpret_cast<u32x4*>(&As[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = ra2[p];
-#pragma unroll
-            for (int p = 0; p < BL; ++p)
-                *reinterpret_cast<u32x4*>(&Bs[buf][((tid >> 3) + RSTEP * p) * LDT + col4]) = rb2[p];
-        };
-        // fragment double-buffering: the LDS reads of K-chunk c+1 are issued before the MFMAs of
-        // chunk c, and the next tile is staged into the other LDS buffer while chunks 2-3 compute
         const int arow = (wm * WTM + (lane & 31)) * LDT + (lane >> 5) * 4;
         const int brow = (wn * WTN + (lane & 31)) * LDT + (lane >> 5) * 4;
-        auto readfrag = [&](const float* __restrict__ Asm, const float* __restrict__ Bsm, int kc, float4 (&af)[MB], float4 (&bf)[NB]) {
-#pragma unroll
-            for (int i = 0; i < MB; ++i) af[i] = *reinterpret_cast<const float4*>(&Asm[arow + i * 32 * LDT + kc * 8]);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) bf[j] = *reinterpret_cast<const float4*>(&Bsm[brow + j * 32 * LDT + kc * 8]);
-        };
-        // k-major order: consecutive MFMAs rotate over all MB*NB accumulators, so an accumulator is
-        // re-used only every MB*NB-th instruction (dependent-accumulator latency never on the issue path)
-        auto mfma_chunk = [&](const float4 (&af)[MB], const float4 (&bf)[NB]) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < MB; ++i)
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) {
-                        const float av = e == 0 ? af[i].x : e == 1 ? af[i].y : e == 2 ? af[i].z : af[i].w;
-                        const float bv = e == 0 ? bf[j].x : e == 1 ? bf[j].y : e == 2 ? bf[j].z : bf[j].w;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                    }
-        };
 
-        {
-            if (s_begin < s_end) {
-                set_tap(t);
-                load(); advance();
-                if (s_begin + 1 < s_end) { load2(); advance(); }
-                stage(0);
-            }
+        if (s_begin < s_end) {
+            rows.set_tap(a, taps, t, col4);
+            load(regs0);
+            if (s_begin + 1 < s_end) load(regs1);
+            regs0.template stage<RSTEP>(As[0], Bs[0], r0, col4);
+        }
+        __syncthreads();
+        FV_STAMP(1);
+        auto body = [&](int s, auto odd) {
+            constexpr int ODD = decltype(odd)::value;       // even steps: LDS buffer 0, the next step staged from regs1 into buffer 1
+            if (s + 2 < s_end) load(ODD ? regs1 : regs0);
+            k_step(acc, As[ODD], Bs[ODD], arow, brow, [&] {
+                if (s + 1 < s_end) (ODD ? regs0 : regs1).template stage<RSTEP>(As[1 - ODD], Bs[1 - ODD], r0, col4);
+            });
             __syncthreads();
-            FV_STAMP(1);
-            auto body = [&](int s, auto odd) {
-                constexpr bool ODD = decltype(odd)::value;      // even steps (from s_begin): LDS 0, next staged from set 2
-                const float* Ac = As[ODD ? 1 : 0]; const float* Bc = Bs[ODD ? 1 : 0];
-                if (s + 2 < s_end) { if constexpr (ODD) load2(); else load(); advance(); }
-                float4 af0[MB], bf0[NB], af1[MB], bf1[NB];
-                readfrag(Ac, Bc, 0, af0, bf0);
-                readfrag(Ac, Bc, 1, af1, bf1);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_chunk(af0, bf0);
-                __builtin_amdgcn_sched_barrier(0);
-                readfrag(Ac, Bc, 2, af0, bf0);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_chunk(af1, bf1);
-                __builtin_amdgcn_sched_barrier(0);
-                readfrag(Ac, Bc, 3, af1, bf1);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_chunk(af0, bf0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (s + 1 < s_end) { if constexpr (ODD) stage(0); else stage2(1); }
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_chunk(af1, bf1);
-                __syncthreads();
-            };
-            for (int s = s_begin; s < s_end; s += 2) {
-                body(s, std::false_type{});
-                if (s + 1 < s_end) body(s + 1, std::true_type{});
-            }
+        };
+        for (int s = s_begin; s < s_end; s += 2) {
+            body(s, std::false_type{});
+            if (s + 1 < s_end) body(s + 1, std::true_type{});
         }
     }
 
     // ------------------------------------------------------------------ epilogue
     FV_STAMP(2);
     const int half = lane >> 5, lc = lane & 31;
+    float* Cs = smem;                    // the (now free) operand LDS takes the BM x BN output tile
     if (tail_part) {
         // K-slice of a tail tile: raw partial tile, tile-local [BM][BN] layout, to its slab
-        float* Cs = smem;
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Cs[(wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * BN + wn * WTN + j * 32 + lc] = acc[i][j][r];
+        acc_to_lds<BN>(Cs, acc, wm * WTM, wn * WTN, half, lc);
         __syncthreads();
         float4* dst = reinterpret_cast<float4*>(a.tail_slab + (size_t)tail_q * (BM * BN));
 #pragma unroll
         for (int p = 0; p < BM * BN / 4 / NTH; ++p) dst[tid + NTH * p] = reinterpret_cast<const float4*>(Cs)[tid + NTH * p];
         return;
     }
-    if (a.epi & FV_EPI_STATS) {
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { float v = acc[i][j][r]; s += v; q += v * v; }
-            s += __shfl_xor(s, 32);
-            q += __shfl_xor(q, 32);
-            if (half == 0) { red[0][wm][wn * WTN + j * 32 + lc] = s; red[1][wm][wn * WTN + j * 32 + lc] = q; }
-        }
-        __syncthreads();
-        if (tid < BN && n0 + tid < a.Nout) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int w = 0; w < WAVES_M; ++w) { s += red[0][w][tid]; q += red[1][w][tid]; }
-            stat_store(a, mt, n0 + tid, s, q);
-        }
-    }
+    if (a.epi & FV_EPI_STATS) tile_stats(a, acc, red, wm, wn * WTN, half, lc, tid, n0, mt);
     if ((a.Nout & 3) == 0) {
-        // Wide store path.  In the accumulator layout a lane owns one output column and 16 scattered
-        // rows, i.e. 64 four-byte stores per lane and tile -- a store-issue-bound tail of ~10 us per
-        // tile.  Transpose the tile through the (now free) operand LDS and write whole 16-byte pieces:
-        // 4x fewer store instructions, every wave instruction covers two full 512-byte rows.
-        float* Cs = smem;
         __syncthreads();         // every wave is done reading the operand tiles
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Cs[(wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * BN + wn * WTN + j * 32 + lc] = acc[i][j][r];
+        acc_to_lds<BN>(Cs, acc, wm * WTM, wn * WTN, half, lc);
         __syncthreads();
-        constexpr int C4 = BN / 4;                   // float4 pieces per tile row
-        float* outp = a.out + (size_t)blockIdx.y * a.split_stride;
-        const bool bnred = (a.epi & FV_EPI_BNRED) != 0;
-        BnRedAcc br;                                 // NTH % C4 == 0: a thread keeps its 4 columns over the rows
-        br.init(a, n0 + (tid % C4) * 4, bnred && n0 + (tid % C4) * 4 < a.Nout);
-        // The tile leaves in groups of four pieces per thread: the global loads of a group (the residual addend; z of the fused
-        // BN-backward reduction) are ALL issued before the first of them is used.  Piece by piece -- load, wait, combine, store --
-        // every one of the BM * C4 / NTH pieces paid a full memory round trip (eight s_waitcnt vmcnt(0) in a row): ~10 us per tile,
-        // which is most of a 1x1 data-gradient tile's life (4 - 8 K steps).  Rows outside the problem load from row 0 (in range,
-        // unused).
-        constexpr int NP = BM * C4 / NTH, GP = NP < 4 ? NP : 4;
-        static_assert(NP % GP == 0, "epilogue grouping");
-        const bool addon = (a.epi & FV_EPI_ADD) != 0;
-#pragma unroll
-        for (int p0 = 0; p0 < NP; p0 += GP) {
-            int offn[GP]; bool okp[GP];
-            float4 zq[GP], aq[GP];
-#pragma unroll
-            for (int q = 0; q < GP; ++q) {
-                const int f = tid + NTH * (p0 + q), row = f / C4, c4 = (f % C4) * 4;
-                const int off = rowoff[row], n = n0 + c4;
-                okp[q] = off >= 0 && n < a.Nout;
-                offn[q] = okp[q] ? off + n : 0;
-            }
-            if (bnred) {
-#pragma unroll
-                for (int q = 0; q < GP; ++q) zq[q] = *reinterpret_cast<const float4*>(a.bn_z + offn[q]);
-            }
-            if (addon) {
-#pragma unroll
-                for (int q = 0; q < GP; ++q) aq[q] = *reinterpret_cast<const float4*>(a.addend + offn[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < GP; ++q) {
-                const int f = tid + NTH * (p0 + q), row = f / C4, c4 = (f % C4) * 4;
-                const int n = n0 + c4;
-                if (okp[q]) {
-                    float4 v = *reinterpret_cast<const float4*>(&Cs[row * BN + c4]);
-                    if (a.epi & FV_EPI_AFFINE) {
-                        if (a.scale) { const float4 s = *reinterpret_cast<const float4*>(a.scale + n); v.x *= s.x; v.y *= s.y; v.z *= s.z; v.w *= s.w; }
-                        if (a.shift) { const float4 s = *reinterpret_cast<const float4*>(a.shift + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-                    }
-                    if (a.epi & FV_EPI_LEAKY) {
-                        v.x = v.x > 0.f ? v.x : v.x * a.leaky; v.y = v.y > 0.f ? v.y : v.y * a.leaky;
-                        v.z = v.z > 0.f ? v.z : v.z * a.leaky; v.w = v.w > 0.f ? v.w : v.w * a.leaky;
-                    }
-                    if (addon) { v.x += aq[q].x; v.y += aq[q].y; v.z += aq[q].z; v.w += aq[q].w; }
-                    *reinterpret_cast<float4*>(outp + offn[q]) = v;
-                    if (bnred) br.add(v, zq[q], a.bn_leaky);
-                }
-            }
-        }
-        if (bnred) bnred_flush<BN, NTH>(a, br, smem + BM * BN, n0, mt + cls * (int)(gridDim.x / NT), tid);
+        wide_store<BM, BN, NTH>(a, Cs, a.out + (size_t)blockIdx.y * a.split_stride, RowTable{rowoff}, n0, mt + cls * (int)(gridDim.x / NT), tid,
+                                (a.epi & FV_EPI_BNRED) != 0);
         FV_STAMP(3);
         return;
     }
@@ -437,7 +252,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_kernel(const F
         for (int i = 0; i < MB; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int row = wm * WTM + i * 32 + acc_row(r, half);
                 const int off = rowoff[row];
                 if (off >= 0 && nv) {
                     float v = acc[i][j][r];
@@ -468,14 +283,7 @@ __global__ __launch_bounds__(1024) void conv_tail_fixup_kernel(const FvConvArgs 
     const int mt = tile / NT, nt = tile - mt * NT;
     const int m0 = mt * BM, n0 = nt * BN;
     const int HWl = a.Hl * a.Wl;
-    if (tid < BM) {
-        int m = m0 + tid, off = -1;
-        if (m < a.M) {
-            int b = m / HWl, rem = m - b * HWl, oh = rem / a.Wl, ow = rem - oh * a.Wl;
-            off = ((b * a.Hout + oh * a.os + a.oph[0]) * a.Wout + ow * a.os + a.opw[0]) * a.Nout;
-        }
-        rowoff[tid] = off;
-    }
+    if (tid < BM) rowoff[tid] = lattice_rowoff(a, 0, m0 + tid, HWl);
     __syncthreads();
     const int c4 = (tid % C4) * 4, rl = tid / C4;
     const int n = n0 + c4;
@@ -498,18 +306,7 @@ __global__ __launch_bounds__(1024) void conv_tail_fixup_kernel(const FvConvArgs 
         cq.x += v.x * v.x; cq.y += v.y * v.y; cq.z += v.z * v.z; cq.w += v.w * v.w;
         const int off = rowoff[row];
         if (off >= 0 && n < a.Nout) {
-            if (a.epi & FV_EPI_AFFINE) {
-                if (a.scale) { const float4 s = *reinterpret_cast<const float4*>(a.scale + n); v.x *= s.x; v.y *= s.y; v.z *= s.z; v.w *= s.w; }
-                if (a.shift) { const float4 s = *reinterpret_cast<const float4*>(a.shift + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-            }
-            if (a.epi & FV_EPI_LEAKY) {
-                v.x = v.x > 0.f ? v.x : v.x * a.leaky; v.y = v.y > 0.f ? v.y : v.y * a.leaky;
-                v.z = v.z > 0.f ? v.z : v.z * a.leaky; v.w = v.w > 0.f ? v.w : v.w * a.leaky;
-            }
-            if (a.epi & FV_EPI_ADD) {
-                const float4 s = *reinterpret_cast<const float4*>(a.addend + off + n);
-                v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w;
-            }
+            piece_transform(a, v, n, (a.epi & FV_EPI_ADD) != 0, reinterpret_cast<const float4*>(a.addend + off + n));
             *reinterpret_cast<float4*>(a.out + off + n) = v;
             if (bnred) br.add(v, zv, a.bn_leaky);
         }
@@ -660,8 +457,6 @@ void fv_conv_tail_plan(int M, int Nout, int ksteps, int* tail_f, int* tail_full,
         *tail_f = best_f; *tail_full = full; *slab_floats = (long long)R * best_f * BM * 128;
     }
 }
-
-static inline bool gather_cin(int cin) { return cin % BK != 0; }
 
 int fv_conv_launch(fv_ctx* ctx, const FvConvArgs& a) {
     FV_REQUIRE(ctx, a.x && a.w && a.out, "conv: NULL tensor");

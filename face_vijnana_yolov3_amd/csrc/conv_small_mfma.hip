@@ -9,8 +9,8 @@
 // waves) each multiply 1/Q of the K steps from their own double-buffered operand tiles in LDS -- Q independent load -> LDS -> MFMA
 // chains per CU instead of one --, then groups 1 .. Q-1 park their accumulators in LDS and group 0's layout adds them in group
 // order (deterministic, whatever finishes first), followed by the inference epilogue (affine, LeakyReLU, residual).  No slabs, no
-// finish launch.  Gather addressing as in conv_kernel (taps, stride, out-of-image rows read as zeros through the buffer
-// descriptor); forward launches only (dense output lattice).
+// finish launch.  Gather addressing (LatticeRows), the MFMA chunk, the accumulator row formula and the per-piece output transform
+// are conv_kernel's own (conv_tile.h); forward launches only (dense output lattice).
 //   <64, 64, 4>  52x52 3x3 layers (172 workgroups, 9 steps per group)        <64, 32, 4>  26x26 3x3, 52x52 1x1 (176 / 172, 18 / 2)
 //   <32, 32, 8>  13x13 3x3 and 1x1, 26x26 1x1 (192 / 96 / 176 workgroups, 18 / 4 / 2 steps)
 // fv_conv_small_plan picks the configuration with the shortest chain that fits 256 workgroups, or none (the tile kernels).
@@ -54,80 +54,40 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const FvConvArgs a) 
     float* As0 = smem + (PRIV ? wave : q) * UF;  // [2][AR][LDT]
     float* Bs0 = As0 + 2 * AR * LDT;             // [2][TN][LDT]
 
-    constexpr unsigned OOB = 0x80000000u;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)((unsigned)a.B * a.Hin * a.Win * a.Cin * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t wr_ = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (int)((unsigned)a.Nout * a.Tw * a.Cin * 4u), 0x00020000);
     const int col4 = (ut & 7) * 4, r0 = ut >> 3;
     const int HWl = a.Hl * a.Wl;
-    int a_pix[APT], a_oh[APT], a_ow[APT];        // image row base, input row / column of tap (0, 0) for this thread's A rows
-#pragma unroll
-    for (int p = 0; p < APT; ++p) {
-        const int m = m0 + arow0 + r0 + RS * p;
-        if (m < a.M) {
-            const int b = m / HWl, rem = m - b * HWl, oh = rem / a.Wl, ow = rem - oh * a.Wl;
-            a_pix[p] = b * a.Hin; a_oh[p] = oh * a.is; a_ow[p] = ow * a.is;
-        } else {
-            a_pix[p] = 0; a_oh[p] = -(1 << 28); a_ow[p] = 0;          // every tap lands outside the image: zeros
-        }
-    }
+    LatticeRows<APT> rows;                       // this thread's A rows
+    rows.init(a, m0 + arow0 + r0, RS, HWl);
     unsigned b_row[BPT];
 #pragma unroll
     for (int p = 0; p < BPT; ++p) b_row[p] = (unsigned)((n0 + r0 + RS * p) * a.Tw * a.Cin + col4) * 4u;   // Nout % TN == 0: in range
 
-    u32x4 ra[PF][APT], rb[PF][BPT];
+    OperandRegs<APT, BPT> regs[PF];
     // Steps are requested in order, so (tap, channel chunk) of the NEXT request advance incrementally and the row offsets of a tap are
     // worked out once per tap, as in conv_kernel (the first version divided and redid the bounds tests in every step: ~100 vector
     // instructions per thread and step, which compete with the MFMAs for the issue slot).
     int lt = (q * per) / cpk, lci = (q * per) - lt * cpk;
-    unsigned a_off[APT];
-    auto set_tap = [&](int t) {
-        const int dh = taps.dh[t], dw = taps.dw[t];
-#pragma unroll
-        for (int p = 0; p < APT; ++p) {
-            const int ih = a_oh[p] + dh, iw = a_ow[p] + dw;
-            const bool ok = (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
-            a_off[p] = ok ? (unsigned)(((a_pix[p] + ih) * a.Win + iw) * a.Cin + col4) * 4u : OOB;
-        }
-    };
-    set_tap(lt);
+    rows.set_tap(a, taps, lt, col4);
     auto load = [&](int slot) {                  // the next K step of THIS group
         const int c0b = lci * BK * 4;
         const int wofs = taps.wslot[lt] * a.Cin * 4 + c0b;
-#pragma unroll
-        for (int p = 0; p < APT; ++p) ra[slot][p] = __builtin_amdgcn_raw_buffer_load_b128(xr, a_off[p], c0b, 0);
-#pragma unroll
-        for (int p = 0; p < BPT; ++p) rb[slot][p] = __builtin_amdgcn_raw_buffer_load_b128(wr_, b_row[p], wofs, 0);
-        if (++lci == cpk) { lci = 0; ++lt; if (lt < taps.n) set_tap(lt); }
+        regs[slot].load(xr, wr_, rows.off, b_row, c0b, wofs);
+        if (++lci == cpk) { lci = 0; ++lt; if (lt < taps.n) rows.set_tap(a, taps, lt, col4); }
     };
-    auto stage = [&](int buf, int slot) {
-#pragma unroll
-        for (int p = 0; p < APT; ++p) *reinterpret_cast<u32x4*>(&As0[buf * AR * LDT + (r0 + RS * p) * LDT + col4]) = ra[slot][p];
-#pragma unroll
-        for (int p = 0; p < BPT; ++p) *reinterpret_cast<u32x4*>(&Bs0[buf * TN * LDT + (r0 + RS * p) * LDT + col4]) = rb[slot][p];
-    };
-    f32x16 acc[NBK];
-#pragma unroll
-    for (int j = 0; j < NBK; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    auto stage = [&](int buf, int slot) { regs[slot].template stage<RS>(As0 + buf * AR * LDT, Bs0 + buf * TN * LDT, r0, col4); };
+    f32x16 acc[1][NBK];
+    acc_zero(acc);
     const int arow = ((PRIV ? 0 : wr * 32) + (lane & 31)) * LDT + (lane >> 5) * 4;
     const int brow = (lane & 31) * LDT + (lane >> 5) * 4;
-    auto compute = [&](int cur) {                // the chunk / lane-half k order of conv_kernel
+    auto compute = [&](int cur) {                // chunk by chunk, no scheduling barriers: read, multiply
         const float* Ac = As0 + cur * AR * LDT; const float* Bc = Bs0 + cur * TN * LDT;
 #pragma unroll
         for (int kc = 0; kc < BK / 8; ++kc) {
-            const float4 af = *reinterpret_cast<const float4*>(&Ac[arow + kc * 8]);
-            float4 bf[NBK];
-#pragma unroll
-            for (int j = 0; j < NBK; ++j) bf[j] = *reinterpret_cast<const float4*>(&Bc[brow + j * 32 * LDT + kc * 8]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int j = 0; j < NBK; ++j) {
-                    const float av = e == 0 ? af.x : e == 1 ? af.y : e == 2 ? af.z : af.w;
-                    const float bv = e == 0 ? bf[j].x : e == 1 ? bf[j].y : e == 2 ? bf[j].z : bf[j].w;
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[j], 0, 0, 0);
-                }
+            float4 af[1], bf[NBK];
+            readfrag<1, NBK>(Ac, Bc, arow, brow, kc, af, bf);
+            mfma_chunk<1, NBK>(acc, af, bf);
         }
     };
 
@@ -154,13 +114,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const FvConvArgs a) 
     // hand-off: groups 1 .. Q-1 park their accumulators tile-local [TM][TN]; group 0's layout adds them in group order
     const int half = lane >> 5, lc = lane & 31;
     float* H = smem;                             // [Q-1][TM][TN] parked tiles, then [TM][TN] the sum
-    if (q > 0) {
-#pragma unroll
-        for (int j = 0; j < NBK; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                H[(q - 1) * TM * TN + (wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * TN + j * 32 + lc] = acc[j][r];
-    }
+    if (q > 0) acc_to_lds<TN>(H + (q - 1) * TM * TN, acc, wr * 32, 0, half, lc);
     __syncthreads();
     float* Cs = smem + (Q - 1) * TM * TN;
     if (q == 0) {
@@ -168,8 +122,8 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const FvConvArgs a) 
         for (int j = 0; j < NBK; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int e = (wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * TN + j * 32 + lc;
-                float v = acc[j][r];
+                const int e = (wr * 32 + acc_row(r, half)) * TN + j * 32 + lc;
+                float v = acc[0][j][r];
 #pragma unroll
                 for (int g = 0; g < Q - 1; ++g) v += H[g * TM * TN + e];
                 Cs[e] = v;
@@ -183,16 +137,8 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const FvConvArgs a) 
         const int m = m0 + row, n = n0 + c4;
         if (m >= a.M) continue;
         float4 v = *reinterpret_cast<const float4*>(&Cs[row * TN + c4]);
-        if (a.epi & FV_EPI_AFFINE) {
-            if (a.scale) { const float4 sc = *reinterpret_cast<const float4*>(a.scale + n); v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
-            if (a.shift) { const float4 sh = *reinterpret_cast<const float4*>(a.shift + n); v.x += sh.x; v.y += sh.y; v.z += sh.z; v.w += sh.w; }
-        }
-        if (a.epi & FV_EPI_LEAKY) {
-            v.x = v.x > 0.f ? v.x : v.x * a.leaky; v.y = v.y > 0.f ? v.y : v.y * a.leaky;
-            v.z = v.z > 0.f ? v.z : v.z * a.leaky; v.w = v.w > 0.f ? v.w : v.w * a.leaky;
-        }
         const size_t off = (size_t)m * a.Nout + n;
-        if (a.epi & FV_EPI_ADD) { const float4 sk = *reinterpret_cast<const float4*>(a.addend + off); v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w; }
+        piece_transform(a, v, n, (a.epi & FV_EPI_ADD) != 0, reinterpret_cast<const float4*>(a.addend + off));
         *reinterpret_cast<float4*>(a.out + off) = v;
     }
 }
