@@ -109,6 +109,8 @@ def _declare(L):
                                     ctypes.POINTER(ctypes.c_int32)]),
         'fv_letterbox_crops': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
+        'fv_crop_nearest_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
+                                    ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_yolov3_num_layers': (i32, []),
         'fv_yolov3_layer': (i32, [i32, i32, ctypes.POINTER(LayerDesc)]),
         'fv_yolov3_param_count': (i64, [i32]),

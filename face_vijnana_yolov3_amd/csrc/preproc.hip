@@ -135,6 +135,55 @@ __global__ __launch_bounds__(256) void letterbox_crops_kernel(const unsigned cha
     o[0] = r; o[1] = g; o[2] = b;
 }
 
+// Nearest-neighbour crop + letterbox on uint8 (create_db_fi, fi.py:113-161: cv.resize(INTER_NEAREST) then cv.copyMakeBorder(0)):
+// a pure gather.  A crop's S x S x 3 output is one flat run of 16-byte chunks; a workgroup writes CNU_CHUNKS consecutive chunks of
+// crop blockIdx.y, one 16-byte store per lane, lanes on consecutive chunks (1 KiB per wave-instruction), the padding written as
+// zeros by the same stores.  The fp64 column index (OpenCV's resizeNN: min(floor(x * ifx), w - 1), ifx = 1.0 / (w_p / (double)w))
+// is computed once per output column per workgroup and expanded to a per-output-BYTE table of source byte offsets in LDS (3S
+// int32, -1 = padding), so a chunk is 4 ds_read_b128 + 16 byte loads; the row index is one fp64 multiply per chunk.
+constexpr int CNU_THREADS = 256;
+constexpr int CNU_ITERS = 4;                          // chunks per thread: the table build (3S entries) is amortised over 16 KiB of output
+constexpr int CNU_CHUNKS = CNU_THREADS * CNU_ITERS;
+constexpr int CNU_MAX_S = 4096;                       // 3S int32 of LDS <= 48 KiB
+
+__global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsigned char* __restrict__ packed, LbcTable t, int S,
+                                                                      unsigned char* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) int cnu_src[];      // [3S]: source byte offset inside a row of output byte b, or -1
+    const int c = blockIdx.y;
+    const int h = t.h[c], w = t.w[c], w_p = t.w_p[c], h_p = t.h_p[c], pitch = t.pitch[c], pad_t = t.pad_t[c], pad_l = t.pad_l[c];
+    const double ifx = 1.0 / ((double)w_p / (double)w), ify = 1.0 / ((double)h_p / (double)h);
+    for (int x = threadIdx.x; x < S; x += CNU_THREADS) {
+        const int xi = x - pad_l;
+        int o = -1;
+        if (xi >= 0 && xi < w_p) o = min((int)floor(xi * ifx), w - 1) * 3;
+        cnu_src[3 * x] = o; cnu_src[3 * x + 1] = o < 0 ? -1 : o + 1; cnu_src[3 * x + 2] = o < 0 ? -1 : o + 2;
+    }
+    __syncthreads();
+    const unsigned char* __restrict__ src = packed + t.off[c];
+    const int row_chunks = 3 * S / 16, n_chunks = S * row_chunks;
+    uint4* __restrict__ out = reinterpret_cast<uint4*>(dst + (size_t)c * S * S * 3);
+#pragma unroll
+    for (int it = 0; it < CNU_ITERS; ++it) {
+        const int q = blockIdx.x * CNU_CHUNKS + it * CNU_THREADS + threadIdx.x;
+        if (q >= n_chunks) break;
+        const int y = q / row_chunks, j = q - y * row_chunks;
+        const int yi = y - pad_t;
+        unsigned v[4] = {0u, 0u, 0u, 0u};
+        if (yi >= 0 && yi < h_p) {
+            const unsigned char* __restrict__ row = src + (size_t)min((int)floor(yi * ify), h - 1) * pitch;
+            const int4* tab = reinterpret_cast<const int4*>(cnu_src + 16 * j);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int4 o = tab[k];
+                const unsigned b0 = o.x >= 0 ? row[o.x] : 0u, b1 = o.y >= 0 ? row[o.y] : 0u;
+                const unsigned b2 = o.z >= 0 ? row[o.z] : 0u, b3 = o.w >= 0 ? row[o.w] : 0u;
+                v[k] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+            }
+        }
+        out[q] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+}
+
 bool lb_geometry(int h, int w, int S, int* g) {
     int w_p, h_p, pad_t = 0, pad_b = 0, pad_l = 0, pad_r = 0;
     if (w >= h) {   // face_detection.py:120-133
@@ -146,6 +195,39 @@ bool lb_geometry(int h, int w, int S, int* g) {
     }
     g[0] = w_p; g[1] = h_p; g[2] = pad_t; g[3] = pad_b; g[4] = pad_l; g[5] = pad_r;
     return w_p >= 1 && h_p >= 1;
+}
+
+// every record of a crop list (image, y0, x0, h, w) inside its image and letterboxable: checked before anything is enqueued,
+// so a bad record leaves dst untouched
+int lbc_validate(fv_ctx* ctx, const char* who, const int64_t* offsets, const int32_t* hw, int n_img, const int32_t* crops, int n, int S) {
+    for (int c = 0; c < n; ++c) {
+        const int* r = crops + 5 * c;
+        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
+        FV_REQUIRE(ctx, im >= 0 && im < n_img, "%s: crop %d names image %d of %d", who, c, im, n_img);
+        const int H = hw[2 * im], W = hw[2 * im + 1];
+        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "%s: bad image %d", who, im);
+        FV_REQUIRE(ctx, h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
+                   "%s: crop %d (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", who, c, y0, x0, h, w, im, H, W);
+        int g[6];
+        FV_REQUIRE(ctx, lb_geometry(h, w, S, g), "%s: crop %d (%d x %d) too elongated for image_size %d", who, c, h, w, S);
+    }
+    return FV_OK;
+}
+
+// crops [c0, c0 + nc) as the kernels' table; -> source bytes of those crops
+double lbc_fill(LbcTable& t, const int64_t* offsets, const int32_t* hw, const int32_t* crops, int c0, int nc, int S) {
+    double bytes = 0.0;
+    for (int i = 0; i < nc; ++i) {
+        const int* r = crops + 5 * (c0 + i);
+        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
+        const int W = hw[2 * im + 1];
+        int g[6];
+        lb_geometry(h, w, S, g);
+        t.off[i] = offsets[im] + ((long long)y0 * W + x0) * 3; t.pitch[i] = W * 3;
+        t.h[i] = h; t.w[i] = w; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
+        bytes += (double)h * w * 3;
+    }
+    return bytes;
 }
 
 }  // namespace
@@ -181,35 +263,41 @@ extern "C" int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int6
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, packed && offsets && hw && crops && dst && n_img >= 1 && n >= 1 && image_size >= 1, "letterbox_crops: bad arguments");
     const int S = image_size;
-    // validate every crop before anything is enqueued: a bad record leaves dst untouched
-    for (int c = 0; c < n; ++c) {
-        const int* r = crops + 5 * c;
-        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-        FV_REQUIRE(ctx, im >= 0 && im < n_img, "letterbox_crops: crop %d names image %d of %d", c, im, n_img);
-        const int H = hw[2 * im], W = hw[2 * im + 1];
-        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "letterbox_crops: bad image %d", im);
-        FV_REQUIRE(ctx, h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
-                   "letterbox_crops: crop %d (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", c, y0, x0, h, w, im, H, W);
-        int g[6];
-        FV_REQUIRE(ctx, lb_geometry(h, w, S, g), "letterbox_crops: crop %d (%d x %d) too elongated for image_size %d", c, h, w, S);
-    }
+    if (int rc = lbc_validate(ctx, "letterbox_crops", offsets, hw, n_img, crops, n, S)) return rc;
     for (int c0 = 0; c0 < n; c0 += LBC_MAX) {
         const int nc = n - c0 < LBC_MAX ? n - c0 : LBC_MAX;
         LbcTable t{};
-        double bytes = 0.0;
-        for (int i = 0; i < nc; ++i) {
-            const int* r = crops + 5 * (c0 + i);
-            const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-            const int W = hw[2 * im + 1];
-            int g[6];
-            lb_geometry(h, w, S, g);
-            t.off[i] = offsets[im] + ((long long)y0 * W + x0) * 3; t.pitch[i] = W * 3;
-            t.h[i] = h; t.w[i] = w; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
-            bytes += (double)h * w * 3 + 12.0 * S * S;
-        }
+        const double bytes = lbc_fill(t, offsets, hw, crops, c0, nc, S) + 12.0 * S * S * nc;
         FvProfScope ps(ctx, "letterbox_crops_kernel", 0.0, bytes);
         hipLaunchKernelGGL(letterbox_crops_kernel, dim3((S + 15) / 16, (S + 15) / 16, nc), dim3(256), 0, ctx->stream, packed, t, S,
                            dst + (size_t)c0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+extern "C" int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                                  const int32_t* crops, int n, int image_size, uint8_t* dst) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, n >= 0 && image_size >= 16 && image_size % 16 == 0 && image_size <= CNU_MAX_S,
+               "crop_nearest_u8: n %d, image_size %d (a multiple of 16 up to %d: rows are stored 16 bytes at a time)", n, image_size,
+               CNU_MAX_S);
+    if (n == 0) return FV_OK;
+    FV_REQUIRE(ctx, packed && offsets && hw && crops && dst && n_img >= 1 && ((uintptr_t)dst & 15) == 0,
+               "crop_nearest_u8: bad arguments (dst must be 16-byte aligned)");
+    const int S = image_size;
+    if (int rc = lbc_validate(ctx, "crop_nearest_u8", offsets, hw, n_img, crops, n, S)) return rc;
+    // The crop table travels in the kernel arguments, LBC_MAX crops per launch, as in fv_letterbox_crops: no device allocation, no
+    // host-to-device copy of a pageable table (which would block the host) and nothing that has to outlive the call; one launch of
+    // 64 crops is already ~2 000 workgroups at 416.
+    const int blocks = (S * (3 * S / 16) + CNU_CHUNKS - 1) / CNU_CHUNKS;
+    for (int c0 = 0; c0 < n; c0 += LBC_MAX) {
+        const int nc = n - c0 < LBC_MAX ? n - c0 : LBC_MAX;
+        LbcTable t{};
+        const double bytes = lbc_fill(t, offsets, hw, crops, c0, nc, S) + 3.0 * S * S * nc;
+        FvProfScope ps(ctx, "crop_nearest_u8_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(crop_nearest_u8_kernel, dim3(blocks, nc), dim3(CNU_THREADS), 3 * S * sizeof(int), ctx->stream, packed, t,
+                           S, dst + (size_t)c0 * S * S * 3);
         FV_LAUNCH_CHECK(ctx);
     }
     return FV_OK;

@@ -3,18 +3,23 @@
 Port of the reference's `src/space/face_identification.py` (fi.py): the model (fi.py:318-345), the facial-ID extractor
 (`_make_fid_extractor`, fi.py:378-395), `train` (fi.py:616-643) over its two triplet sequences (fi.py:1490-1601 and the VGGFace2
 variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `test` (fi.py:994-1153) and `main`
-(fi.py:1715-1760) for the modes implemented here.  The hot path is the C ABI (fv_fid_extract, fv_fid_train_step, fv_adam_step,
-fv_letterbox_crops, fv_fid_match, fv_fid_pair_dists); this module holds the weights and drives it.  Not ported: create_db_fi /
-save_extracted_face (the data mode), evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
+(fi.py:1715-1760) for the modes implemented here, and the data mode (`create_db_fi` / `save_extracted_face`, fi.py:78-280) that
+cuts the face crops and writes the subject db everything else reads.  The hot path is the C ABI (fv_fid_extract,
+fv_fid_train_step, fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match, fv_fid_pair_dists); this module holds the
+weights and drives it.  Not ported: evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
 moving-statistics update order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test()
-batching its frames and crops (same rows), fp64 match distances, and crops whose letterboxed side rounds to 0 being skipped (the
-reference's cv.resize raises)."""
+batching its frames and crops (same rows), fp64 match distances, crops whose letterboxed side rounds to 0 being skipped (the
+reference's cv.resize raises), and the data mode's walk by source file (section 16)."""
+import collections
+import csv
 import ctypes
 import glob
+import io
 import json
 import os
 import pickle
 import platform
+import shutil
 import time
 from random import shuffle
 
@@ -271,8 +276,13 @@ def crop_rect(box, h, w):
     projected box, Python slice semantics on an h x w image (a start of -1 -- a box on the top or left edge -- counts from the end
     and leaves the crop empty).  -> (y0, x0, rows, cols), or None for an empty crop (the reference skips it, fi.py:1072-1073)."""
     l, t, r, b = int(box.xmin), int(box.ymin), int(box.xmax), int(box.ymax)
-    ys = range(*slice(t - 1, b - 1).indices(int(h)))
-    xs = range(*slice(l - 1, r - 1).indices(int(w)))
+    return slice_rect(t - 1, b - 1, l - 1, r - 1, h, w)
+
+
+def slice_rect(y0, y1, x0, x1, h, w):
+    """`image[y0:y1, x0:x1]` of an h x w image with Python slice semantics -> (y0, x0, rows, cols), or None when it is empty."""
+    ys = range(*slice(y0, y1).indices(int(h)))
+    xs = range(*slice(x0, x1).indices(int(w)))
     if len(ys) == 0 or len(xs) == 0:
         return None
     return ys.start, xs.start, len(ys), len(xs)
@@ -413,6 +423,241 @@ def letterbox_crops(ctx, images, crops, image_size, out=None):
                                   (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
     ctx.check(rc, 'fv_letterbox_crops')
     return out
+
+
+def crop_nearest_u8(ctx, images, crops, image_size, out=None):
+    """fv_crop_nearest_u8: images and crops as for letterbox_crops -> (n, S, S, 3) uint8 CUDA tensor, each crop resized by
+    nearest neighbour to its letterbox size and zero padded (create_db_fi's cv.resize(INTER_NEAREST) + cv.copyMakeBorder)."""
+    dbuf, offs, hw = images
+    n, ni, S = len(crops), len(offs), int(image_size)
+    if out is None:
+        out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dbuf.device)
+    flat = [int(v) for c in crops for v in c]
+    rc = lib().fv_crop_nearest_u8(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni,
+                                  (ctypes.c_int32 * max(1, 5 * n))(*flat), n, S, ptr(out))
+    ctx.check(rc, 'fv_crop_nearest_u8')
+    return out
+
+
+# ----------------------------------------------------------------------------- data mode (fi.py:78-280)
+# One face crop to cut: the source image, the rectangle (y0, x0, rows, cols) inside it, the file name under the faces directory
+# and the db row (subject_id, face_file, w, h) -- w, h of the cut crop, not of the csv's box.
+CropRecord = collections.namedtuple('CropRecord', 'source rect name row')
+
+DATA_BATCH_BYTES = 192 << 20     # decoded RGB per batch: three 18-megapixel UCCS frames (their coefficients take as much again)
+DATA_BATCH_CROPS = 256           # crops per batch: 133 MB of output at 416, on the device and in each pinned slot
+
+
+def image_hw(path):
+    """(rows, columns) from the file's header; the pixels are not decoded."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size[1], im.size[0]
+
+
+def _keep(records, skipped, source, rect, name, subject_id, image_size):
+    if rect is None:
+        skipped['empty'] += 1
+    elif not lb_side_ok(rect[2], rect[3], image_size):
+        skipped['side_rounds_to_0'] += 1
+    else:
+        records.append(CropRecord(source, rect, name, (subject_id, name, rect[3], rect[2])))
+
+
+def uccs_records(raw_data_path, image_size, hw_of=image_hw):
+    """The crops create_db_fi cuts for UCCS (fi.py:92-167), in its order: training/training.csv grouped by SUBJECT_ID, the
+    subjects walked sorted, -1 skipped, a row skipped unless FACE_X, FACE_Y, FACE_WIDTH and FACE_HEIGHT are all > 0, the cut
+    `image[(t - 1):(b - 1), (l - 1):(r - 1)]` with l, t = int(x), int(y) and r, b = int(x + w - 1), int(y + h - 1).
+    -> (records, skipped): skipped counts the rows whose cut is empty or whose letterboxed side rounds to 0 (the reference
+    raises on those).  Reads the csv and, through hw_of(path), the image sizes; nothing else."""
+    import pandas as pd
+    gt = pd.read_csv(os.path.join(raw_data_path, 'training', 'training.csv'))
+    records, skipped, sizes = [], {'empty': 0, 'side_rounds_to_0': 0}, {}
+    for k, df in gt.groupby('SUBJECT_ID'):
+        if k == -1:
+            continue
+        for file_name, x, y, w, h in zip(df.iloc[:, 1], df.iloc[:, 3], df.iloc[:, 4], df.iloc[:, 5], df.iloc[:, 6]):
+            if not (x > 0 and y > 0 and w > 0 and h > 0):
+                continue
+            source = os.path.join(raw_data_path, 'training', file_name)
+            if source not in sizes:
+                sizes[source] = hw_of(source)
+            l, t, r, b = int(x), int(y), int(x + w - 1), int(y + h - 1)
+            stem, ext = os.path.splitext(file_name)
+            name = stem + '_' + str(k) + '_' + str(int(x)) + '_' + str(int(y)) + ext
+            _keep(records, skipped, source, slice_rect(t - 1, b - 1, l - 1, r - 1, *sizes[source]), name, k, image_size)
+    return records, skipped
+
+
+def vggface2_records(raw_data_path, image_size, hw_of=image_hw):
+    """The crops save_extracted_face cuts for VGGFace2 (fi.py:212-280), in loose_bb_train.csv's row order: a row with x < 0,
+    y < 0, w <= 0 or h <= 0 skipped, the cut `image[y:(y + h), x:(x + w)]` of train/<identity>/<file>.jpg clipped by the image,
+    saved as <identity>_<file>.jpg.  -> (records, skipped) as uccs_records."""
+    import pandas as pd
+    df = pd.read_csv(os.path.join(raw_data_path, 'loose_bb_train.csv'))
+    records, skipped, sizes = [], {'empty': 0, 'side_rounds_to_0': 0}, {}
+    for name_id, x, y, w, h in zip(df.iloc[:, 0], df.iloc[:, 1], df.iloc[:, 2], df.iloc[:, 3], df.iloc[:, 4]):
+        if x < 0 or y < 0 or w <= 0 or h <= 0:
+            continue
+        identity, file_name = name_id.split('/')[0], name_id.split('/')[1] + '.jpg'
+        source = os.path.join(raw_data_path, 'train', identity, file_name)
+        if source not in sizes:
+            sizes[source] = hw_of(source)
+        x, y, w, h = int(x), int(y), int(w), int(h)
+        _keep(records, skipped, source, slice_rect(y, y + h, x, x + w, *sizes[source]), identity + '_' + file_name, identity,
+              image_size)
+    return records, skipped
+
+
+def db_csv_text(records):
+    """The subject db as the reference's `db.to_csv()` writes it: the index column first -- every row's label is 0, each row
+    having been a one-row frame of its own before pd.concat -- then subject_id, face_file, w, h."""
+    f = io.StringIO()
+    out = csv.writer(f, lineterminator='\n')
+    out.writerow(['', 'subject_id', 'face_file', 'w', 'h'])
+    for r in records:
+        out.writerow([0] + list(r.row))
+    return f.getvalue()
+
+
+def source_batches(records, hw_of, batch_bytes=DATA_BATCH_BYTES, batch_crops=DATA_BATCH_CROPS):
+    """Group the records by source file (files in order of first appearance) and the files into batches of at most
+    batch_bytes of decoded RGB and batch_crops crops -- a single file beyond either makes a batch of its own.
+    -> [[(source, [record index, ...]), ...], ...]"""
+    by_source = collections.OrderedDict()
+    for i, r in enumerate(records):
+        by_source.setdefault(r.source, []).append(i)
+    batches, cur, nbytes, ncrops = [], [], 0, 0
+    for source, idx in by_source.items():
+        h, w = hw_of(source)
+        if cur and (nbytes + h * w * 3 > batch_bytes or ncrops + len(idx) > batch_crops):
+            batches.append(cur); cur, nbytes, ncrops = [], 0, 0
+        cur.append((source, idx)); nbytes += h * w * 3; ncrops += len(idx)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def load_batch(files, pool, ring, device_jpeg=True):
+    """Host half of a batch's decode, as FaceDetector._detect_files does it: the files Huffman-decoded on `pool` into a pinned
+    slot of `ring` -> ('jpeg', int16 coefficients, jpeg.BatchPlan); when the parser refuses one of them (progressive, CMYK, ...)
+    or the scan data are damaged, the batch decoded by Pillow -> pack_images' (buffer, offsets, hw)."""
+    from . import jpeg
+    from .face_detection import map_all
+    from .postproc import pack_images
+    if device_jpeg:
+        datas = list(pool.map(lambda f: open(f, 'rb').read(), files))
+        infos = [jpeg.parse(d) for d in datas]
+        if all(i is not None for i in infos):
+            plan = jpeg.BatchPlan(infos)
+            buf = ring.take(2 * plan.total_coefs).view(torch.int16)
+            view = buf.numpy()
+            try:
+                map_all(pool, lambda i: jpeg.entropy_decode(datas[i], infos[i],
+                                                            view[plan.coef_off[i]:plan.coef_off[i] + int(infos[i].total_coefs)]),
+                        range(len(files)))
+                return 'jpeg', buf, plan
+            except ValueError:
+                ring.untake()
+    return pack_images(list(pool.map(_imread, files)), ring=ring)
+
+
+def stage_batch(ctx, loaded, ring, device):
+    """Device half: the host-to-device copy and, for a 'jpeg' batch, fv_jpeg_reconstruct_batch -> (device uint8 buffer, offsets,
+    hw), the packed RGB images as fv_crop_nearest_u8 reads them."""
+    from . import jpeg
+    if isinstance(loaded[0], str):
+        _tag, coefs, plan = loaded
+        images = (jpeg.reconstruct_batch(ctx, plan, coefs.to(device, non_blocking=True), device), plan.rgb_off, plan.hw)
+        ring.copied(coefs)
+    else:
+        buf, offs, hw = loaded
+        images = (buf.to(device, non_blocking=True), offs, hw)
+        ring.copied(buf)
+    return images
+
+
+def write_crop(pixels, path):
+    from PIL import Image
+    Image.fromarray(pixels).save(path)
+
+
+def cut_and_write(ctx, records, image_size, out_dir, threads, hw_of=image_hw, device_jpeg=True, batch_bytes=DATA_BATCH_BYTES,
+                  batch_crops=DATA_BATCH_CROPS):
+    """Cut every record's crop and write it to out_dir/<name>.  Per batch of source files: decode (load_batch on a loader thread,
+    stage_batch), ONE fv_crop_nearest_u8 call for all its crops, the S x S x 3 uint8 crops copied to a pinned buffer, then
+    encoded and written by Pillow on the thread pool while the next batch decodes."""
+    from concurrent.futures import ThreadPoolExecutor, wait
+    from .postproc import PinnedRing
+    S = int(image_size)
+    dev = torch.device('cuda', ctx.device)
+    batches = source_batches(records, hw_of, batch_bytes, batch_crops)
+    if not batches:
+        return
+    ring = PinnedRing(3)
+    outs = [[None, []], [None, []]]              # two pinned output slots: (buffer, the writes still reading it)
+    with ThreadPoolExecutor(max_workers=threads) as pool, ThreadPoolExecutor(max_workers=1) as one:
+        pending = one.submit(load_batch, [s for s, _ in batches[0]], pool, ring, device_jpeg)
+        writes = []
+        for k, batch in enumerate(batches):
+            loaded = pending.result()
+            if k + 1 < len(batches):
+                pending = one.submit(load_batch, [s for s, _ in batches[k + 1]], pool, ring, device_jpeg)
+            images = stage_batch(ctx, loaded, ring, dev)
+            idx = [i for _, ii in batch for i in ii]
+            crops = [(f,) + tuple(records[i].rect) for f, (_, ii) in enumerate(batch) for i in ii]
+            cut = crop_nearest_u8(ctx, images, crops, S)
+            slot = outs[k % 2]
+            wait(slot[1])                         # the writes of batch k - 2 have let go of the slot
+            if slot[0] is None or slot[0].shape[0] < len(crops):
+                slot[0] = torch.empty((max(len(crops), min(batch_crops, len(records))), S, S, 3), dtype=torch.uint8).pin_memory()
+            host = slot[0][:len(crops)]
+            host.copy_(cut, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            pixels = host.numpy()
+            slot[1] = [pool.submit(write_crop, pixels[j], os.path.join(out_dir, records[i].name)) for j, i in enumerate(idx)]
+            writes += slot[1]
+        wait(writes)
+        for w in writes:
+            w.result()
+
+
+def create_db_fi(conf, device=None):
+    """The data mode (fi.py:78-210): cut every face of the resource's ground truth, letterbox it to image_size by nearest
+    neighbour and write it under <raw_data_path>/subject_faces/ (vggface2: subject_faces_vggface2/), emptied first; write the
+    subject db (subject_image_db.csv / subject_image_vggface2_db.csv) in the reference's row order.  A source image is decoded
+    once for all its faces (cut_and_write).  Rows the reference would raise on are skipped and counted.
+    -> {'written': crops, 'empty': ..., 'side_rounds_to_0': ...}"""
+    conf = conf['fi_conf']
+    db_file, faces_dir = db_files(conf['resource_type'])[:2]
+    raw_data_path = conf['raw_data_path']
+    S = int(conf['nn_arch']['image_size'])
+    if S % 32 or S < 32:
+        raise ValueError('image_size must be a positive multiple of 32 (network stride)')
+    if device is None:
+        device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
+    ctx = Context(device)                  # no GPU, no data mode -- found out before the faces directory is emptied
+    out_dir = os.path.join(raw_data_path, faces_dir)
+    if os.path.isdir(out_dir):
+        shutil.rmtree(out_dir)
+    os.mkdir(out_dir)
+    sizes = {}
+
+    def hw_of(path):
+        if path not in sizes:
+            sizes[path] = image_hw(path)
+        return sizes[path]
+    enumerate_records = uccs_records if conf['resource_type'] == RESOURCE_TYPE_UCCS else vggface2_records
+    records, skipped = enumerate_records(raw_data_path, S, hw_of)
+    from .face_detection import default_loader_threads
+    hps = conf.get('hps', {})
+    cut_and_write(ctx, records, S, out_dir, max(1, int(hps.get('loader_threads', default_loader_threads()))), hw_of,
+                  bool(hps.get('device_jpeg', True)))
+    with open(db_file, 'w') as f:
+        f.write(db_csv_text(records))
+    print('Saved %d face images to %s; skipped %d empty crops and %d whose letterboxed side rounds to 0.'
+          % (len(records), out_dir, skipped['empty'], skipped['side_rounds_to_0']))
+    return dict(skipped, written=len(records))
 
 
 # ----------------------------------------------------------------------------- FaceIdentifier (fi.py:288-643)
@@ -597,18 +842,29 @@ class FaceIdentifier(object):
 
 def main():
     """Reads ./face_vijnana_yolov3.json (Windows: _win) and dispatches on fi_conf.mode (fi.py:1715-1760):
+      data    create_db_fi: the face crops and the subject db of fi_conf.resource_type (no model is built); a configuration
+              that names neither 'uccs' nor 'vggface2' is refused like a mode that is not implemented;
       train   trains and saves face_identifier.h5, then builds the facial-ID database (make_facial_ids_db, register_facial_ids),
               as fi.py:1734-1743 does;
       fid_db  make_facial_ids_db, then register_facial_ids -- the reference leaves the second call commented out, but nothing else
               would register the IDs of a loaded model, and test() reads the registry;
       test    test() -> output_file_path.
-    'evaluate' and 'data' are not implemented here."""
+    'evaluate' is not implemented here."""
     name = 'face_vijnana_yolov3_win.json' if platform.system() == 'Windows' else 'face_vijnana_yolov3.json'
     with open(name, 'r') as f:
         conf = json.load(f)
     mode = conf['fi_conf']['mode']
-    if mode not in ('train', 'fid_db', 'test'):
-        raise NotImplementedError('fi_conf.mode %r is not implemented (available: train, fid_db, test)' % mode)
+    if mode not in ('data', 'train', 'fid_db', 'test'):
+        raise NotImplementedError('fi_conf.mode %r is not implemented (available: data, train, fid_db, test)' % mode)
+    if mode == 'data':                     # needs no model
+        resource_type = conf['fi_conf'].get('resource_type')
+        if resource_type not in (RESOURCE_TYPE_UCCS, RESOURCE_TYPE_VGGFACE2):
+            raise NotImplementedError('fi_conf.mode \'data\' is not implemented for resource_type %r (available: %s, %s)'
+                                      % (resource_type, RESOURCE_TYPE_UCCS, RESOURCE_TYPE_VGGFACE2))
+        ts = time.time()
+        create_db_fi(conf)
+        print('Elasped time: {0:f}s'.format(time.time() - ts))
+        return
     fi = FaceIdentifier(conf)
     ts = time.time()
     if mode == 'train':

@@ -314,6 +314,17 @@ int fv_letterbox_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offset
  * nothing is enqueued. */
 int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
                        const int32_t* crops, int n, int image_size, float* dst);
+/* Crop + nearest-neighbour letterbox of many face rectangles on uint8, in one call (create_db_fi / save_extracted_face,
+ * fi.py:113-161 and 233-274: the slice, cv.resize(INTER_NEAREST), cv.copyMakeBorder(value 0)).  Images and crop records as for
+ * fv_letterbox_crops; dst: device uint8 [n][S][S][3], 16-byte aligned; image_size a multiple of 16, at most 4096.  Geometry as
+ * fv_letterbox (int(h / w * S), the odd padding pixel at the bottom / right).  Destination pixel (y, x) of the resized area
+ * reads source pixel (min(floor(y * ify), h - 1), min(floor(x * ifx), w - 1)) of the crop, ifx = 1.0 / (w_p / (double)w), ify
+ * likewise, in IEEE fp64; the padding is 0.  That index rule is this build's DEFINITION of INTER_NEAREST (OpenCV's resizeNN as
+ * published); parity with cv2 itself is unpinned, as for the bicubic path.  A pure gather: exact against that definition.  Any
+ * number of crops (chunked inside the call); n == 0 does nothing.  A crop outside its image, h or w below 1, or a letterboxed
+ * side that rounds to 0 is FV_ERR_INVALID and nothing is enqueued. */
+int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                       const int32_t* crops, int n, int image_size, uint8_t* dst);
 
 /* ------------------------------------------------------------------ JPEG decode, split host / device
  * (replaces `imread` of fd.py:112, 656, 798 for baseline / extended-sequential Huffman JPEGs with 1 or 3
