@@ -128,6 +128,7 @@ def _declare(L):
         'fv_fid_workspace_bytes': (sz, [i32, i32, i32]),
         'fv_fid_extract': (i32, [vp, vp, vp, vp, i32, i32, vp, sz, vp]),
         'fv_fid_train_step': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+        'fv_fid_train_step_dp': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp, f64, BUCKET_FN, vp]),
         'fv_fid_dense_partial_floats': (i64, [i32, i64]),
         'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
         'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),

@@ -16,8 +16,9 @@ inline long long fv_fid_chunks(long long F) { return F / FID_KC; }
 int fv_fid_dense_fwd(fv_ctx* ctx, FidRows X, int M, long long F, const float* W, float* part);
 // u = l2_normalize(relu(sum of the partials in chunk order + bias)); pre (may be NULL) keeps the pre-activation
 int fv_fid_dense_finish(fv_ctx* ctx, const float* part, long long chunks, int M, const float* bias, float* pre, float* u);
-// triplet loss over B triplets (rows b, B + b, 2B + b of pre / u); dE [3B][64] = dL / d pre, dbias [64] = its column sums
-int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias);
+// triplet loss over B triplets (rows b, B + b, 2B + b of pre / u): loss = their unweighted mean; dE [3B][64] = loss_weight *
+// dL / d pre, dbias [64] = its column sums.  loss_weight must be finite and > 0.
+int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias, double loss_weight);
 // dX = dE . W^T, written (not added) into the rows of dX
 int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const float* W, FidRows dX);
 // dW [F][64] = X^T . dE over the M rows, stored

@@ -8,6 +8,8 @@
 // own whole kernel rows -- the same image gives the same facial ID bits in any batch.
 #include "fid.h"
 
+#include <cmath>
+
 namespace {
 
 constexpr int FWD_MT = 32;     // rows per forward workgroup
@@ -95,8 +97,9 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void fid_dense_finish_kernel(const 
 }
 
 // d pre of one row from d u: back through l2_normalize (the rsqrt factor s is a constant where sum x^2 <= 1e-12) and ReLU (TF's
-// ReluGrad: passes only where pre > 0)
-__device__ __forceinline__ float l2_relu_bwd(float y, double du) {
+// ReluGrad: passes only where pre > 0).  `weight` multiplies the fp64 result once, where it is rounded to float: a power of two
+// scales the stored value exactly.
+__device__ __forceinline__ float l2_relu_bwd(float y, double du, double weight) {
     const double r = y > 0.f ? (double)y : 0.0;
     const double ss = wave_sum(r * r);
     double dr;
@@ -106,14 +109,17 @@ __device__ __forceinline__ float l2_relu_bwd(float y, double du) {
     } else {
         dr = du * 1e6;
     }
-    return y > 0.f ? (float)dr : 0.f;
+    return y > 0.f ? (float)(dr * weight) : 0.f;
 }
 
 // Triplet loss mean_b max(|a - p| - |a - n| + 0.2, 0) (fi.py:72-76) and its gradient.  Wave w takes the triplets b = w, w + 4, ...
 // (lane = column); max passes the gradient where its argument is >= 0 (TF's MaximumGrad); the gradient of a distance that is
 // exactly 0 is defined as 0 (TF's sqrt gradient is NaN there).  Sums: per wave in b order, then the four waves in order.
+// loss_weight (a data-parallel slice's share of the merged batch) scales dE where it is stored; dbias sums the stored rows in
+// fp64, so it carries the same factor.  The loss is this call's own mean, unweighted.
 __global__ __launch_bounds__(256) void fid_triplet_kernel(const float* __restrict__ pre, const float* __restrict__ u, int B,
-                                                          float* __restrict__ loss, float* __restrict__ dE, float* __restrict__ dbias) {
+                                                          float* __restrict__ loss, float* __restrict__ dE, float* __restrict__ dbias,
+                                                          double loss_weight) {
     __shared__ double s_loss[4], s_db[4][FID_DIM];
     const int n = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double lsum = 0.0, db = 0.0;
@@ -128,7 +134,8 @@ __global__ __launch_bounds__(256) void fid_triplet_kernel(const float* __restric
             const double cp = dp > 0.0 ? 1.0 / ((double)B * dp) : 0.0, cn = dn > 0.0 ? 1.0 / ((double)B * dn) : 0.0;
             ga = cp * dap - cn * dan; gp = -cp * dap; gn = cn * dan;
         }
-        const float ea = l2_relu_bwd(pre[ra], ga), ep = l2_relu_bwd(pre[rp], gp), en = l2_relu_bwd(pre[rn], gn);
+        const float ea = l2_relu_bwd(pre[ra], ga, loss_weight), ep = l2_relu_bwd(pre[rp], gp, loss_weight),
+                    en = l2_relu_bwd(pre[rn], gn, loss_weight);
         dE[ra] = ea; dE[rp] = ep; dE[rn] = en;
         db += ((double)ea + (double)ep) + (double)en;
     }
@@ -228,10 +235,11 @@ int fv_fid_dense_finish(fv_ctx* ctx, const float* part, long long chunks, int M,
     return FV_OK;
 }
 
-int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias) {
+int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias, double loss_weight) {
     FV_REQUIRE(ctx, pre && u && loss && dE && dbias && B >= 1, "fid_triplet: bad arguments");
+    FV_REQUIRE(ctx, std::isfinite(loss_weight) && loss_weight > 0.0, "fid_triplet: loss_weight must be finite and > 0");
     FvProfScope ps(ctx, "fid_triplet_kernel", 0.0, 4.0 * 9.0 * B * FID_DIM);
-    hipLaunchKernelGGL(fid_triplet_kernel, dim3(1), dim3(256), 0, ctx->stream, pre, u, B, loss, dE, dbias);
+    hipLaunchKernelGGL(fid_triplet_kernel, dim3(1), dim3(256), 0, ctx->stream, pre, u, B, loss, dE, dbias, loss_weight);
     FV_LAUNCH_CHECK(ctx);
     return FV_OK;
 }

@@ -4,6 +4,8 @@
 #include "fid.h"
 #include "net_plan.h"
 
+#include <cmath>
+
 namespace {
 
 constexpr int NB = 52;   // base layers: conv_0 .. the add_23 block
@@ -94,8 +96,17 @@ int fv_fid_extract(fv_ctx* ctx, const float* params, const float* bn_state, cons
 
 int fv_fid_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* xa, const float* xp, const float* xn, int batch,
                       int image_size, void* workspace, size_t workspace_bytes, float* grads, float* loss) {
+    return fv_fid_train_step_dp(ctx, params, bn_state, xa, xp, xn, batch, image_size, workspace, workspace_bytes, grads, loss, 1.0,
+                                nullptr, nullptr);
+}
+
+int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, const float* xa, const float* xp, const float* xn, int batch,
+                         int image_size, void* workspace, size_t workspace_bytes, float* grads, float* loss, double loss_weight,
+                         fv_bucket_fn on_bucket, void* user) {
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, params && bn_state && xa && xp && xn && workspace && grads && loss, "fid_train_step: NULL buffer");
+    FV_REQUIRE(ctx, std::isfinite(loss_weight) && loss_weight > 0.0,
+               "fid_train_step: loss_weight must be finite and > 0 (the slice's share of the merged batch)");
     if (int rc = check_batch(ctx, "fid_train_step", batch, image_size)) return rc;
     TrainWs w = make_train(workspace, batch, image_size);
     if (w.bytes > workspace_bytes) return fv_fail(ctx, FV_ERR_WORKSPACE, "fid_train_step: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
@@ -134,15 +145,28 @@ int fv_fid_train_step(fv_ctx* ctx, const float* params, float* bn_state, const f
     const int M = 3 * batch;
     if (int rc = fv_fid_dense_fwd(ctx, X, M, F, params + dense_off, w.part)) return rc;
     if (int rc = fv_fid_dense_finish(ctx, w.part, fv_fid_chunks(F), M, params + dense_off + F * FID_DIM, w.pre, w.u)) return rc;
-    if (int rc = fv_fid_triplet(ctx, w.pre, w.u, batch, loss, w.dE, grads + dense_off + F * FID_DIM)) return rc;
+    if (int rc = fv_fid_triplet(ctx, w.pre, w.u, batch, loss, w.dE, grads + dense_off + F * FID_DIM, loss_weight)) return rc;
     if (int rc = fv_fid_dense_wgrad(ctx, X, w.dE, M, F, grads + dense_off)) return rc;
+    // The dense ranges are complete here (no tower adds to them): bias, then kernel, before any base backward starts.  They were
+    // made on the context's stream; a callback that works on the side stream (fv_set_bucket_on_side) is ordered behind them by an
+    // event first.
+    if (on_bucket) {
+        if (ctx->overlap && ctx->side && ctx->bucket_on_side) {
+            FV_HIP(ctx, hipEventRecord(ctx->ev_dz[0], ctx->stream));
+            FV_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_dz[0], 0));
+        }
+        on_bucket(user, dense_off + F * FID_DIM, FID_DIM);
+        on_bucket(user, dense_off, F * FID_DIM);
+    }
     if (int rc = fv_fid_dense_dgrad(ctx, w.dE, M, F, params + dense_off, FidRows{{w.t[0].G[0], w.t[1].G[0], w.t[2].G[0]}, batch})) return rc;
 
     // ---------------- backward of each tower into the same gradient vector: conv weight-gradients accumulate (float atomics), BN
-    // d-beta / d-gamma are added (accumulate_bn); the top layer's BN reduction is not fused into the dense data-gradient
+    // d-beta / d-gamma are added (accumulate_bn); the top layer's BN reduction is not fused into the dense data-gradient.  A base
+    // range is complete only when the LAST tower's share of it is in the queue: the third pass alone reports (both streams are in
+    // order, so that tower's weight-gradient and BN-backward of a layer lie behind the other two towers')
     for (int i = 0; i < 3; ++i) {
         const Train t{ctx, N.L, w.t[i].k, batch, image_size, params, bn_state, grads, true};
-        WgradPipe pipe(t, nullptr, nullptr, w.t[i].G[2], w.t[i].G[3]);
+        WgradPipe pipe(t, i == 2 ? on_bucket : nullptr, user, w.t[i].G[2], w.t[i].G[3]);
         if (int rc = base_backward(pipe, NB, x[i], w.t[i].G, {}, false)) return rc;
         if (int rc = pipe.finish()) return rc;
     }

@@ -5,8 +5,11 @@ Port of the reference's `src/space/face_identification.py` (fi.py): the model (f
 variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `test` (fi.py:994-1153) and `main`
 (fi.py:1715-1760) for the modes implemented here, and the data mode (`create_db_fi` / `save_extracted_face`, fi.py:78-280) that
 cuts the face crops and writes the subject db everything else reads.  The hot path is the C ABI (fv_fid_extract,
-fv_fid_train_step, fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match, fv_fid_pair_dists); this module holds the
-weights and drives it.  Not ported: evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
+fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match, fv_fid_pair_dists); this module holds the
+weights and drives it.  fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
+fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
+of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
+Not ported: evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
 moving-statistics update order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test()
 batching its frames and crops (same rows), fp64 match distances, crops whose letterboxed side rounds to 0 being skipped (the
 reference's cv.resize raises), and the data mode's walk by source file (section 16)."""
@@ -116,17 +119,21 @@ class FidModel(Model):
         return fid
 
     # ------------------------------------------------------------------ training
-    def forward_backward(self, xa, xp, xn):
-        """Triplet forward + loss + backward (fv_fid_train_step): gradients in self.grads, BN moving statistics updated a -> p -> n;
-        returns the loss as a 1-element CUDA tensor (no host sync)."""
+    def forward_backward(self, xa, xp, xn, on_bucket=None, loss_weight=1.0):
+        """Triplet forward + loss + backward (fv_fid_train_step_dp): gradients in self.grads, BN moving statistics updated
+        a -> p -> n; returns the loss as a 1-element CUDA tensor (no host sync).  on_bucket(offset, count) is called as gradient
+        ranges complete (descending offsets: the dense bias and kernel first, then the base layers from the third tower's pass),
+        the protocol of Engine.forward_backward -- parallel.DataParallelTrainer drives either.  loss_weight: this slice's share
+        n_r / N of a merged data-parallel batch: scales the gradients, not the loss."""
         self.ensure_optimizer()
         xa, xp, xn = self._as_input(xa), self._as_input(xp), self._as_input(xn)
         B = xa.shape[0]
         if xp.shape != xa.shape or xn.shape != xa.shape:
             raise ValueError('anchor, positive and negative batches differ in shape')
         ws = self._workspace(B, self.image_size, True)
-        return self._train_call('fv_fid_train_step', ptr(xa), ptr(xp), ptr(xn), B, self.image_size, ptr(ws), ws.numel(),
-                                ptr(self.grads), ptr(self._loss))
+        cb, errors = self._bucket_fn(on_bucket)
+        return self._train_call('fv_fid_train_step_dp', ptr(xa), ptr(xp), ptr(xn), B, self.image_size, ptr(ws), ws.numel(),
+                                ptr(self.grads), ptr(self._loss), float(loss_weight), cb, None, errors=errors)
 
     def train_on_batch(self, xa, xp, xn, lr, beta_1, beta_2, decay=0.0):
         loss = self.forward_backward(xa, xp, xn)
@@ -227,9 +234,16 @@ class _TripletSequence(object):
         img = _imread(os.path.join(self.raw_data_path, self.FACES_DIR, self.db.loc[label, 'face_file']))
         return img.astype(np.float32) / np.float32(255.0)
 
-    def __getitem__(self, index):
+    def rows(self, index):
+        """The triplets of batch `index` (the last batch is the short one)."""
         end = len(self.img_triplet_pairs) if index == self.hps['step'] - 1 else (index + 1) * self.batch_size
-        rows = self.img_triplet_pairs[index * self.batch_size:end]
+        return self.img_triplet_pairs[index * self.batch_size:end]
+
+    def __getitem__(self, index):
+        return self.load(self.rows(index))
+
+    def load(self, rows):
+        """The Keras batch of the triplets `rows`: only their images are read."""
         xa = np.asarray([self._image(t[0]) for t in rows])
         xp = np.asarray([self._image(t[1]) for t in rows])
         xn = np.asarray([self._image(t[2]) for t in rows])
@@ -248,6 +262,17 @@ class TrainingSequenceVGGFace2(_TripletSequence):
     DB_FILE = 'subject_image_vggface2_db.csv'
     PICKLE_FILE = 'img_triplet_pairs_vggface2.pickle'
     FACES_DIR = 'subject_faces_vggface2'
+
+
+def slice_triplets(rows, world_size, rank):
+    """This rank's part of a triplet batch, as keras.utils.multi_gpu_model cuts the three inputs (parallel.slice_batch:
+    contiguous, the remainder to the last rank) -> (rows of the slice, its weight n_r / n in the merged-batch mean), or None on
+    EVERY rank when the batch holds fewer triplets than there are ranks."""
+    from .parallel import slice_batch
+    sl = slice_batch(len(rows), world_size, rank)
+    if sl is None:
+        return None
+    return rows[sl[0]:sl[1]], sl[2]
 
 
 # ----------------------------------------------------------------------------- identification helpers (fi.py:645-770, 994-1153)
@@ -684,7 +709,10 @@ class FaceIdentifier(object):
         if int(self.nn_arch['dense1_dim']) != DENSE1_DIM:
             raise ValueError('dense1_dim must be %d: the triplet loss slices 0:64 / 64:128 / 128:192 (reference triplet_loss)'
                              % DENSE1_DIM)
-        if device is None:
+        # multi_gpu: one process per GPU (main() starts them); a FaceIdentifier made in a process without WORLD_SIZE is one rank
+        self.world = int(os.environ.get('WORLD_SIZE', 1)) if self.conf.get('multi_gpu') else 1
+        self.rank = int(os.environ.get('RANK', 0)) if self.world > 1 else 0
+        if device is None:           # FV_DEVICE: several ranks on ONE device, to rehearse N > 1 on a one-GPU box (gloo transport)
             device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
         self.model = FidModel(self.image_size, device)
         self.model.bn_zero_debias = bool(self.conf.get('bn_zero_debias', True))
@@ -708,7 +736,7 @@ class FaceIdentifier(object):
         """YOLOV3Base (fi.py:398-614), as FaceDetector._load_base: yolov3_base.h5 when yolov3_base_model_load is set, else the
         Darknet file (then yolov3_base.h5 is written, fi.py:612), else synthetic weights (announced)."""
         base = weights.load_base('FaceIdentifier', self.model.layers, self.BASE_MODEL_PATH, self.DARKNET_WEIGHTS_PATH,
-                                 self.conf.get('yolov3_base_model_load'), save_base=True)
+                                 self.conf.get('yolov3_base_model_load'), save_base=self.rank == 0)
         if base is None:
             self.model.init_synthetic(seed=7)
         else:
@@ -722,22 +750,48 @@ class FaceIdentifier(object):
 
     def train(self):
         """fi.py:616-643: fit_generator over the triplet sequence (batch order shuffled every epoch, as Keras does for a Sequence),
-        hps['epochs'] epochs of hps['step'] steps (the sequence sets hps['step'] to its batch count), then save face_identifier.h5."""
+        hps['epochs'] epochs of hps['step'] steps (the sequence sets hps['step'] to its batch count), then save face_identifier.h5.
+        With more than one rank (multi_gpu): rank 0 builds, shuffles and pickles the triplet list and the others read it; every
+        rank walks the same batch order and trains on its slice of each batch (slice_triplets) through
+        parallel.DataParallelTrainer; a batch with fewer triplets than ranks is skipped on all ranks; rank 0 prints the loss of
+        the merged batches and saves the model."""
+        from .parallel import DataParallelTrainer
         if self.conf['resource_type'] == RESOURCE_TYPE_UCCS:
-            tr_gen = self.TrainingSequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=False)
+            sequence = self.TrainingSequence
         elif self.conf['resource_type'] == RESOURCE_TYPE_VGGFACE2:
-            tr_gen = self.TrainingSequenceVGGFace2(self.raw_data_path, self.hps, self.nn_arch, load_flag=False)
+            sequence = self.TrainingSequenceVGGFace2
         else:
             raise ValueError('resource type is not valid.')
-        steps = int(self.hps['step'])
-        for e in range(int(self.hps['epochs'])):
+        trainer = DataParallelTrainer(self.model, world_size=self.world, rank=self.rank)
+        # one triplet list for all ranks: rank 0 writes the pickle, the others load it once it is complete
+        if self.rank == 0:
+            tr_gen = sequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=False)
+        trainer.barrier()
+        if self.rank != 0:
+            tr_gen = sequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=True)
+        h = self.hps
+        steps, epochs = int(h['step']), int(h['epochs'])
+        # one rank: the global numpy stream, as before; several: one seeded generator, the same batch order on every rank
+        rng = np.random.default_rng(0) if self.world > 1 else np.random
+        for e in range(epochs):
             losses = []
-            for i in np.random.permutation(len(tr_gen))[:steps]:
-                x, _ = tr_gen[int(i)]
-                losses.append(self.train_on_batch(x['input_a'], x['input_p'], x['input_n']))
-            print('Epoch %d/%d - loss: %.4f' % (e + 1, int(self.hps['epochs']), float(np.mean(losses)) if losses else float('nan')))
-        print('Save the model.')
-        self.model.save(self.MODEL_PATH)
+            for i in rng.permutation(len(tr_gen))[:steps]:
+                part = slice_triplets(tr_gen.rows(int(i)), self.world, self.rank)
+                if part is None:       # on every rank alike: a rank that stayed out of a collective would hang the others
+                    if self.rank == 0:
+                        print('batch %d - skipped (fewer triplets than ranks)' % int(i))
+                    continue
+                rows, weight = part
+                x, _ = tr_gen.load(rows)
+                loss = trainer.train_on_inputs((x['input_a'], x['input_p'], x['input_n']), h['lr'], h['beta_1'], h['beta_2'],
+                                               h.get('decay', 0.0), weight=weight)
+                losses.append(trainer.merged_loss(loss, weight))          # collective: every rank calls it
+            if self.rank == 0:
+                print('Epoch %d/%d - loss: %.4f' % (e + 1, epochs, float(np.mean(losses)) if losses else float('nan')))
+        if self.rank == 0:
+            print('Save the model.')
+            self.model.save(self.MODEL_PATH)
+        trainer.shutdown()
 
     # ------------------------------------------------------------------ facial-ID database (fi.py:645-770)
     def _extract_db(self):
@@ -845,11 +899,13 @@ def main():
       data    create_db_fi: the face crops and the subject db of fi_conf.resource_type (no model is built); a configuration
               that names neither 'uccs' nor 'vggface2' is refused like a mode that is not implemented;
       train   trains and saves face_identifier.h5, then builds the facial-ID database (make_facial_ids_db, register_facial_ids),
-              as fi.py:1734-1743 does;
+              as fi.py:1734-1743 does.  With fi_conf.multi_gpu and num_gpus > 1 this process starts num_gpus ranks of itself
+              (parallel.launch_ranks) before any GPU call and exits with their code; the ranks train data-parallel, then rank 0
+              alone builds the database (the others return after train());
       fid_db  make_facial_ids_db, then register_facial_ids -- the reference leaves the second call commented out, but nothing else
               would register the IDs of a loaded model, and test() reads the registry;
       test    test() -> output_file_path.
-    'evaluate' is not implemented here."""
+    'evaluate' is not implemented here; the other modes ignore multi_gpu."""
     name = 'face_vijnana_yolov3_win.json' if platform.system() == 'Windows' else 'face_vijnana_yolov3.json'
     with open(name, 'r') as f:
         conf = json.load(f)
@@ -865,10 +921,19 @@ def main():
         create_db_fi(conf)
         print('Elasped time: {0:f}s'.format(time.time() - ts))
         return
-    fi = FaceIdentifier(conf)
+    if mode == 'train':
+        n = int(conf['fi_conf'].get('num_gpus', 1)) if conf['fi_conf'].get('multi_gpu') else 1
+        if n > 1 and 'WORLD_SIZE' not in os.environ:
+            # multi_gpu_model(model, gpus=num_gpus) (fi.py:348-361) is one process driving num_gpus towers; here it is one process
+            # per GPU, started from this one BEFORE it makes any GPU call -- the reference's command line stays what it was
+            from .parallel import launch_ranks
+            raise SystemExit(launch_ranks(n, ['-m', 'face_vijnana_yolov3_amd.face_identification']))
+    fi =FaceIdentifier(conf)
     ts = time.time()
     if mode == 'train':
-        fi.train()
+        fi.train()                         # ends the process group
+        if conf['fi_conf'].get('multi_gpu') and int(os.environ.get('WORLD_SIZE', 1)) > 1 and int(os.environ.get('RANK', 0)) != 0:
+            return                         # the database is rank 0's job
         fi.make_facial_ids_db()
         fi.register_facial_ids()
     elif mode == 'fid_db':

@@ -20,7 +20,11 @@ merged-batch MSE is sum_r n_r/N * loss_r, so every rank hands its share n_r/N to
 `loss_weight` (fv_train_step scales dL/dy with it in the loss kernel: the gradients arrive pre-scaled,
 no pass over the 162 MB vector) and the ranks SUM; a batch with fewer images than ranks is skipped on
 ALL ranks (`slice_batch` returns None everywhere), never on some -- a rank that stayed out of a
-collective would hang the others."""
+collective would hang the others.
+
+The trainer drives any model of model.Model whose forward_backward(*inputs, on_bucket=, loss_weight=) follows that protocol:
+Engine and Yolov3 through train_on_batch(x, y, ...), FidModel (the FaceIdentifier's three-tower triplet step,
+fv_fid_train_step_dp) through train_on_inputs((xa, xp, xn), ...)."""
 import os
 import shutil
 
@@ -257,10 +261,15 @@ class DataParallelTrainer(object):
         return e0.elapsed_time(e1)
 
     def train_on_batch(self, x, y, lr, beta_1, beta_2, decay=0.0, weight=None):
-        """weight: this rank's share n_rank / n_total of the merged batch (default 1 / world)."""
+        """The detectors' step (Engine: images and targets; Yolov3: images and the three target tensors)."""
+        return self.train_on_inputs((x, y), lr, beta_1, beta_2, decay, weight)
+
+    def train_on_inputs(self, inputs, lr, beta_1, beta_2, decay=0.0, weight=None):
+        """inputs: the tensors the model's forward_backward takes, in its order ((x, y) of a detector, (xa, xp, xn) of FidModel).
+        weight: this rank's share n_rank / n_total of the merged batch (default 1 / world)."""
         eng = self.eng
         if not self.bucketed:
-            return eng.train_on_batch(x, y, lr, beta_1, beta_2, decay)
+            return eng.train_on_batch(*inputs, lr, beta_1, beta_2, decay)
         if self._auto_k is not None:
             self._auto_tick()
         self._weight = float(weight) if weight is not None else 1.0 / self.world
@@ -268,7 +277,7 @@ class DataParallelTrainer(object):
         eng.ctx.set_bucket_on_side(on_side)       # per step: several trainers may share one context
         self.reducer.reset()
         try:
-            loss = eng.forward_backward(x, y, on_bucket=self.reducer.on_range, loss_weight=self._weight)
+            loss = eng.forward_backward(*inputs, on_bucket=self.reducer.on_range, loss_weight=self._weight)
         finally:
             eng.ctx.set_bucket_on_side(False)     # a later direct forward_backward(on_bucket=...) gets stream-ordered callbacks again
         self.reducer.flush()

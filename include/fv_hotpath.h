@@ -365,7 +365,7 @@ int fv_jpeg_reconstruct_batch(fv_ctx* ctx, const int16_t* coefs, const fv_jpeg_d
  * [F][64] (Keras layout), then the bias [64] -- 51 660 576 floats at 416.  BN moving statistics: the fv_state_count() vector.
  * dense1_dim is fixed at 64: the reference's loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76). */
 int64_t fv_fid_param_count(int image_size);   /* 0 unless image_size is a positive multiple of 32 */
-/* training = 0: fv_fid_extract, != 0: fv_fid_train_step (three towers' kept tensors). */
+/* training = 0: fv_fid_extract, != 0: fv_fid_train_step / fv_fid_train_step_dp (three towers' kept tensors). */
 size_t fv_fid_workspace_bytes(int batch, int image_size, int training);
 /* Replaces fid_extractor.predict (fi.py:378-395): x [batch][S][S][3] in [0,1] -> fid [batch][64], inference-mode BN.  Runs
  * fv_forward_base (feature map kept in the workspace), then the dense layer split over F in fixed chunks whose partials are
@@ -384,10 +384,26 @@ int fv_fid_extract(fv_ctx* ctx, const float* params, const float* bn_state, cons
  *    the model's life (the host passes k = 3 * steps so far + 1); with 0 all three are the plain EMA.
  *  - a distance of exactly 0 contributes gradient 0 (TF's sqrt gradient is NaN there and would poison every weight); the hinge
  *    passes the gradient where its argument is >= 0 (TF's MaximumGrad), ReLU where the pre-activation is > 0 (ReluGrad).
- * Reproducibility as fv_train_step (float atomics in the conv weight-gradients).  No bucket callback: data-parallel FI training
- * is not provided. */
+ * Reproducibility as fv_train_step (float atomics in the conv weight-gradients).  The same call as fv_fid_train_step_dp with
+ * loss_weight 1 and no callback. */
 int fv_fid_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* xa, const float* xp, const float* xn,
                       int batch, int image_size, void* workspace, size_t workspace_bytes, float* grads, float* loss);
+/* The data-parallel form of fv_fid_train_step (the reference wraps the triplet model in keras.utils.multi_gpu_model,
+ * fi.py:303-312, 348-361): one process per GPU runs this call on its slice of the merged triplet batch.
+ * loss_weight: the slice's share n_rank / n_total, finite and > 0 (FV_ERR_INVALID otherwise, nothing is written).  It scales
+ * dL/d(pre-activation) of the 3*batch dense rows and the bias gradient inside the loss kernel, once, where the fp64 values are
+ * rounded to float (a power of two scales both exactly); every gradient downstream arrives pre-scaled and the SUM all-reduce over
+ * the ranks yields the gradient of the merged-batch mean.  `loss` stays this slice's own unweighted mean.
+ * on_bucket (may be NULL): as for fv_train_step / fv_yolov3_train_step -- ranges arrive on the host in enqueue order, with
+ * descending offsets, contiguous, covering [0, fv_fid_param_count(image_size)) exactly once; fv_set_bucket_on_side and the
+ * "overlap" option mean what they mean there.  All three towers accumulate into the same vector, so a range is reported only when
+ * the last tower's contribution to it is in the queue: the dense bias and the dense kernel right after the dense weight-gradient,
+ * before any base backward starts (made on the context's stream; with fv_set_bucket_on_side the side stream is made to wait for
+ * them first), then the base layers' ranges from the backward pass of the third tower.  `grads` is zeroed on the context's
+ * stream at the top of the call: the caller joins the previous step's collectives before that (before fv_adam_step). */
+int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, const float* xa, const float* xp, const float* xn,
+                         int batch, int image_size, void* workspace, size_t workspace_bytes, float* grads, float* loss,
+                         double loss_weight, fv_bucket_fn on_bucket, void* user);
 /* The dense head on its own (operator parity tests): x [rows][F] -> out [rows][64] = l2_normalize(relu(x . w + bias)),
  * w [F][64]; pre (may be NULL) receives x . w + bias.  F % 256 == 0; partial: fv_fid_dense_partial_floats(rows, F) floats. */
 int64_t fv_fid_dense_partial_floats(int rows, int64_t F);
