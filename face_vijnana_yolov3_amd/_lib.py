@@ -104,6 +104,13 @@ def _declare(L):
         'fv_bn_bwd_slots': (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp, i32, i32, vp, vp, vp]),
         'fv_mse_loss_grad': (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         'fv_fd_loss_grad': (i32, [vp, vp, vp, i32, i32, vp, vp]),
+        'fv_upsample_concat': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32]),
+        'fv_upsample_concat_bwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32]),
+        'fv_colsum_partial_doubles': (i64, [i64, i32]),
+        'fv_colsum': (i32, [vp, vp, i64, i32, i32, vp, vp]),
+        'fv_yolo_loss_partial_doubles': (i64, [ctypes.POINTER(i64), i32]),
+        'fv_yolo_loss_grad': (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i32, i32, i32, f64, vp, vp,
+                                    ctypes.POINTER(vp)]),
         'fv_letterbox': (i32, [vp, vp, i32, i32, i32, vp, ctypes.POINTER(ctypes.c_int32)]),
         'fv_letterbox_batch': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32, i32, vp,
                                     ctypes.POINTER(ctypes.c_int32)]),
@@ -131,6 +138,10 @@ def _declare(L):
         'fv_fid_train_step_dp': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp, f64, BUCKET_FN, vp]),
         'fv_fid_dense_partial_floats': (i64, [i32, i64]),
         'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
+        'fv_fid_towers_dense_l2': (i32, [vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
+        'fv_fid_triplet_loss_grad': (i32, [vp, vp, vp, i32, f64, vp, vp, vp]),
+        'fv_fid_towers_dense_dgrad': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i32]),
+        'fv_fid_towers_dense_wgrad': (i32, [vp, vp, vp, vp, i32, vp, i32, i64, vp]),
         'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),
         'fv_fid_pair_dists': (i32, [vp, vp, i64, ctypes.POINTER(PairBlock), i32, ctypes.POINTER(f32), i32, vp, i64, vp]),
     }

@@ -125,8 +125,10 @@ __global__ __launch_bounds__(256) void fid_triplet_kernel(const float* __restric
     double lsum = 0.0, db = 0.0;
     for (int b = wv; b < B; b += 4) {
         const long long ra = (long long)b * FID_DIM + n, rp = ra + (long long)B * FID_DIM, rn = rp + (long long)B * FID_DIM;
-        const float dap = u[ra] - u[rp], dan = u[ra] - u[rn];
-        const double dp = sqrt(wave_sum((double)dap * dap)), dn = sqrt(wave_sum((double)dan * dan));
+        // differences in fp64 (exact): an fp32 difference is off by 2^-24 of itself, and where a row's gradient nearly cancels in
+        // the projection of l2_relu_bwd that rounding came out many times larger than 2^-24 of the result
+        const double dap = (double)u[ra] - (double)u[rp], dan = (double)u[ra] - (double)u[rn];
+        const double dp = sqrt(wave_sum(dap * dap)), dn = sqrt(wave_sum(dan * dan));
         const double h = dp - dn + 0.2;
         lsum += h > 0.0 ? h : 0.0;
         double ga = 0.0, gp = 0.0, gn = 0.0;

@@ -2,7 +2,10 @@
 // gather-convolution tap lists of conv.h.
 #include "conv.h"
 #include "elementwise.h"
+#include "fid.h"
 #include "ops.h"
+
+#include <cmath>
 
 static void fwd_taps(int ksize, FvTaps& t) {
     if (ksize == 1) { t.n = 1; t.dh[0] = t.dw[0] = 0; t.wslot[0] = 0; return; }
@@ -238,6 +241,98 @@ int fv_scale(fv_ctx* ctx, float* v, int64_t n, double alpha) {
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, v && n >= 0, "scale: NULL buffer");
     return fv_ew_scale(ctx, v, n, (float)alpha);
+}
+
+// ---- the three-scale helpers and the FaceIdentifier head, one call per operator: each forwards to the launcher the training
+// steps call (elementwise.hip, fid.hip) and sizes its partial buffer with the same helper
+int fv_upsample_concat(fv_ctx* ctx, const float* src, const float* skip, float* out, int B, int Hs, int Ws, int C1, int C2) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, src && skip && out && B >= 1 && Hs >= 1 && Ws >= 1 && C1 >= 4 && C2 >= 4, "upsample_concat: NULL buffer or empty shape");
+    return fv_ew_upsample_concat(ctx, src, skip, out, B, Hs, Ws, C1, C2);
+}
+
+int fv_upsample_concat_bwd(fv_ctx* ctx, const float* g, float* g_up, float* g_skip, int B, int Hs, int Ws, int C1, int C2) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, g && g_up && g_skip && B >= 1 && Hs >= 1 && Ws >= 1 && C1 >= 4 && C2 >= 4, "upsample_concat_bwd: NULL buffer or empty shape");
+    return fv_ew_upsample_concat_bwd(ctx, g, g_up, g_skip, B, Hs, Ws, C1, C2);
+}
+
+int64_t fv_colsum_partial_doubles(int64_t rows, int C) {
+    if (rows < 1 || C < 1) return 0;
+    return (int64_t)fv_ew_colsum_chunks(rows) * C;
+}
+
+int fv_colsum(fv_ctx* ctx, const float* dy, int64_t rows, int C, int c_pad, double* partial, float* out) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, dy && partial && out && rows >= 1 && C >= 1 && c_pad >= C, "colsum: NULL buffer, rows < 1 or c_pad < C");
+    return fv_ew_colsum(ctx, dy, rows, C, c_pad, partial, out);
+}
+
+int64_t fv_yolo_loss_partial_doubles(const int64_t* cells3, int A) {
+    if (!cells3 || A < 1) return 0;
+    int64_t n = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (cells3[s] < 1) return 0;
+        n += fv_ew_yolo_loss_blocks(cells3[s] * A);
+    }
+    return n;
+}
+
+int fv_yolo_loss_grad(fv_ctx* ctx, const float* const* yp3, const float* const* yt3, const int64_t* cells3, int ncls, int A, int c_pad,
+                      double grad_weight, double* partial, float* loss, float* const* dy3) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, yp3 && yt3 && cells3 && dy3 && partial && loss && ncls >= 1 && A >= 1, "yolo_loss_grad: NULL buffer or bad ncls / A");
+    FV_REQUIRE(ctx, std::isfinite(grad_weight) && grad_weight > 0.0, "yolo_loss_grad: grad_weight must be finite and > 0");
+    long long cells[3];
+    for (int s = 0; s < 3; ++s) {
+        FV_REQUIRE(ctx, yp3[s] && yt3[s] && dy3[s] && cells3[s] >= 1, "yolo_loss_grad: scale %d: NULL buffer or no cells", s);
+        cells[s] = cells3[s];
+    }
+    int off = 0;   // the partial layout of fv_yolov3_train_step: the scales' block sums back to back
+    for (int s = 0; s < 3; ++s) {
+        if (int rc = fv_ew_yolo_loss_part(ctx, yp3[s], yt3[s], cells[s], ncls, A, c_pad, dy3[s], partial + off, grad_weight)) return rc;
+        off += fv_ew_yolo_loss_blocks(cells[s] * A);
+    }
+    return fv_ew_yolo_loss_finish(ctx, partial, cells, A, loss);
+}
+
+static int fid_rows(fv_ctx* ctx, const float* r0, const float* r1, const float* r2, int per, int M, const char* who, FidRows& out) {
+    FV_REQUIRE(ctx, per >= 1 && M >= 1 && M <= 3 * per, "%s: needs per >= 1 and 1 <= M <= 3 * per (M=%d, per=%d)", who, M, per);
+    out = FidRows{{(float*)r0, (float*)r1, (float*)r2}, per};
+    for (int t = 0; t * per < M; ++t) FV_REQUIRE(ctx, out.p[t], "%s: tower %d is NULL but M = %d reaches it", who, t, M);
+    return FV_OK;
+}
+
+int fv_fid_towers_dense_l2(fv_ctx* ctx, const float* x0, const float* x1, const float* x2, int per, int M, int64_t F, const float* w,
+                           const float* bias, float* partial, float* pre, float* out) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, w && bias && partial && out, "fid_towers_dense_l2: NULL buffer");
+    FidRows X;
+    if (int rc = fid_rows(ctx, x0, x1, x2, per, M, "fid_towers_dense_l2", X)) return rc;
+    if (int rc = fv_fid_dense_fwd(ctx, X, M, F, w, partial)) return rc;
+    return fv_fid_dense_finish(ctx, partial, fv_fid_chunks(F), M, bias, pre, out);
+}
+
+int fv_fid_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, int B, double grad_weight, float* loss, float* dE,
+                             float* dbias) {
+    if (!ctx) return FV_ERR_INVALID;
+    return fv_fid_triplet(ctx, pre, u, B, loss, dE, dbias, grad_weight);
+}
+
+int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
+                              int per) {
+    if (!ctx) return FV_ERR_INVALID;
+    FidRows dX;
+    if (int rc = fid_rows(ctx, dx0, dx1, dx2, per, M, "fid_towers_dense_dgrad", dX)) return rc;
+    return fv_fid_dense_dgrad(ctx, dE, M, F, w, dX);
+}
+
+int fv_fid_towers_dense_wgrad(fv_ctx* ctx, const float* x0, const float* x1, const float* x2, int per, const float* dE, int M,
+                              int64_t F, float* dw) {
+    if (!ctx) return FV_ERR_INVALID;
+    FidRows X;
+    if (int rc = fid_rows(ctx, x0, x1, x2, per, M, "fid_towers_dense_wgrad", X)) return rc;
+    return fv_fid_dense_wgrad(ctx, X, dE, M, F, dw);
 }
 
 }  // extern "C"

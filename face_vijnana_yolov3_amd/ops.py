@@ -176,3 +176,103 @@ def adam_step(ctx, p, g, m, v, iteration, lr, beta_1, beta_2, eps=1e-7, decay=0.
     rc = lib().fv_adam_step(ctx.handle, ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), int(iteration), float(lr), float(beta_1),
                             float(beta_2), float(eps), float(decay))
     ctx.check(rc, 'fv_adam_step')
+
+
+# ------------------------------------------------------------------ three-scale helpers / FaceIdentifier head, one call per kernel family
+# Output tensors may be passed in (`out=` ...): the parity tests pre-fill them with NaN so that an element the kernel skips shows.
+def _new(shape, like, out=None):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape), (tuple(out.shape), tuple(shape))
+    return out
+
+
+def upsample_concat(ctx, src, skip, out=None):
+    """src (B,Hs,Ws,C1), skip (B,2Hs,2Ws,C2) -> (B,2Hs,2Ws,C1+C2)."""
+    B, Hs, Ws, C1 = src.shape
+    C2 = skip.shape[3]
+    assert tuple(skip.shape[:3]) == (B, 2 * Hs, 2 * Ws)
+    out = _new((B, 2 * Hs, 2 * Ws, C1 + C2), src, out)
+    ctx.check(lib().fv_upsample_concat(ctx.handle, ptr(src), ptr(skip), ptr(out), B, Hs, Ws, C1, C2), 'fv_upsample_concat')
+    return out
+
+
+def upsample_concat_bwd(ctx, g, C1, g_up=None, g_skip=None):
+    """g (B,2Hs,2Ws,C1+C2) -> g_up (B,Hs,Ws,C1), g_skip (B,2Hs,2Ws,C2)."""
+    B, H2, W2, C = g.shape
+    g_up = _new((B, H2 // 2, W2 // 2, C1), g, g_up)
+    g_skip = _new((B, H2, W2, C - C1), g, g_skip)
+    ctx.check(lib().fv_upsample_concat_bwd(ctx.handle, ptr(g), ptr(g_up), ptr(g_skip), B, H2 // 2, W2 // 2, C1, C - C1),
+              'fv_upsample_concat_bwd')
+    return g_up, g_skip
+
+
+def colsum(ctx, dy, C, out=None):
+    """dy (rows, c_pad) -> (C,): sums of the first C columns."""
+    rows, c_pad = dy.shape
+    part = torch.full((max(1, lib().fv_colsum_partial_doubles(rows, C)),), float('nan'), dtype=torch.float64, device=dy.device)
+    out = _new((C,), dy, out)
+    ctx.check(lib().fv_colsum(ctx.handle, ptr(dy), rows, C, c_pad, ptr(part), ptr(out)), 'fv_colsum')
+    return out
+
+
+def yolo_loss_grad(ctx, yp3, yt3, ncls, c_pad, grad_weight=1.0, A=3, dy3=None):
+    """Three scales' logits / targets (cells_s, A*(5+ncls)) -> loss (1,), [dy_s (cells_s, c_pad)]."""
+    import ctypes
+    cells = [int(y.shape[0]) for y in yp3]
+    c3 = (ctypes.c_int64 * 3)(*cells)
+    n = lib().fv_yolo_loss_partial_doubles(c3, A)
+    part = torch.full((max(1, n),), float('nan'), dtype=torch.float64, device=yp3[0].device)
+    loss = torch.full((1,), float('nan'), dtype=torch.float32, device=yp3[0].device)
+    dy3 = [_new((c, c_pad), yp3[0], None if dy3 is None else dy3[s]) for s, c in enumerate(cells)]
+    arr = lambda ts: (c_void_p * 3)(*[t.data_ptr() for t in ts])
+    for t in list(yp3) + list(yt3):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    rc = lib().fv_yolo_loss_grad(ctx.handle, arr(yp3), arr(yt3), c3, ncls, A, c_pad, float(grad_weight), ptr(part), ptr(loss), arr(dy3))
+    ctx.check(rc, 'fv_yolo_loss_grad')
+    return loss, dy3
+
+
+def _towers(ts):
+    """Up to three (per, F) tower buffers -> (three pointers, per)."""
+    ts = list(ts) + [None] * (3 - len(ts))
+    return [_p(t) for t in ts], int(ts[0].shape[0])
+
+
+def fid_towers_dense_l2(ctx, towers, M, w, bias, pre=None, out=None):
+    """towers: up to three (per, F) buffers holding rows m -> towers[m // per][m % per]; -> pre, u (M, 64)."""
+    (x0, x1, x2), per = _towers(towers)
+    F = int(w.shape[0])
+    part = torch.full((max(1, lib().fv_fid_dense_partial_floats(max(M, 1), F)),), float('nan'), dtype=torch.float32, device=w.device)
+    pre = _new((M, 64), w, pre)
+    out = _new((M, 64), w, out)
+    rc = lib().fv_fid_towers_dense_l2(ctx.handle, x0, x1, x2, per, M, F, ptr(w), ptr(bias), ptr(part), ptr(pre), ptr(out))
+    ctx.check(rc, 'fv_fid_towers_dense_l2')
+    return pre, out
+
+
+def fid_triplet_loss_grad(ctx, pre, u, grad_weight=1.0, dE=None, dbias=None):
+    """pre, u (3B, 64) -> loss (1,), dE (3B, 64), dbias (64,)."""
+    B = pre.shape[0] // 3
+    loss = torch.full((1,), float('nan'), dtype=torch.float32, device=pre.device)
+    dE = _new((3 * B, 64), pre, dE)
+    dbias = _new((64,), pre, dbias)
+    rc = lib().fv_fid_triplet_loss_grad(ctx.handle, ptr(pre), ptr(u), B, float(grad_weight), ptr(loss), ptr(dE), ptr(dbias))
+    ctx.check(rc, 'fv_fid_triplet_loss_grad')
+    return loss, dE, dbias
+
+
+def fid_towers_dense_dgrad(ctx, dE, w, towers, M):
+    """dE (M, 64), w (F, 64): writes rows m of dE . w^T into towers[m // per][m % per]."""
+    (d0, d1, d2), per = _towers(towers)
+    rc = lib().fv_fid_towers_dense_dgrad(ctx.handle, ptr(dE), M, int(w.shape[0]), ptr(w), d0, d1, d2, per)
+    ctx.check(rc, 'fv_fid_towers_dense_dgrad')
+
+
+def fid_towers_dense_wgrad(ctx, towers, dE, M, F, dw=None):
+    """-> dw (F, 64) = X^T . dE over the M rows of the towers."""
+    (x0, x1, x2), per = _towers(towers)
+    dw = _new((F, 64), dE, dw)
+    rc = lib().fv_fid_towers_dense_wgrad(ctx.handle, x0, x1, x2, per, ptr(dE), M, F, ptr(dw))
+    ctx.check(rc, 'fv_fid_towers_dense_wgrad')
+    return dw

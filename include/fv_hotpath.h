@@ -293,6 +293,27 @@ int fv_bn_bwd_slots(fv_ctx* ctx, const float* g, const float* z, const float* sc
  * dbias[C] = column sums of dy (may be NULL). */
 int fv_mse_loss_grad(fv_ctx* ctx, const float* yp, const float* yt, int rows, int C, int c_pad,
                      float* loss, float* dy, float* dbias);
+/* ---- the helpers of fv_yolov3_train_step as single operators (exported so that each is checked against float64 on its own, at
+ * the production row counts the small whole-step tests never reach).  Each call forwards to the launcher the step calls and sizes
+ * its partial buffer with the step's own helper; an additive part of ABI version 4 (no existing entry point changed).
+ * UpSampling2D(2) (nearest) of src [B][Hs][Ws][C1] concatenated in front of skip [B][2Hs][2Ws][C2] (yd.py:282-283, 298-299)
+ * -> out [B][2Hs][2Ws][C1+C2]; a pure copy.  C1 % 4 == 0 and C2 % 4 == 0, FV_ERR_INVALID otherwise (nothing is written). */
+int fv_upsample_concat(fv_ctx* ctx, const float* src, const float* skip, float* out, int B, int Hs, int Ws, int C1, int C2);
+/* its backward: g [B][2Hs][2Ws][C1+C2] -> g_up [B][Hs][Ws][C1] = (p + q) + (r + t) of the 2x2 block of the first C1 channels
+ * (p, q the upper row left to right, r, t the lower; fp32, this order), g_skip [B][2Hs][2Ws][C2] = a copy of the other C2. */
+int fv_upsample_concat_bwd(fv_ctx* ctx, const float* g, float* g_up, float* g_skip, int B, int Hs, int Ws, int C1, int C2);
+/* out[C] = column sums of dy [rows][c_pad] over its first C columns (the bias gradient of a detection conv): fp64 sums in a
+ * fixed order, rounded to float once; columns >= C are never read.  partial: fv_colsum_partial_doubles(rows, C) doubles. */
+int64_t fv_colsum_partial_doubles(int64_t rows, int C);
+int fv_colsum(fv_ctx* ctx, const float* dy, int64_t rows, int C, int c_pad, double* partial, float* out);
+/* The detection loss of fv_yolov3_train_step and its gradient.  yp3 / yt3 / dy3: HOST arrays of three DEVICE pointers (scale 0
+ * first): logits and targets [cells3[s]][A][5+ncls], dy [cells3[s]][c_pad] = grad_weight * dL/d(logit), columns >= A*(5+ncls)
+ * zeroed.  loss (device float) = sum over the scales of the mean over (cell, anchor) of the per-box term stated at
+ * fv_yolov3_train_step, unweighted.  grad_weight finite and > 0, c_pad >= A*(5+ncls); partial:
+ * fv_yolo_loss_partial_doubles(cells3, A) doubles, laid out as in the step.  Deterministic (fp64 sums in a fixed order). */
+int64_t fv_yolo_loss_partial_doubles(const int64_t* cells3, int A);
+int fv_yolo_loss_grad(fv_ctx* ctx, const float* const* yp3, const float* const* yt3, const int64_t* cells3, int ncls, int A,
+                      int c_pad, double grad_weight, double* partial, float* loss, float* const* dy3);
 /* Letterbox preprocessing (SURVEY 8f "next" row 1): replaces image/255 -> cv2.resize(INTER_CUBIC)
  * -> cv2.copyMakeBorder(zeros) of fd.py:112-147 / 656-694 / 798-835.  src: uint8 [h][w][3] (device),
  * dst: float32 [S][S][3]; geom (host, may be NULL) receives w_p, h_p, pad_t, pad_b, pad_l, pad_r.
@@ -409,6 +430,26 @@ int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, cons
 int64_t fv_fid_dense_partial_floats(int rows, int64_t F);
 int fv_fid_dense_l2(fv_ctx* ctx, const float* x, int rows, int64_t F, const float* w, const float* bias, float* partial,
                     float* pre, float* out);
+/* The head kernels of fv_fid_train_step as single operators, over the rows the step builds: row m (0 <= m < M <= 3 * per) lies
+ * at tower m / per, row m % per -- three separately allocated [per][F] buffers read (written) in place; a tower that M does not
+ * reach may be NULL, one that it reaches may not (FV_ERR_INVALID, as for M > 3 * per and F % 256 != 0; nothing is written).
+ * fv_fid_towers_dense_l2: fv_fid_dense_l2 over those rows; partial: fv_fid_dense_partial_floats(M, F) floats.  A row's pre / out
+ * bits depend on that row, w and bias alone -- not on M, per or the other rows. */
+int fv_fid_towers_dense_l2(fv_ctx* ctx, const float* x0, const float* x1, const float* x2, int per, int M, int64_t F,
+                           const float* w, const float* bias, float* partial, float* pre, float* out);
+/* Triplet loss over B triplets (rows b, B + b, 2B + b of pre / u [3B][64], u = l2_normalize(relu(pre)) as the dense call returns
+ * them): loss (device float) = mean_b max(|ua - up| - |ua - un| + 0.2, 0), unweighted; dE [3B][64] = grad_weight * dL/d pre with
+ * the definitions stated at fv_fid_train_step (distance exactly 0: gradient 0; hinge passes at >= 0; ReLU at pre > 0; a row with
+ * sum relu(pre)^2 <= 1e-12 is scaled by the constant 1e6); dbias [64] = the column sums of the stored dE (fp64, fixed order).
+ * grad_weight finite and > 0. */
+int fv_fid_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, int B, double grad_weight, float* loss, float* dE,
+                             float* dbias);
+/* dX = dE . w^T ([M][64] x [F][64]^T) stored into the towers' rows; each element one fp32 chain over the 64 columns in order. */
+int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
+                              int per);
+/* dw [F][64] = X^T . dE over the M rows, stored; each element one fp32 chain over the rows in order. */
+int fv_fid_towers_dense_wgrad(fv_ctx* ctx, const float* x0, const float* x1, const float* x2, int per, const float* dE, int M,
+                              int64_t F, float* dw);
 /* Nearest registered facial ID (FaceIdentifier.test, fi.py:1117-1127: `norm(anchor - reg)` per subject, then np.argmin):
  * queries [n][64] and registry [m][64] float32 (device; registry 16-byte aligned) -> best_index int32 [n] and best_dist
  * float64 [n] (device).  Distance: sqrt of the fp64 sum, in dimension order 0..63, of the squared fp64 differences.  The
