@@ -61,6 +61,13 @@ class PairBlock(ctypes.Structure):
                 ('out_off', ctypes.c_int64), ('kind', ctypes.c_int32), ('pad', ctypes.c_int32)]
 
 
+class DrawPrim(ctypes.Structure):
+    """fv_draw_prim of include/fv_hotpath.h."""
+    _fields_ = [('kind', ctypes.c_int32), ('image', ctypes.c_int32), ('x0', ctypes.c_int32), ('y0', ctypes.c_int32),
+                ('x1', ctypes.c_int32), ('y1', ctypes.c_int32), ('width', ctypes.c_int32), ('r', ctypes.c_uint8),
+                ('g', ctypes.c_uint8), ('b', ctypes.c_uint8), ('reserved', ctypes.c_uint8), ('mask_off', ctypes.c_int64)]
+
+
 BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64)
 
 
@@ -118,6 +125,8 @@ def _declare(L):
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_crop_nearest_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
+        'fv_draw_prims_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
+                                  ctypes.POINTER(DrawPrim), i32, vp, i64]),
         'fv_yolov3_num_layers': (i32, []),
         'fv_yolov3_layer': (i32, [i32, i32, ctypes.POINTER(LayerDesc)]),
         'fv_yolov3_param_count': (i64, [i32]),

@@ -324,6 +324,7 @@ class FaceDetector(object):
             self._eval_ring = PinnedRing(3)          # kept across evaluate()/test() calls: page-locking is the expensive part
         ring = self._eval_ring
         with ThreadPoolExecutor(max_workers=threads) as pool, ThreadPoolExecutor(max_workers=1) as one:
+            self._pool = pool      # FaceIdentifier.evaluate writes its annotated frames on it, between two items of this generator
             def load(chunk):
                 if use_jpeg:       # test() never looks at the pixels on the host: Huffman-decode only, the rest on the device
                     import torch

@@ -2,17 +2,20 @@
 
 Port of the reference's `src/space/face_identification.py` (fi.py): the model (fi.py:318-345), the facial-ID extractor
 (`_make_fid_extractor`, fi.py:378-395), `train` (fi.py:616-643) over its two triplet sequences (fi.py:1490-1601 and the VGGFace2
-variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `test` (fi.py:994-1153) and `main`
-(fi.py:1715-1760) for the modes implemented here, and the data mode (`create_db_fi` / `save_extracted_face`, fi.py:78-280) that
-cuts the face crops and writes the subject db everything else reads.  The hot path is the C ABI (fv_fid_extract,
-fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match, fv_fid_pair_dists); this module holds the
+variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `evaluate` (fi.py:772-992), `test`
+(fi.py:994-1153) and `main` (fi.py:1715-1760) for the modes it dispatches, and the data mode (`create_db_fi` /
+`save_extracted_face`, fi.py:78-280) that cuts the face crops and writes the subject db everything else reads.  The hot path is
+the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match,
+fv_fid_pair_dists, fv_draw_prims_u8); this module holds the
 weights and drives it.  fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
-Not ported: evaluate and the reconstruction model.  Differences, documented in DESIGN.md: the BN
-moving-statistics update order of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test()
-batching its frames and crops (same rows), fp64 match distances, crops whose letterboxed side rounds to 0 being skipped (the
-reference's cv.resize raises), and the data mode's walk by source file (section 16)."""
+Not ported: the reconstruction model (dead code in the reference).  evaluate() is a method only: main() does not dispatch
+fi_conf.mode 'evaluate' yet.  Differences, documented in DESIGN.md: the BN moving-statistics update order
+of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test() and evaluate() batching their
+frames and crops (same rows), fp64 match distances, crops whose letterboxed side rounds to 0 being skipped (the reference's
+cv.resize raises), the data mode's walk by source file (section 16), and evaluate() drawing its annotated frames on the device
+with two documented departures from Pillow's rectangle (section 17)."""
 import collections
 import csv
 import ctypes
@@ -31,6 +34,7 @@ import torch
 
 from . import weights
 from ._lib import Context, FvError, lib, ptr
+from .annotate import MaskBlend, Outline, _font, annotation_prims, pack_masks      # noqa: F401 (part of this module's surface)
 from .model import Model
 from .weights import NUM_BASE_LAYERS
 
@@ -323,24 +327,30 @@ def crop_rects(boxes, h, w, image_size):
     return out
 
 
+def matched_boxes(rects, best_dist, sim_th, limit=MAX_ROWS_PER_IMAGE):
+    """Indices of the boxes of one image that test() / evaluate() write a row for (fi.py:1057-1148, 864-941): boxes in detector
+    order, those without a crop skipped, a match farther than sim_th skipped, at most `limit` rows."""
+    out = []
+    for k, rect in enumerate(rects):
+        if len(out) >= limit:
+            break
+        if rect is None or best_dist[k] > sim_th:
+            continue
+        out.append(k)
+    return out
+
+
 def identification_rows(file_name, boxes, rects, best_index, best_dist, subject_ids, sim_th, limit=MAX_ROWS_PER_IMAGE):
     """The rows test() writes for one image (fi.py:1057-1148): boxes in detector order, those without a crop skipped, a match
     farther than sim_th skipped, at most `limit` rows written.  best_index / best_dist: per box (read only where a row can still be
     written).  -> csv text, `str()` of each value exactly as fi.py:1143-1148."""
     base = file_name.split('\\')[-1] if platform.system() == 'Windows' else file_name.split('/')[-1]
     out = []
-    count = 1
-    for k, box in enumerate(boxes):
-        if count > limit:
-            break
-        if rects[k] is None:
-            continue
-        if best_dist[k] > sim_th:
-            continue
+    for k in matched_boxes(rects, best_dist, sim_th, limit):
+        box = boxes[k]
         subject_id = subject_ids[int(best_index[k])]
         out.append(base + ',' + str(subject_id) + ',' + str(box.xmin) + ',' + str(box.ymin) + ',')
         out.append(str(box.xmax - box.xmin) + ',' + str(box.ymax - box.ymin) + ',' + str(box.get_score()) + '\n')
-        count += 1
     return ''.join(out)
 
 
@@ -462,6 +472,54 @@ def crop_nearest_u8(ctx, images, crops, image_size, out=None):
                                   (ctypes.c_int32 * max(1, 5 * n))(*flat), n, S, ptr(out))
     ctx.check(rc, 'fv_crop_nearest_u8')
     return out
+
+
+def draw_prims_u8(ctx, images, prims, masks):
+    """fv_draw_prims_u8: draw the annotate.Outline / annotate.MaskBlend records `prims`, in order, onto images = (device uint8
+    buffer, offsets, hw) of a batch, in place (stream-ordered).  masks: uint8 CUDA tensor the MaskBlend offsets point into
+    (annotate.pack_masks), or None when there is no MaskBlend.  A bad record raises FvError and nothing is drawn."""
+    from ._lib import DrawPrim
+    dbuf, offs, hw = images
+    n, ni = len(prims), len(offs)
+    if n == 0:
+        return
+    if dbuf.dtype != torch.uint8 or not dbuf.is_cuda or (masks is not None and (masks.dtype != torch.uint8 or not masks.is_cuda)):
+        raise ValueError('draw_prims_u8 expects uint8 CUDA tensors')
+    for i in range(ni):
+        if offs[i] < 0 or offs[i] + max(0, hw[2 * i]) * max(0, hw[2 * i + 1]) * 3 > dbuf.numel():
+            raise ValueError('draw_prims_u8: image %d lies outside the buffer' % i)
+    table = (DrawPrim * n)()
+    for k, p in enumerate(prims):
+        if isinstance(p, Outline):
+            v = (0, p.image, p.x0, p.y0, p.x1, p.y1, p.width) + tuple(p.color) + (0, 0)
+        else:
+            v = (1, p.image, p.x, p.y, p.mw, p.mh, 0) + tuple(p.color) + (0, p.mask_off)
+        v = tuple(int(a) for a in v)
+        if not all(-2 ** 31 <= a < 2 ** 31 for a in v[:7]) or not all(0 <= c <= 255 for c in v[7:10]):
+            raise ValueError('draw_prims_u8: primitive %d out of range: %r' % (k, p))
+        table[k] = DrawPrim(*v)
+    rc = lib().fv_draw_prims_u8(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni, table, n,
+                                None if masks is None else ptr(masks), 0 if masks is None else masks.numel())
+    ctx.check(rc, 'fv_draw_prims_u8')
+
+
+def ground_truth_boxes(df):
+    """The ground-truth boxes evaluate() draws for one frame's rows of validation.csv (fi.py:956-969), filtered as
+    FaceDetector.evaluate filters them: a row counts only when FACE_X, FACE_Y, FACE_WIDTH and FACE_HEIGHT are all > 0; the box is
+    int(x), int(y), int(x + w - 1), int(y + h - 1) and carries the row's SUBJECT_ID."""
+    from .postproc import BoundBox
+    out = []
+    for i in range(df.shape[0]):
+        x, y, w, h = df.iloc[i, 3:7].values.astype(np.float64)
+        if not (x > 0 and y > 0 and w > 0 and h > 0):
+            continue
+        out.append(BoundBox(int(x), int(y), int(x + w - 1), int(y + h - 1), objness=1., classes=[1.0], subject_id=df.iloc[i, 2]))
+    return out
+
+
+def save_frame(pixels, path):
+    from PIL import Image
+    Image.fromarray(pixels).save(path)
 
 
 # ----------------------------------------------------------------------------- data mode (fi.py:78-280)
@@ -838,18 +896,18 @@ class FaceIdentifier(object):
         with open(db_files(self.conf['resource_type'])[3], 'wb') as f:
             pickle.dump(db, f)
 
-    # ------------------------------------------------------------------ test (fi.py:994-1153)
-    def test(self):
-        """Detect faces in every <test_path>/*.jpg (sorted), identify each against ref_facial_id_db.pickle and write
-        `name,subject_id,xmin,ymin,w,h,score` rows to output_file_path.  The detector's pipelined loop (FaceDetector._detect_files)
-        runs the frames in batches; per batch the face crops are cut and letterboxed on the device from the batch's decoded images
-        (fv_letterbox_crops), extracted in chunks of at most Engine.max_infer_batch(S) (fv_fid_extract) and matched against the
-        registry in one launch (fv_fid_match).  Rows, order and text as the reference's per-crop loop."""
+    # ------------------------------------------------------------------ evaluate / test (fi.py:772-992, 994-1153)
+    def _identify_files(self, on_batch):
+        """The loop test() and evaluate() share.  Detect faces in every <test_path>/*.jpg (sorted) through the detector's
+        pipelined loop (FaceDetector._detect_files), which runs the frames in batches; per batch the face crops are cut and
+        letterboxed on the device from the batch's decoded images (fv_letterbox_crops), extracted in chunks of at most
+        Engine.max_infer_batch(S) (fv_fid_extract) and matched against ref_facial_id_db.pickle in one launch (fv_fid_match);
+        the `name,subject_id,xmin,ymin,w,h,score` rows go to output_file_path -- rows, order and text as the reference's
+        per-crop loop -- and every box that got a row has its subject_id set (fi.py:928-929; the others keep -1).
+        on_batch(group, images), if given, is then called with the batch's items (file name, None, boxes, (images, index)) and
+        its decoded images (device uint8 buffer, offsets, hw), while the detector's generator is suspended -- its thread pool
+        (self.fd._pool) is alive.  The caller has checked the image sizes."""
         from .engine import Engine
-        fd_size = int(self._full_conf['fd_conf']['nn_arch']['image_size'])
-        if fd_size != self.image_size:
-            raise ValueError('fd_conf.nn_arch.image_size (%d) must equal fi_conf.nn_arch.image_size (%d): the reference letterboxes '
-                             'the frames with the identifier\'s size for the detector' % (fd_size, self.image_size))
         test_path = self.conf['test_path']
         out_path = self.conf['output_file_path']
         with open('ref_facial_id_db.pickle', 'rb') as f:
@@ -883,6 +941,10 @@ class FaceIdentifier(object):
                     if r is not None:
                         idx[j], dist[j] = bi[k], bd[k]; k += 1
                 f.write(identification_rows(it[0], it[2], rs, idx, dist, subject_ids, sim_th))
+                for j in matched_boxes(rs, dist, sim_th):
+                    it[2][j].subject_id = subject_ids[int(idx[j])]
+            if on_batch is not None:
+                on_batch(group, images)
 
         with open(out_path, 'w') as f:
             group = []
@@ -890,8 +952,79 @@ class FaceIdentifier(object):
                 if group and group[0][3][0] is not item[3][0]:
                     flush(group, f); group = []
                 group.append(item)
-            if group:
-                flush(group, f)
+                if item[0] == files[-1]:       # the last batch is flushed before the generator ends and takes its pool with it
+                    flush(group, f); group = []
+
+    def _check_fd_size(self):
+        fd_size = int(self._full_conf['fd_conf']['nn_arch']['image_size'])
+        if fd_size != self.image_size:
+            raise ValueError('fd_conf.nn_arch.image_size (%d) must equal fi_conf.nn_arch.image_size (%d): the reference letterboxes '
+                             'the frames with the identifier\'s size for the detector' % (fd_size, self.image_size))
+
+    def test(self):
+        """Detect faces in every <test_path>/*.jpg (sorted), identify each against ref_facial_id_db.pickle and write
+        `name,subject_id,xmin,ymin,w,h,score` rows to output_file_path (_identify_files)."""
+        self._check_fd_size()
+        self._identify_files(None)
+
+    def evaluate(self):
+        """fi.py:772-992: test()'s solution csv (the same rows, byte for byte), and under <test_path>/results_fi/ (emptied first)
+        an annotated copy `<name>_detected.jpg` of every frame that has rows in <test_path>/validation.csv of which at least one
+        survives ground_truth_boxes' filter, and at least one detection: ground truth in red, then the detections in green, each
+        box labelled `score, class score, subject id` (draw_boxes_v3; -1 where no row was written for the box).
+        The frames are not decoded a second time: per batch, once the crops are cut and extracted, ONE fv_draw_prims_u8 call
+        draws every frame's boxes into the batch's decoded images on the device (annotate.annotation_prims), one device-to-host
+        copy brings the drawn frames into a pinned slot, and the detector's thread pool encodes and writes them with Pillow
+        while the next batch runs.  Single process: multi_gpu is ignored, as in test().
+        main() does not dispatch fi_conf.mode 'evaluate' yet: call this method."""
+        import pandas as pd
+        from concurrent.futures import wait
+        from .postproc import PinnedRing
+        self._check_fd_size()
+        res_dir = os.path.join(self.conf['test_path'], 'results_fi')
+        if os.path.isdir(res_dir):
+            shutil.rmtree(res_dir)
+        os.mkdir(res_dir)
+        gt_df = pd.read_csv(os.path.join(self.conf['test_path'], 'validation.csv'))
+        groups = {k: v for k, v in gt_df.groupby('FILE')}
+        font = _font()
+        m = self.model
+        ring = PinnedRing(2)
+        saves = [[], []]                           # per pinned slot: the writes still reading it
+        state = {'takes': 0, 'all': []}
+
+        def annotate(group, images):
+            dbuf, offs, hw = images
+            prims, frames = [], []
+            for name, _raw, boxes, (_imgs, i) in group:
+                base = name.split('\\')[-1] if platform.system() == 'Windows' else name.split('/')[-1]
+                df = groups.get(base)
+                gt_boxes = ground_truth_boxes(df) if df is not None else []
+                if len(gt_boxes) == 0 or len(boxes) == 0:
+                    continue
+                prims += annotation_prims(i, gt_boxes, (255, 0, 0), font) + annotation_prims(i, boxes, (0, 255, 0), font)
+                frames.append((i, os.path.join(res_dir, base[:-4] + '_detected' + base[-4:])))
+            if not frames:
+                return
+            prims, masks = pack_masks(prims)
+            draw_prims_u8(m.ctx, images, prims, torch.from_numpy(masks).to(dbuf.device) if masks.size else None)
+            lo = min(offs[i] for i, _ in frames)
+            hi = max(offs[i] + hw[2 * i] * hw[2 * i + 1] * 3 for i, _ in frames)
+            slot = state['takes'] % 2
+            state['takes'] += 1
+            wait(saves[slot])                      # the writes of two copies ago have let go of the slot
+            host = ring.take(hi - lo)
+            host.copy_(dbuf[lo:hi], non_blocking=True)
+            torch.cuda.current_stream(dbuf.device).synchronize()
+            view = host.numpy()
+            saves[slot] = [self.fd._pool.submit(save_frame, view[offs[i] - lo:offs[i] - lo + hw[2 * i] * hw[2 * i + 1] * 3]
+                                                .reshape(hw[2 * i], hw[2 * i + 1], 3), path) for i, path in frames]
+            state['all'] += saves[slot]
+
+        self._identify_files(annotate)
+        wait(state['all'])
+        for w in state['all']:
+            w.result()
 
 
 def main():

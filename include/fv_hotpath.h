@@ -346,6 +346,32 @@ int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offset
  * side that rounds to 0 is FV_ERR_INVALID and nothing is enqueued. */
 int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
                        const int32_t* crops, int n, int image_size, uint8_t* dst);
+/* Draw onto the packed uint8 RGB images of a batch, in place (FaceIdentifier.evaluate, fi.py:945-992: the rectangles and labels
+ * of draw_boxes_v3, yolov3_detect.py:515-530).  packed / offsets / hw: the batch's n_img decoded images as for
+ * fv_letterbox_batch.  prims: HOST array of n primitives, applied in order; masks: DEVICE buffer of mask_bytes 8-bit masks.
+ *   FV_DRAW_OUTLINE  corners x0, y0, x1, y1 (inclusive) and a width: every pixel with x0 <= x <= x1, y0 <= y <= y1 and
+ *                    (x - x0 < width or x1 - x < width or y - y0 < width or y1 - y < width) becomes (r, g, b).  Corners may lie
+ *                    outside the image on any side, or be out of order (nothing is drawn then).
+ *   FV_DRAW_MASK     top-left x0, y0 (may be negative), mask size x1 = mw, y1 = mh, the mask row-major with mw bytes per row at
+ *                    masks + mask_off.  For every mask pixel inside the image and each channel, with m the mask byte:
+ *                    t = old * (255 - m) + ink * m + 128; new = ((t >> 8) + t) >> 8 (Pillow's BLEND8, what ImageDraw.text does
+ *                    with the rasterised text).  `width` is ignored.
+ * The result equals applying the primitives one after another: where two overlap, the later one sees the earlier one's output.
+ * Every primitive is clipped to its image; images and pixels no primitive touches keep their bytes.  Stream-ordered; no device
+ * allocation and no synchronisation inside the call; the table travels in the kernel arguments, 32 primitives per launch, in
+ * order.  Any number of primitives; n == 0 does nothing.  FV_ERR_INVALID, with nothing enqueued, for: an image index outside
+ * [0, n_img), an outline width < 1, a negative mask size, a mask that does not lie inside [0, mask_bytes), an unknown kind, an
+ * image with fewer than 1 row or column or more than 524 280 rows. */
+enum { FV_DRAW_OUTLINE = 0, FV_DRAW_MASK = 1 };
+typedef struct fv_draw_prim {
+    int32_t kind, image;
+    int32_t x0, y0, x1, y1;
+    int32_t width;
+    uint8_t r, g, b, reserved;
+    int64_t mask_off;
+} fv_draw_prim;
+int fv_draw_prims_u8(fv_ctx* ctx, uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                     const fv_draw_prim* prims, int n, const uint8_t* masks, int64_t mask_bytes);
 
 /* ------------------------------------------------------------------ JPEG decode, split host / device
  * (replaces `imread` of fd.py:112, 656, 798 for baseline / extended-sequential Huffman JPEGs with 1 or 3
