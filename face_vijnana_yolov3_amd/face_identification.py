@@ -665,11 +665,30 @@ def write_crop(pixels, path):
     Image.fromarray(pixels).save(path)
 
 
+def write_bytes(data, path):
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+# device_encode where a configuration does not say: on -- the files are the same bytes, and DESIGN.md section 18 gives the
+# measurements behind the choice
+DEVICE_ENCODE_DEFAULT = True
+
+
+def encode_on_device(device_encode, h, w):
+    """Whether an h x w image of a batch is encoded by jpeg.encode_batch: only when the caller asked for it, and only sizes a
+    JPEG's 16-bit fields hold (an image taller or wider than 65535 pixels goes to Pillow, whose error is then the user's)."""
+    from . import jpeg
+    return bool(device_encode) and jpeg.can_encode(h, w)
+
+
 def cut_and_write(ctx, records, image_size, out_dir, threads, hw_of=image_hw, device_jpeg=True, batch_bytes=DATA_BATCH_BYTES,
-                  batch_crops=DATA_BATCH_CROPS):
+                  batch_crops=DATA_BATCH_CROPS, device_encode=DEVICE_ENCODE_DEFAULT):
     """Cut every record's crop and write it to out_dir/<name>.  Per batch of source files: decode (load_batch on a loader thread,
     stage_batch), ONE fv_crop_nearest_u8 call for all its crops, the S x S x 3 uint8 crops copied to a pinned buffer, then
-    encoded and written by Pillow on the thread pool while the next batch decodes."""
+    encoded and written by Pillow on the thread pool while the next batch decodes.  device_encode: the crops are encoded where
+    they lie (jpeg.encode_batch), only the files' bytes -- the same bytes -- cross into the pinned slot, and the pool just writes
+    them."""
     from concurrent.futures import ThreadPoolExecutor, wait
     from .postproc import PinnedRing
     S = int(image_size)
@@ -692,6 +711,18 @@ def cut_and_write(ctx, records, image_size, out_dir, threads, hw_of=image_hw, de
             cut = crop_nearest_u8(ctx, images, crops, S)
             slot = outs[k % 2]
             wait(slot[1])                         # the writes of batch k - 2 have let go of the slot
+            if encode_on_device(device_encode, S, S):
+                from . import jpeg
+
+                def pinned(nbytes, slot=slot):
+                    if slot[0] is None or slot[0].numel() < nbytes:
+                        slot[0] = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8).pin_memory()
+                    return slot[0]
+                files = jpeg.encode_batch(ctx, cut.view(-1), [j * S * S * 3 for j in range(len(crops))], [S, S] * len(crops), dev,
+                                          pinned=pinned)
+                slot[1] = [pool.submit(write_bytes, files[j], os.path.join(out_dir, records[i].name)) for j, i in enumerate(idx)]
+                writes += slot[1]
+                continue
             if slot[0] is None or slot[0].shape[0] < len(crops):
                 slot[0] = torch.empty((max(len(crops), min(batch_crops, len(records))), S, S, 3), dtype=torch.uint8).pin_memory()
             host = slot[0][:len(crops)]
@@ -735,7 +766,7 @@ def create_db_fi(conf, device=None):
     from .face_detection import default_loader_threads
     hps = conf.get('hps', {})
     cut_and_write(ctx, records, S, out_dir, max(1, int(hps.get('loader_threads', default_loader_threads()))), hw_of,
-                  bool(hps.get('device_jpeg', True)))
+                  bool(hps.get('device_jpeg', True)), device_encode=bool(hps.get('device_encode', DEVICE_ENCODE_DEFAULT)))
     with open(db_file, 'w') as f:
         f.write(db_csv_text(records))
     print('Saved %d face images to %s; skipped %d empty crops and %d whose letterboxed side rounds to 0.'
@@ -967,7 +998,7 @@ class FaceIdentifier(object):
         self._check_fd_size()
         self._identify_files(None)
 
-    def evaluate(self):
+    def evaluate(self, device_encode=None):
         """fi.py:772-992: test()'s solution csv (the same rows, byte for byte), and under <test_path>/results_fi/ (emptied first)
         an annotated copy `<name>_detected.jpg` of every frame that has rows in <test_path>/validation.csv of which at least one
         survives ground_truth_boxes' filter, and at least one detection: ground truth in red, then the detections in green, each
@@ -975,12 +1006,17 @@ class FaceIdentifier(object):
         The frames are not decoded a second time: per batch, once the crops are cut and extracted, ONE fv_draw_prims_u8 call
         draws every frame's boxes into the batch's decoded images on the device (annotate.annotation_prims), one device-to-host
         copy brings the drawn frames into a pinned slot, and the detector's thread pool encodes and writes them with Pillow
-        while the next batch runs.  Single process: multi_gpu is ignored, as in test().
+        while the next batch runs.  device_encode (None: hps['device_encode'], on where that is absent): the drawn frames are
+        encoded on the device (jpeg.encode_batch: the same bytes Pillow writes), only the files cross to the host and the pool
+        just writes them; a frame taller or wider than 65535 pixels still takes the Pillow path.
+        Single process: multi_gpu is ignored, as in test().
         main() does not dispatch fi_conf.mode 'evaluate' yet: call this method."""
         import pandas as pd
         from concurrent.futures import wait
         from .postproc import PinnedRing
         self._check_fd_size()
+        if device_encode is None:
+            device_encode = bool(self.hps.get('device_encode', DEVICE_ENCODE_DEFAULT))
         res_dir = os.path.join(self.conf['test_path'], 'results_fi')
         if os.path.isdir(res_dir):
             shutil.rmtree(res_dir)
@@ -1008,6 +1044,19 @@ class FaceIdentifier(object):
                 return
             prims, masks = pack_masks(prims)
             draw_prims_u8(m.ctx, images, prims, torch.from_numpy(masks).to(dbuf.device) if masks.size else None)
+            on_dev = [f for f in frames if encode_on_device(device_encode, hw[2 * f[0]], hw[2 * f[0] + 1])]
+            if on_dev:
+                from . import jpeg
+                slot = state['takes'] % 2
+                state['takes'] += 1
+                wait(saves[slot])
+                files = jpeg.encode_batch(m.ctx, dbuf, [offs[i] for i, _ in on_dev],
+                                          [v for i, _ in on_dev for v in hw[2 * i:2 * i + 2]], dbuf.device, pinned=ring.take)
+                saves[slot] = [self.fd._pool.submit(write_bytes, data, path) for data, (_, path) in zip(files, on_dev)]
+                state['all'] += saves[slot]
+                frames = [f for f in frames if f not in on_dev]
+                if not frames:
+                    return
             lo = min(offs[i] for i, _ in frames)
             hi = max(offs[i] + hw[2 * i] * hw[2 * i + 1] * 3 for i, _ in frames)
             slot = state['takes'] % 2

@@ -403,6 +403,34 @@ int64_t fv_jpeg_plane_bytes(const fv_jpeg_info* info);
 int fv_jpeg_reconstruct_batch(fv_ctx* ctx, const int16_t* coefs, const fv_jpeg_desc* descs, int n, uint8_t* planes, uint8_t* rgb,
                               int64_t max_blocks, int64_t max_pixels);
 
+/* ------------------------------------------------------------------ JPEG encode, on the device (csrc/jpeg_enc.hip)
+ * The entropy-coded scan of what `PIL.Image.fromarray(rgb).save(path)` writes with libjpeg-turbo -- 8-bit RGB, quality 75, 4:2:0,
+ * the Annex K Huffman tables, no restart markers; nothing else is offered -- byte for byte, for a batch of n images of any sizes
+ * in one pair of calls.  packed / offsets / hw: the images as for fv_letterbox_batch (packed: device, packed_bytes long; offsets,
+ * hw: HOST arrays; any order, gaps allowed).  The caller puts the header (SOI .. SOS, which depends on the size alone) in front
+ * and EOI behind.  An additive part of ABI version 4.
+ *   fv_jpeg_encode_workspace_bytes  bytes of workspace the batch needs (device, 16-byte aligned), -1 for a size outside
+ *       1 <= rows, columns <= 65535.  Sized for the longest block the tables admit (1658 bits), so it holds whatever the pixels.
+ *   fv_jpeg_encode_coefs    the front end alone: colour conversion, edge replication, 2x2 chroma downsampling, forward DCT
+ *       (jpeg_fdct_islow), quantisation.  Leaves int16 coefficients in the workspace at byte *coef_offset_bytes: [64] per block in
+ *       ZIGZAG order, the blocks in scan order (MCU after MCU, Y00 Y01 Y10 Y11 Cb Cr), image after image.  Luma blocks beyond
+ *       ceil(w/8) x ceil(h/8) are libjpeg's dummy blocks (AC 0, DC of the block before them in the MCU).
+ *   fv_jpeg_encode_measure  call 1: the front end, the Huffman bit lengths, their prefix sum, the bits packed, the FF bytes
+ *       counted.  counts (DEVICE int64 [n]) receives every scan's length in bytes, stuffing and the 1-bit pad included.
+ *   fv_jpeg_encode_emit     call 2, on the same stream, workspace, hw and n: counts is the HOST copy of what call 1 left; the
+ *       scans are written back to back in image order, scan i at out + counts[0] + .. + counts[i-1].  out_bytes >= their sum; not a
+ *       byte of out beyond that sum is written.
+ * Stream-ordered; no allocation and no synchronisation inside (the caller waits once, to read counts).  n == 0 does nothing.
+ * Every argument is checked before anything is enqueued: a size outside 1..65535, an image that does not lie inside
+ * [0, packed_bytes), a workspace or output too small, a count below 1 is FV_ERR_INVALID with workspace and outputs untouched. */
+int64_t fv_jpeg_encode_workspace_bytes(const int32_t* hw, int n);
+int fv_jpeg_encode_coefs(fv_ctx* ctx, const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets, const int32_t* hw, int n,
+                         void* workspace, size_t workspace_bytes, int64_t* coef_offset_bytes);
+int fv_jpeg_encode_measure(fv_ctx* ctx, const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets, const int32_t* hw, int n,
+                           void* workspace, size_t workspace_bytes, int64_t* counts);
+int fv_jpeg_encode_emit(fv_ctx* ctx, const int32_t* hw, int n, void* workspace, size_t workspace_bytes, const int64_t* counts,
+                        uint8_t* out, int64_t out_bytes);
+
 /* ------------------------------------------------------------------ FaceIdentifier (facial IDs, triplet loss)
  * The reference's second model (face_identification.py = fi.py): FaceIdentifier (fi.py:288-376) runs ONE shared Darknet-53 base
  * (the 52 BN layers of fv_layer(0..51), weights as FaceDetector.YOLOV3Base) over three inputs, then Flatten (NHWC row-major,

@@ -3,7 +3,8 @@ faces each) and like VGGFace2 (small images, one face each), image_size 416.
 
 For each tree, one batch at a time and every stage on its own (a synchronise between stages, so nothing overlaps): Huffman decode
 on the host threads, host-to-device copy + fv_jpeg_reconstruct_batch, the fv_crop_nearest_u8 call, the device-to-host copy of the
-crops, Pillow encode + write.  Then the whole mode as a user runs it (create_db_fi, stages overlapped) in crops/s, alternating with
+crops, Pillow encode + write -- and, next to those two, the device encode of the same crops (jpeg.encode_batch: both calls, the copy
+of the byte counts and the device-to-host copy of the files, between device events) and the write of its files.  Then the whole mode as a user runs it (create_db_fi, stages overlapped) in crops/s, with hps.device_encode off and on, alternating with each other and with
 the reference's way on the host -- one Pillow decode of the whole image per csv row, a numpy nearest-neighbour gather, one Pillow
 save, single-threaded as the reference's UCCS loop is -- run on the first --host-rows rows and extrapolated to the tree when the
 tree has more (the JSON says which: host_rows_run < crops means extrapolated).  The crop kernel is also timed alone (device events,
@@ -29,6 +30,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from face_vijnana_yolov3_amd import face_identification as fi  # noqa: E402
+from face_vijnana_yolov3_amd import jpeg  # noqa: E402
 from face_vijnana_yolov3_amd._lib import Context  # noqa: E402
 from face_vijnana_yolov3_amd.data import letterbox_geometry  # noqa: E402
 from face_vijnana_yolov3_amd.face_detection import default_loader_threads  # noqa: E402
@@ -71,9 +73,9 @@ def vgg_tree(root, images, rng):
     open(os.path.join(root, 'loose_bb_train.csv'), 'w').write('\n'.join(rows) + '\n')
 
 
-def conf_of(root, resource_type):
+def conf_of(root, resource_type, device_encode=False):
     return {'fi_conf': dict(mode='data', resource_type=resource_type, raw_data_path=root, nn_arch=dict(image_size=S, dense1_dim=64),
-                            hps={})}
+                            hps={'device_encode': device_encode})}
 
 
 def device_ms(fn):
@@ -107,8 +109,8 @@ def stages(ctx, records, out_dir, threads, bw, iters):
     host = torch.empty((fi.DATA_BATCH_CROPS, S, S, 3), dtype=torch.uint8).pin_memory()
     with ThreadPoolExecutor(max_workers=threads) as pool:
         for timed in (False, True):              # the first pass page-locks the ring, loads code objects and warms the page cache
-            t = dict(huffman=0.0, h2d_reconstruct=0.0, crop=0.0, d2h=0.0, encode_write=0.0)
-            kernel_ms = floor_bytes = 0.0
+            t = dict(huffman=0.0, h2d_reconstruct=0.0, crop=0.0, d2h=0.0, encode_write=0.0, device_encode=0.0, write_files=0.0)
+            kernel_ms = floor_bytes = file_bytes = 0.0
             for batch in fi.source_batches(records, hw_of):
                 t0 = time.perf_counter()
                 loaded = fi.load_batch([s for s, _ in batch], pool, ring)
@@ -134,8 +136,15 @@ def stages(ctx, records, out_dir, threads, bw, iters):
                 t0 = time.perf_counter()
                 list(pool.map(lambda ji: fi.write_crop(pixels[ji[0]], os.path.join(out_dir, records[ji[1]].name)), enumerate(idx)))
                 t['encode_write'] += time.perf_counter() - t0
+                files, ms = device_ms(lambda: jpeg.encode_batch(ctx, cut.view(-1), [j * S * S * 3 for j in range(len(crops))],
+                                                                [S, S] * len(crops), dev))
+                t['device_encode'] += ms * 1e-3
+                file_bytes += sum(len(f) for f in files)
+                t0 = time.perf_counter()
+                list(pool.map(lambda ji: fi.write_bytes(files[ji[0]], os.path.join(out_dir, records[ji[1]].name)), enumerate(idx)))
+                t['write_files'] += time.perf_counter() - t0
     res = {'stage_%s_s' % k: v for k, v in t.items()}
-    res.update(crop_kernel_ms=kernel_ms, crop_kernel_floor_ms=floor_bytes / bw * 1e3)
+    res.update(crop_kernel_ms=kernel_ms, crop_kernel_floor_ms=floor_bytes / bw * 1e3, file_bytes=file_bytes)
     return res
 
 
@@ -169,15 +178,20 @@ def run_tree(tag, root, resource_type, ctx, bw, a):
     try:
         fi.create_db_fi(conf_of(root, resource_type))            # warm-up: pinned buffers, code objects, the page cache
         rows = min(n, a.host_rows)
-        dev_s, host_s = [], []
+        fi.create_db_fi(conf_of(root, resource_type, True))
+        dev_s, enc_s, host_s = [], [], []
         for _ in range(a.reps):                                 # alternating
             t0 = time.perf_counter()
             fi.create_db_fi(conf_of(root, resource_type))
             dev_s.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            fi.create_db_fi(conf_of(root, resource_type, True))
+            enc_s.append(time.perf_counter() - t0)
             host_s.append(host_way(records, scratch, rows))
     finally:
         os.chdir(cwd)
     res.update(create_db_fi_s=min(dev_s), create_db_fi_s_all=dev_s, crops_per_s=n / min(dev_s), host_rows_run=rows,
+               device_encode_create_db_fi_s_all=enc_s, device_encode_crops_per_s=n / min(enc_s),
                host_loop_s_all=host_s, host_loop_crops_per_s=rows / min(host_s), host_loop_s_for_tree=min(host_s) * n / rows)
     shutil.rmtree(scratch)
     return {'%s_%s' % (tag, k): v for k, v in res.items()}
