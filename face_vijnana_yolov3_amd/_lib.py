@@ -125,6 +125,7 @@ def _declare(L):
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_crop_nearest_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
+        'fv_gather_u8_f32': (i32, [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_int32), i32, vp]),
         'fv_draw_prims_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
                                   ctypes.POINTER(DrawPrim), i32, vp, i64]),
         'fv_yolov3_num_layers': (i32, []),

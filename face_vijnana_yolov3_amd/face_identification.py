@@ -5,8 +5,8 @@ Port of the reference's `src/space/face_identification.py` (fi.py): the model (f
 variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, fi.py:645-770), `evaluate` (fi.py:772-992), `test`
 (fi.py:994-1153) and `main` (fi.py:1715-1760) for the modes it dispatches, and the data mode (`create_db_fi` /
 `save_extracted_face`, fi.py:78-280) that cuts the face crops and writes the subject db everything else reads.  The hot path is
-the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_fid_match,
-fv_fid_pair_dists, fv_draw_prims_u8); this module holds the
+the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_gather_u8_f32,
+fv_fid_match, fv_fid_pair_dists, fv_draw_prims_u8); this module holds the
 weights and drives it.  fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
@@ -234,8 +234,12 @@ class _TripletSequence(object):
     def __len__(self):
         return self.hps['step']
 
+    def path(self, label):
+        """The crop file of db row `label`."""
+        return os.path.join(self.raw_data_path, self.FACES_DIR, self.db.loc[label, 'face_file'])
+
     def _image(self, label):
-        img = _imread(os.path.join(self.raw_data_path, self.FACES_DIR, self.db.loc[label, 'face_file']))
+        img = _imread(self.path(label))
         return img.astype(np.float32) / np.float32(255.0)
 
     def rows(self, index):
@@ -474,6 +478,26 @@ def crop_nearest_u8(ctx, images, crops, image_size, out=None):
     return out
 
 
+GATHER_CHUNK = 128               # FV_GATHER_CHUNK of include/fv_hotpath.h: indices per launch of fv_gather_u8_f32
+
+
+def gather_crops_f32(ctx, store, idx, out=None):
+    """fv_gather_u8_f32: store (N, ...) uint8 CUDA tensor, idx int sequence -> (n, ...) float32 CUDA tensor, out[j] = store[idx[j]]
+    / 255 (correctly rounded; stream-ordered).  A slot's byte count must be a multiple of 16."""
+    idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), np.int32)
+    if store.dtype != torch.uint8 or not store.is_cuda or store.dim() < 2:
+        raise ValueError('gather_crops_f32 expects a uint8 CUDA tensor of slots')
+    n, elems = len(idx), int(np.prod(store.shape[1:]))
+    if out is None:
+        out = torch.empty((n,) + tuple(store.shape[1:]), dtype=torch.float32, device=store.device)
+    elif out.dtype != torch.float32 or out.device != store.device or out.numel() != n * elems:
+        raise ValueError('gather_crops_f32: out must be a float32 tensor of %d x %d elements on the store\'s device' % (n, elems))
+    rc = lib().fv_gather_u8_f32(ctx.handle, ptr(store), int(store.shape[0]), elems, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                n, ptr(out))
+    ctx.check(rc, 'fv_gather_u8_f32')
+    return out
+
+
 def draw_prims_u8(ctx, images, prims, masks):
     """fv_draw_prims_u8: draw the annotate.Outline / annotate.MaskBlend records `prims`, in order, onto images = (device uint8
     buffer, offsets, hw) of a batch, in place (stream-ordered).  masks: uint8 CUDA tensor the MaskBlend offsets point into
@@ -673,6 +697,9 @@ def write_bytes(data, path):
 # device_encode where a configuration does not say: on -- the files are the same bytes, and DESIGN.md section 18 gives the
 # measurements behind the choice
 DEVICE_ENCODE_DEFAULT = True
+# crop_store where a configuration does not say: on -- train() and the facial-ID database read their crops from a device-resident
+# store (crop_store.py); the inputs are the same bits, and DESIGN.md section 19 gives the measurements
+CROP_STORE_DEFAULT = True
 
 
 def encode_on_device(device_encode, h, w):
@@ -837,6 +864,25 @@ class FaceIdentifier(object):
         loss = self.model.train_on_batch(xa, xp, xn, h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0))
         return float(loss.item())
 
+    def _loader_threads(self):
+        from .face_detection import default_loader_threads
+        return max(1, int(self.hps.get('loader_threads', default_loader_threads())))
+
+    def _triplet_inputs(self, tr_gen):
+        """crop_store.TripletInputs over the sequence's db (hps['crop_store'], on by default; hps['crop_store_mb'] bounds the
+        resident store, 0 forces the per-batch tier), or None: the sequence's own load().  The training workspace of the first
+        batch is allocated first, so that the default budget -- half of what is free -- is taken from what training leaves."""
+        if not self.hps.get('crop_store', CROP_STORE_DEFAULT):
+            return None
+        from .crop_store import TripletInputs, store_budget
+        m = self.model
+        first = slice_triplets(tr_gen.rows(0), self.world, self.rank) if len(tr_gen) else None
+        if first is not None and len(first[0]):
+            m.ensure_optimizer()
+            m._workspace(len(first[0]), self.image_size, True)
+        return TripletInputs(m.ctx, m.dev, self.image_size, list(tr_gen.db.index), tr_gen.path, tr_gen.batch_size,
+                             store_budget(self.hps, m.dev), self._loader_threads())
+
     def train(self):
         """fi.py:616-643: fit_generator over the triplet sequence (batch order shuffled every epoch, as Keras does for a Sequence),
         hps['epochs'] epochs of hps['step'] steps (the sequence sets hps['step'] to its batch count), then save face_identifier.h5.
@@ -860,23 +906,34 @@ class FaceIdentifier(object):
             tr_gen = sequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=True)
         h = self.hps
         steps, epochs = int(h['step']), int(h['epochs'])
+        inputs = self._triplet_inputs(tr_gen)
         # one rank: the global numpy stream, as before; several: one seeded generator, the same batch order on every rank
         rng = np.random.default_rng(0) if self.world > 1 else np.random
-        for e in range(epochs):
-            losses = []
-            for i in rng.permutation(len(tr_gen))[:steps]:
-                part = slice_triplets(tr_gen.rows(int(i)), self.world, self.rank)
-                if part is None:       # on every rank alike: a rank that stayed out of a collective would hang the others
-                    if self.rank == 0:
-                        print('batch %d - skipped (fewer triplets than ranks)' % int(i))
-                    continue
-                rows, weight = part
-                x, _ = tr_gen.load(rows)
-                loss = trainer.train_on_inputs((x['input_a'], x['input_p'], x['input_n']), h['lr'], h['beta_1'], h['beta_2'],
-                                               h.get('decay', 0.0), weight=weight)
-                losses.append(trainer.merged_loss(loss, weight))          # collective: every rank calls it
-            if self.rank == 0:
-                print('Epoch %d/%d - loss: %.4f' % (e + 1, epochs, float(np.mean(losses)) if losses else float('nan')))
+        try:
+            for e in range(epochs):
+                losses = []
+                order = [int(i) for i in rng.permutation(len(tr_gen))[:steps]]
+                parts = [slice_triplets(tr_gen.rows(i), self.world, self.rank) for i in order]
+                # crop_store: this epoch's inputs come from the store, in step order (per batch: the next one decodes meanwhile)
+                feed = None if inputs is None else inputs.batches([part[0] for part in parts if part is not None])
+                for i, part in zip(order, parts):
+                    if part is None:       # on every rank alike: a rank that stayed out of a collective would hang the others
+                        if self.rank == 0:
+                            print('batch %d - skipped (fewer triplets than ranks)' % i)
+                        continue
+                    rows, weight = part
+                    if feed is None:
+                        x, _ = tr_gen.load(rows)
+                        xs = (x['input_a'], x['input_p'], x['input_n'])
+                    else:
+                        xs = next(feed)
+                    loss = trainer.train_on_inputs(xs, h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0), weight=weight)
+                    losses.append(trainer.merged_loss(loss, weight))          # collective: every rank calls it
+                if self.rank == 0:
+                    print('Epoch %d/%d - loss: %.4f' % (e + 1, epochs, float(np.mean(losses)) if losses else float('nan')))
+        finally:
+            if inputs is not None:
+                inputs.close()
         if self.rank == 0:
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
@@ -899,13 +956,42 @@ class FaceIdentifier(object):
             for ff in list(df.iloc[:, 1]):
                 names.append(ff); sids.append(subject_id)
         step = max(1, Engine.max_infer_batch(self.image_size))
+        paths = [os.path.join(self.raw_data_path, faces_dir, ff) for ff in names]
         ids = []
-        for i in range(0, len(names), step):
-            x = np.asarray([_imread(os.path.join(self.raw_data_path, faces_dir, ff)) for ff in names[i:i + step]])
-            ids.append(self.fid_extractor.predict(x))
+        if self.hps.get('crop_store', CROP_STORE_DEFAULT) and names:
+            ids = [d.cpu().numpy() for d in self._extract_from_store(paths, step)]
+        else:
+            for i in range(0, len(names), step):
+                x = np.asarray([_imread(f) for f in paths[i:i + step]])
+                ids.append(self.fid_extractor.predict(x))
         ids = np.concatenate(ids) if ids else np.zeros((0, DENSE1_DIM), np.float32)
         self._db_cache = (names, sids, ids)
         return names, sids, ids
+
+    def _extract_from_store(self, paths, step):
+        """Facial IDs (device tensors, one per chunk of at most `step` crops) of the crop files `paths` through a CropStore:
+        decoded on the loader pool; a db within the budget (crop_store.store_budget, taken once the extraction workspace exists)
+        is loaded once and gathered chunk by chunk, a larger one is loaded chunk by chunk into two stores that alternate."""
+        from concurrent.futures import ThreadPoolExecutor
+        from .crop_store import RESIDENT, CropStore, plan_store, store_budget
+        from .postproc import PinnedRing
+        m, S, n = self.model, self.image_size, len(paths)
+        m._workspace(min(step, n), S, False)
+        ids = []
+        with ThreadPoolExecutor(max_workers=self._loader_threads()) as pool:
+            if plan_store(n, S, store_budget(self.hps, m.dev)) == RESIDENT:
+                store = CropStore(m.ctx, n, S, m.dev)
+                store.load(paths, list(range(n)), pool)
+                for i in range(0, n, step):
+                    ids.append(m.extract_device(store.gather(range(i, min(i + step, n)))))
+            else:
+                ring = PinnedRing(2)
+                stores = [CropStore(m.ctx, min(step, n), S, m.dev, ring) for _ in range(2)]
+                for k, i in enumerate(range(0, n, step)):
+                    part = paths[i:i + step]
+                    stores[k % 2].load(part, list(range(len(part))), pool)
+                    ids.append(m.extract_device(stores[k % 2].gather(range(len(part)))))
+        return ids
 
     def make_facial_ids_db(self):
         """fi.py:645-700: subject_facial_ids.h5 (vggface2: subject_facial_vggface2_ids.h5), one dataset per face file."""

@@ -135,13 +135,15 @@ class BatchPlan(object):
         self.total_coefs, self.plane_bytes, self.rgb_bytes = coef, plane, rgb
 
 
-def reconstruct_batch(ctx, plan, coefs_dev, device):
+def reconstruct_batch(ctx, plan, coefs_dev, device, rgb=None):
     """coefficients of the batch (int16 CUDA tensor laid out by `plan`) -> packed RGB uint8 CUDA tensor (image i at
-    plan.rgb_off[i], hw plan.hw[2i:2i+2]): what fv_letterbox_batch takes as `packed`."""
+    plan.rgb_off[i], hw plan.hw[2i:2i+2]): what fv_letterbox_batch takes as `packed`.  rgb: a flat uint8 CUDA tensor to write
+    into instead of a new one -- image i then lands at plan.descs[i].rgb_off, which the caller has set (crop_store.CropStore)."""
     import torch
     descs = torch.frombuffer(bytearray(bytes(plan.descs)), dtype=torch.uint8).to(device, non_blocking=True)
     planes = torch.empty(max(plan.plane_bytes, 16), dtype=torch.uint8, device=device)
-    rgb = torch.empty(max(plan.rgb_bytes, 16), dtype=torch.uint8, device=device)
+    if rgb is None:
+        rgb = torch.empty(max(plan.rgb_bytes, 16), dtype=torch.uint8, device=device)
     rc = _fn().fv_jpeg_reconstruct_batch(ctx.handle, ptr(coefs_dev), ptr(descs), plan.n, ptr(planes), ptr(rgb), plan.max_blocks, plan.max_pixels)
     ctx.check(rc, 'fv_jpeg_reconstruct_batch')
     return rgb

@@ -346,6 +346,20 @@ int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offset
  * side that rounds to 0 is FV_ERR_INVALID and nothing is enqueued. */
 int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
                        const int32_t* crops, int n, int image_size, uint8_t* dst);
+/* Rows of a device-resident store of uint8 images as a float32 batch in [0, 1] (the input of FaceIdentifier.train and of the
+ * facial-ID database from crop_store.CropStore; fi.py:1577, `img.astype(np.float32) / 255.0`, without the host).  store: DEVICE
+ * array of n_slots slots of elems bytes each; idx: HOST int32 [n]; dst: DEVICE float32 [n][elems]:
+ *     dst[j][e] = (float)store[idx[j] * elems + e] / 255.0f,
+ * the correctly rounded IEEE float32 quotient -- bit for bit numpy's `x.astype(np.float32) / np.float32(255.0)` for each of the 256
+ * byte values, whatever floating-point flags the library is built with (csrc/crop_gather.hip).  Indices may repeat and come in
+ * any order.  Stream-ordered; no device allocation and no synchronisation inside the call; the index list travels in the kernel
+ * arguments, FV_GATHER_CHUNK indices per launch, chunked inside the call.  Any n; n == 0 does nothing.  All byte offsets are
+ * 64-bit (a store of 416 x 416 x 3 crops passes 4 GiB at slot 8 273).  Every argument is checked before the first launch, and
+ * before the context is looked at: an index outside [0, n_slots), elems < 16, elems % 16 != 0, elems > 2^36, a store or dst that
+ * is not 16-byte aligned, a negative n or n_slots, or a null pointer with n > 0 is FV_ERR_INVALID and nothing is enqueued.  An
+ * additive part of ABI version 4. */
+#define FV_GATHER_CHUNK 128
+int fv_gather_u8_f32(fv_ctx* ctx, const uint8_t* store, int64_t n_slots, int64_t elems, const int32_t* idx, int n, float* dst);
 /* Draw onto the packed uint8 RGB images of a batch, in place (FaceIdentifier.evaluate, fi.py:945-992: the rectangles and labels
  * of draw_boxes_v3, yolov3_detect.py:515-530).  packed / offsets / hw: the batch's n_img decoded images as for
  * fv_letterbox_batch.  prims: HOST array of n primitives, applied in order; masks: DEVICE buffer of mask_bytes 8-bit masks.
