@@ -21,5 +21,7 @@ int fv_fid_dense_finish(fv_ctx* ctx, const float* part, long long chunks, int M,
 int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias, double loss_weight);
 // dX = dE . W^T, written (not added) into the rows of dX
 int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const float* W, FidRows dX);
+// The reconstruction model's head: u [M][64] = relu(l2_normalize(ids)), x [M][F] = u . W^T + bias (W the dense kernel [F][64])
+int fv_fid_recon_head(fv_ctx* ctx, const float* ids, int M, long long F, const float* W, const float* bias, float* u, float* x);
 // dW [F][64] = X^T . dE over the M rows, stored
 int fv_fid_dense_wgrad(fv_ctx* ctx, FidRows X, const float* dE, int M, long long F, float* dW);

@@ -148,11 +148,14 @@ __global__ __launch_bounds__(256) void fid_triplet_kernel(const float* __restric
     if (threadIdx.x == 0) *loss = (float)((((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3]) / (double)B);
 }
 
-// dX[m][f] = sum_n dE[m][n] W[f][n]: a thread owns one f (its kernel row in 64 registers) and walks the rows of dE, staged in LDS.
-__global__ __launch_bounds__(256) void fid_dense_dgrad_kernel(const float* __restrict__ dE, int M, long long F, const float* __restrict__ W,
-                                                              FidRows dX) {
+// dX[m][f] = sum_n dE[m][n] W[f][n] (+ bias[f], added last): a thread owns one f (its kernel row in 64 registers) and walks the
+// rows of dE, staged in LDS.
+template <bool BIAS>
+__device__ __forceinline__ void dense_dgrad_body(const float* __restrict__ dE, int M, long long F, const float* __restrict__ W,
+                                                 const float* __restrict__ bias, const FidRows& dX) {
     __shared__ __attribute__((aligned(16))) float es[DG_MT][FID_DIM];
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+    const float bf = BIAS ? bias[f] : 0.f;
     float w[FID_DIM];
 #pragma unroll
     for (int q = 0; q < FID_DIM / 4; ++q) {
@@ -172,9 +175,33 @@ __global__ __launch_bounds__(256) void fid_dense_dgrad_kernel(const float* __res
                 acc += e.x * w[4 * q]; acc += e.y * w[4 * q + 1]; acc += e.z * w[4 * q + 2]; acc += e.w * w[4 * q + 3];
             }
             const int m = m0 + r;
-            dX.p[m / dX.per][(long long)(m % dX.per) * F + f] = acc;
+            dX.p[m / dX.per][(long long)(m % dX.per) * F + f] = BIAS ? acc + bf : acc;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void fid_dense_dgrad_kernel(const float* __restrict__ dE, int M, long long F, const float* __restrict__ W,
+                                                              FidRows dX) {
+    dense_dgrad_body<false>(dE, M, F, W, nullptr, dX);
+}
+
+// The reconstruction model's dense layer (reference face_identification.py:1171-1180): x[m][f] = sum_n u[m][n] K[f][n] + b[f] -- the
+// data-gradient's product with u in the place of dE, the same sequential sum over n, the bias added last.
+__global__ __launch_bounds__(256) void fid_dense_bias_kernel(const float* __restrict__ u, int M, long long F, const float* __restrict__ W,
+                                                             const float* __restrict__ bias, FidRows X) {
+    dense_dgrad_body<true>(u, M, F, W, bias, X);
+}
+
+// u = relu(l2_normalize(ids)) over the 64 values of a row (x * rsqrt(max(sum x^2, 1e-12)), TF 1.13): one wave per row, the sum of
+// squares by an xor butterfly -- one fixed order, the same in every lane.
+__global__ __launch_bounds__(256) void fid_ids_l2_relu_kernel(const float* __restrict__ ids, int M, float* __restrict__ u) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), n = threadIdx.x & 63;
+    const float v = m < M ? ids[(long long)m * FID_DIM + n] : 0.f;
+    float s = v * v;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float r = v * (1.0f / sqrtf(fmaxf(s, 1e-12f)));
+    if (m < M) u[(long long)m * FID_DIM + n] = r > 0.f ? r : 0.f;
 }
 
 // dW[f][n] = sum_m X[m][f] dE[m][n] in row order: workgroup = 64 kernel rows, thread (n = tid & 63, g = tid >> 6) owns the 16 rows
@@ -250,6 +277,22 @@ int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const f
     FV_REQUIRE(ctx, F > 0 && F % FID_KC == 0 && rows_ok(dX, M) && dE && W, "fid_dense_dgrad: F must be a positive multiple of %d", FID_KC);
     FvProfScope ps(ctx, "fid_dense_dgrad_kernel", 2.0 * M * F * FID_DIM, 4.0 * ((double)F * FID_DIM + (double)M * F));
     hipLaunchKernelGGL(fid_dense_dgrad_kernel, dim3((unsigned)(F / 256)), dim3(256), 0, ctx->stream, dE, M, F, W, dX);
+    FV_LAUNCH_CHECK(ctx);
+    return FV_OK;
+}
+
+int fv_fid_recon_head(fv_ctx* ctx, const float* ids, int M, long long F, const float* W, const float* bias, float* u, float* x) {
+    FV_REQUIRE(ctx, ids && W && bias && u && x, "fid_recon_head: NULL buffer");
+    FV_REQUIRE(ctx, M >= 1 && F > 0 && F % FID_KC == 0, "fid_recon_head: needs rows >= 1 and F a positive multiple of %d (rows=%d, F=%lld)",
+               FID_KC, M, F);
+    {
+        FvProfScope ps(ctx, "fid_ids_l2_relu_kernel", 0.0, 8.0 * M * FID_DIM);
+        hipLaunchKernelGGL(fid_ids_l2_relu_kernel, dim3((M + 3) / 4), dim3(256), 0, ctx->stream, ids, M, u);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    FvProfScope ps(ctx, "fid_dense_bias_kernel", 2.0 * M * F * FID_DIM, 4.0 * ((double)F * (FID_DIM + 1) + (double)M * F));
+    hipLaunchKernelGGL(fid_dense_bias_kernel, dim3((unsigned)(F / 256)), dim3(256), 0, ctx->stream, (const float*)u, M, F, W, bias,
+                       FidRows{{x, nullptr, nullptr}, M});
     FV_LAUNCH_CHECK(ctx);
     return FV_OK;
 }

@@ -8,7 +8,10 @@ int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H
                        double* stat_slots = nullptr, int stat_nslot = 0);
 // optional fused BN-backward reduction of the layer whose output gradient a data-gradient produces (conv.h FV_EPI_BNRED)
 struct FvBnRed { const float *z, *scale, *shift, *mean, *invstd; double* slots; int nslot; float leaky; };
+// s2_pad_lo: rows / columns of zero padding in FRONT of the input of the stride-2 forward conv this is the gradient of.  1: this
+// network's ZeroPadding2D(1) + 'valid' layers (dx[h] = sum_{2i + r - 1 = h}); 0: a 'same'-padded stride-2 conv, which pads (0, 1) --
+// Keras' Conv2DTranspose(strides=2, padding='same'), out[h] = sum_{2i + r = h} (the reconstruction model, net_recon.hip)
 int fv_op_conv_dgrad(fv_ctx* ctx, const float* dy, const float* w_t, int B, int H, int W, int cin, int cout_pad, int ksize,
-                     int stride, const float* addend, float* dx, const FvBnRed* bn = nullptr);
+                     int stride, const float* addend, float* dx, const FvBnRed* bn = nullptr, int s2_pad_lo = 1);
 int fv_op_conv_wgrad(fv_ctx* ctx, const float* x, const float* dy, int B, int H, int W, int cin, int cout, int dy_stride,
                      int ksize, int stride, float* dw);

@@ -38,8 +38,9 @@ int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H
 }
 
 int fv_op_conv_dgrad(fv_ctx* ctx, const float* dy, const float* w_t, int B, int H, int W, int cin, int cout_pad, int ksize,
-                     int stride, const float* addend, float* dx, const FvBnRed* bn) {
+                     int stride, const float* addend, float* dx, const FvBnRed* bn, int s2_pad_lo) {
     FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "dgrad: unsupported k=%d s=%d", ksize, stride);
+    FV_REQUIRE(ctx, s2_pad_lo == 0 || s2_pad_lo == 1, "dgrad: s2_pad_lo must be 0 or 1");
     FV_REQUIRE(ctx, cout_pad % 32 == 0, "dgrad: cout_pad must be a multiple of 32");
     FV_REQUIRE(ctx, H % stride == 0 && W % stride == 0, "dgrad: H,W must be divisible by the stride");
     FvConvArgs a{};
@@ -65,21 +66,23 @@ int fv_op_conv_dgrad(fv_ctx* ctx, const float* dy, const float* w_t, int B, int 
     } else {
         // forward: z[oh] reads x[2 oh - 1 + r].  Output pixel h = 2a+ph receives from r with
         // (h+1-r) even: ph=0 -> r=1 (oh=a); ph=1 -> r=0 (oh=a+1), r=2 (oh=a).  One class per (ph,pw).
+        // s2_pad_lo = 0: z[oh] reads x[2 oh + r]: ph=0 -> r=0 (oh=a), r=2 (oh=a-1); ph=1 -> r=1 (oh=a).
+        const int p = s2_pad_lo;
         FV_REQUIRE(ctx, H % 2 == 0 && W % 2 == 0, "dgrad: stride 2 needs even H, W");
         a.Hl = H / 2; a.Wl = W / 2; a.os = 2; a.nclass = 4;
         for (int ph = 0; ph < 2; ++ph)
             for (int pw = 0; pw < 2; ++pw) {
                 // class = blockIdx.z, dispatched in ascending order: the 4-tap class (ph = pw = 1) goes
-                // first and the 1-tap class last, so the longest tiles are not left for the tail
-                int c = 3 - (ph * 2 + pw);
+                // first and the 1-tap class last, so the longest tiles are not left for the tail (p = 0: that class is ph = pw = 0)
+                int c = p ? 3 - (ph * 2 + pw) : ph * 2 + pw;
                 a.oph[c] = ph; a.opw[c] = pw;
                 FvTaps& t = a.taps[c];
                 t.n = 0;
                 for (int r = 0; r < 3; ++r) {
-                    if ((ph + 1 - r) % 2 != 0) continue;
+                    if ((ph + p - r) % 2 != 0) continue;
                     for (int q = 0; q < 3; ++q) {
-                        if ((pw + 1 - q) % 2 != 0) continue;
-                        t.dh[t.n] = (ph + 1 - r) / 2; t.dw[t.n] = (pw + 1 - q) / 2; t.wslot[t.n] = r * 3 + q;
+                        if ((pw + p - q) % 2 != 0) continue;
+                        t.dh[t.n] = (ph + p - r) / 2; t.dw[t.n] = (pw + p - q) / 2; t.wslot[t.n] = r * 3 + q;
                         ++t.n;
                     }
                 }

@@ -10,7 +10,8 @@ fv_fid_match, fv_fid_pair_dists, fv_draw_prims_u8); this module holds the
 weights and drives it.  fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
-Not ported: the reconstruction model (dead code in the reference).  evaluate() is a method only: main() does not dispatch
+The reconstruction model (`create_face_reconst_model`, fi.py:1155-1488) is ReconModel over fv_recon_forward; the
+reference never calls it from a mode, and neither does main().  evaluate() is a method only: main() does not dispatch
 fi_conf.mode 'evaluate' yet.  Differences, documented in DESIGN.md: the BN moving-statistics update order
 of the three towers (a -> p -> n), a zero gradient at a triplet distance of exactly 0, test() and evaluate() batching their
 frames and crops (same rows), fp64 match distances, crops whose letterboxed side rounds to 0 being skipped (the reference's
@@ -180,6 +181,197 @@ class FidExtractor(object):
 
     def predict(self, images):
         return self.predict_device(images).cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- reconstruction model (fi.py:1155-1488)
+RECON_MODEL_PATH = 'face_vijnana_recon.h5'
+_BN_WEIGHTS = ('gamma', 'beta', 'moving_mean', 'moving_variance')
+
+
+def recon_offsets(image_size):
+    """The fv_recon_param_count layout: dict(dense, bias, bn, count) in floats -- the 52 conv kernels at their fv_layer w_off,
+    the dense kernel [F][64], the bias [F], then per layer gamma, beta, moving mean, moving variance ([4][cout]); layer l's four
+    vectors begin at bn + 4 * (mean_off / 2)."""
+    d = base_layers()[-1]
+    F = feature_size(image_size)
+    dense = d['beta_off'] + d['cout']
+    bias = dense + F * DENSE1_DIM
+    bn = bias + F
+    return dict(dense=dense, bias=bias, bn=bn, count=bn + 4 * (d['var_off'] + d['cout']) // 2)
+
+
+def recon_stage_order():
+    """Indices into the layer table in the order the model runs its stages (fi.py:1187-1484): 51 .. 0."""
+    return list(range(NUM_BASE_LAYERS - 1, -1, -1))
+
+
+def recon_h5_layout(image_size):
+    """[(dataset path, shape)] of face_vijnana_recon.h5, Keras' weight layout under the reference's layer names: dense1 (the
+    TRANSPOSED dense kernel [64][F] and a bias [F], fi.py:1179-1180), then per stage its BatchNormalization `bnorm_<i>` and its
+    Conv2DTranspose, named as the conv layer it mirrors (`conv_<i>`, i the Darknet index; `output` for layer 0, fi.py:1475) with
+    that layer's (k, k, Cin, Cout) kernel.  Needs no device."""
+    F = feature_size(image_size)
+    out = [('/model_weights/dense1/dense1/kernel:0', (DENSE1_DIM, F)), ('/model_weights/dense1/dense1/bias:0', (F,))]
+    layers = base_layers()
+    for l in recon_stage_order():
+        d = layers[l]
+        i = d['darknet_index']
+        out += [('/model_weights/bnorm_%d/bnorm_%d/%s:0' % (i, i, w), (d['cout'],)) for w in _BN_WEIGHTS]
+        name = 'output' if l == 0 else 'conv_%d' % i
+        out.append(('/model_weights/%s/%s/kernel:0' % (name, name), (d['ksize'], d['ksize'], d['cin'], d['cout'])))
+    return out
+
+
+class ReconModel(Model):
+    """recon_model of create_face_reconst_model (fi.py:1155-1488): a facial ID (64 floats) back through the transposed dense1
+    layer and the 52 base layers as Conv2DTranspose layers to an (S, S, 3) image -- fv_recon_forward; the arithmetic is stated in
+    include/fv_hotpath.h.  The flat parameter vector is fv_recon_param_count's (recon_offsets); there is no BN-state vector: every
+    stage's BatchNormalization is a layer of this model and its four vectors are parameters."""
+
+    def __init__(self, image_size, device=0, ctx=None):
+        self.image_size = int(image_size)
+        n_params = int(lib().fv_recon_param_count(self.image_size))
+        if n_params <= 0:
+            raise ValueError('image_size must be a positive multiple of 32')
+        super(ReconModel, self).__init__(ctx if ctx is not None else Context(device), base_layers(), n_params, 0)
+        self.F = feature_size(self.image_size)
+        self.off = recon_offsets(self.image_size)
+        assert self.off['count'] == n_params
+        self.fresh_bn()
+
+    # ------------------------------------------------------------------ parameters
+    def bn_slice(self, l, which):
+        """Range of vector `which` (0 gamma, 1 beta, 2 moving mean, 3 moving variance) of layer l's BatchNormalization."""
+        d = self.layers[l]
+        a = self.off['bn'] + 4 * (d['mean_off'] // 2) + which * d['cout']
+        return slice(a, a + d['cout'])
+
+    def kernel_slice(self, l):
+        d = self.layers[l]
+        return slice(d['w_off'], d['w_off'] + d['cout'] * d['ksize'] * d['ksize'] * d['cin'])
+
+    def dense_kernel(self):
+        """[F][64]: dense1's kernel as the FaceIdentifier holds it (the model multiplies by its transpose)."""
+        return self.params[self.off['dense']:self.off['bias']].view(self.F, DENSE1_DIM)
+
+    def dense_bias(self):
+        return self.params[self.off['bias']:self.off['bn']]
+
+    def fresh_bn(self):
+        """BatchNormalization.from_config (fi.py:1197): a new layer -- gamma 1, beta 0, moving mean 0, moving variance 1."""
+        for l in range(len(self.layers)):
+            self.params[self.bn_slice(l, 0)] = 1.0
+            self.params[self.bn_slice(l, 1)] = 0.0
+            self.params[self.bn_slice(l, 2)] = 0.0
+            self.params[self.bn_slice(l, 3)] = 1.0
+
+    @classmethod
+    def from_identifier(cls, fid_model, seed=None):
+        """The snapshot create_face_reconst_model takes (set_weights copies): the 52 conv kernels and the dense kernel of
+        fid_model, a bias drawn as np.random.RandomState(seed).rand(F) (the reference: np.random.rand, fi.py:1180), fresh BN.
+        Training fid_model afterwards does not change this model."""
+        m = cls(fid_model.image_size, ctx=fid_model.ctx)
+        for l in range(len(m.layers)):
+            m.params[m.kernel_slice(l)] = fid_model.params[m.kernel_slice(l)]
+        m.dense_kernel().copy_(fid_model.dense_kernel())
+        bias = np.random.RandomState(seed).rand(m.F).astype(np.float32)
+        m.dense_bias().copy_(torch.from_numpy(bias))
+        return m
+
+    # ------------------------------------------------------------------ inference
+    def _workspace_bytes(self, batch, image_size, training):
+        return lib().fv_recon_workspace_bytes(batch, image_size)
+
+    def _as_ids(self, ids):
+        ids = torch.as_tensor(ids)
+        if ids.dtype != torch.float32 or ids.device != self.dev:
+            ids = ids.to(device=self.dev, dtype=torch.float32)
+        ids = ids.contiguous()
+        if ids.dim() != 2 or ids.shape[1] != DENSE1_DIM:
+            raise ValueError('expected facial IDs of shape (N, %d), got %r' % (DENSE1_DIM, tuple(ids.shape)))
+        return ids
+
+    def predict_device(self, ids):
+        """ids (N,64) -> (N,S,S,3) float32 CUDA tensor (no activation on the output, fi.py:1483)."""
+        return self._in_parts(self._forward, self._as_ids(ids), image_size=self.image_size)
+
+    def predict(self, ids):
+        return self.predict_device(ids).cpu().numpy()
+
+    def _forward(self, ids):
+        N, S = ids.shape[0], self.image_size
+        ws = self._workspace(N, S, False)
+        out = torch.empty((N, S, S, 3), dtype=torch.float32, device=self.dev)
+        rc = lib().fv_recon_forward(self.ctx.handle, ptr(self.params), ptr(ids), N, S, ptr(ws), ws.numel(), ptr(out))
+        self.ctx.check(rc, 'fv_recon_forward')
+        return out
+
+    # ------------------------------------------------------------------ checkpoint (fi.py:1488 recon_model.save, fi.py:1161 load_model)
+    def _tensors(self):
+        """{dataset path: array} in the recon_h5_layout order."""
+        p = self.params.cpu().numpy()
+        out = collections.OrderedDict()
+        for name, shape in recon_h5_layout(self.image_size):
+            layer, weight = name.split('/')[-2], name.split('/')[-1][:-2]
+            if layer == 'dense1':
+                a = p[self.off['dense']:self.off['bias']].reshape(self.F, DENSE1_DIM).T if weight == 'kernel' else p[self.off['bias']:self.off['bn']]
+            else:
+                l = self._layer_of(layer)
+                if weight == 'kernel':
+                    d = self.layers[l]
+                    a = p[self.kernel_slice(l)].reshape(d['cout'], d['ksize'], d['ksize'], d['cin']).transpose(1, 2, 3, 0)   # OHWI -> HWIO
+                else:
+                    a = p[self.bn_slice(l, _BN_WEIGHTS.index(weight))]
+            out[name] = np.ascontiguousarray(a, dtype=np.float32)
+            assert out[name].shape == tuple(shape), name
+        return out
+
+    def _layer_of(self, name):
+        if name == 'output':
+            return 0
+        i = int(name.split('_')[1])
+        return [l for l, d in enumerate(self.layers) if d['darknet_index'] == i][0]
+
+    def save(self, path):
+        """face_vijnana_recon.h5 in Keras' weight layout (recon_h5_layout) through hdf5_lite: readable by h5py and by
+        `load_weights` of a model built as the reference builds it; it holds no model_config, so not by `load_model`."""
+        from .hdf5_lite import write_hdf5
+        data = self._tensors()
+        groups = collections.OrderedDict()
+        for name in data:
+            groups.setdefault(name.split('/')[2], []).append('/'.join(name.split('/')[3:]))
+        fixed = lambda xs: np.array([x.encode('utf8') for x in xs])
+        attrs = {'/': {'keras_version': b'2.2.4', 'backend': b'tensorflow'},
+                 '/model_weights': {'layer_names': fixed(list(groups)), 'backend': b'tensorflow', 'keras_version': b'2.2.4'}}
+        for g, names in groups.items():
+            attrs['/model_weights/' + g] = {'weight_names': fixed(names)}
+        write_hdf5(path, data, attrs)
+
+    def load(self, path):
+        """A file written by save() (any HDF5 file with these datasets under these names).  Everything is checked before
+        anything is changed."""
+        from .hdf5_lite import read_hdf5
+        datasets, _ = read_hdf5(path)
+        p = np.zeros(self.n_params, np.float32)
+        for name, shape in recon_h5_layout(self.image_size):
+            if name not in datasets:
+                raise FvError('%s lacks %s' % (path, name))
+            a = np.asarray(datasets[name], np.float32)
+            if a.shape != tuple(shape):
+                raise FvError('%s: %s has shape %r, this model expects %r' % (path, name, a.shape, tuple(shape)))
+            layer, weight = name.split('/')[-2], name.split('/')[-1][:-2]
+            if layer == 'dense1':
+                if weight == 'kernel':
+                    p[self.off['dense']:self.off['bias']] = a.T.reshape(-1)
+                else:
+                    p[self.off['bias']:self.off['bn']] = a
+            else:
+                l = self._layer_of(layer)
+                if weight == 'kernel':
+                    p[self.kernel_slice(l)] = a.transpose(3, 0, 1, 2).reshape(-1)          # HWIO -> OHWI
+                else:
+                    p[self.bn_slice(l, _BN_WEIGHTS.index(weight))] = a
+        self.params.copy_(torch.from_numpy(p))
 
 
 # ----------------------------------------------------------------------------- triplet sequences (fi.py:1490-1601)
@@ -857,6 +1049,21 @@ class FaceIdentifier(object):
             self.model.init_synthetic(seed=7)
         else:
             self.model.set_base(*base)
+
+    def create_face_reconst_model(self, seed=None):
+        """fi.py:1155-1488: with fi_conf['face_vijana_recon_load'] (a missing key means false) self.recon_model is read from
+        face_vijnana_recon.h5; otherwise it is built from the current model (ReconModel.from_identifier: a copy, with the dense
+        bias drawn from np.random.RandomState(seed)) and that file is written.  The reference reads the file with Keras'
+        load_model; a Keras-written full-model file is not served here: the file read is the weight
+        layout ReconModel.save writes.  Raises ValueError without a model."""
+        if not isinstance(getattr(self, 'model', None), FidModel):
+            raise ValueError('A valid model instance doesn\'t exist.')
+        if self.conf.get('face_vijana_recon_load'):
+            self.recon_model = ReconModel(self.image_size, ctx=self.model.ctx)
+            self.recon_model.load(RECON_MODEL_PATH)
+            return
+        self.recon_model = ReconModel.from_identifier(self.model, seed)
+        self.recon_model.save(RECON_MODEL_PATH)
 
     def train_on_batch(self, xa, xp, xn):
         """One Keras train_on_batch of the triplet model: fv_fid_train_step, then Adam with fi_conf.hps.  Returns the loss (float)."""

@@ -118,11 +118,12 @@ class Model(object):
         (2 GiB, 2^29 floats) and the largest activation, the first layer's batch x S x S x 32 output, must stay below 2^29."""
         return ((1 << 29) - 1) // (32 * int(image_size) * int(image_size))
 
-    def _in_parts(self, forward, x, *args):
+    def _in_parts(self, forward, x, *args, image_size=None):
         """forward(x, *args) for images x (B,S,S,3).  Inference is per image (moving statistics): a batch beyond what one call
-        addresses runs in parts of a multiple of 8 images, and the outputs (a tensor, a pair or a list) are concatenated."""
+        addresses runs in parts of a multiple of 8 images, and the outputs (a tensor, a pair or a list) are concatenated.
+        image_size: the side of the images the call works on when x does not hold them (ReconModel: x are facial IDs)."""
         B = x.shape[0]
-        cap = self.max_infer_batch(x.shape[1])
+        cap = self.max_infer_batch(x.shape[1] if image_size is None else image_size)
         if not B > cap >= 1:
             return forward(x, *args)
         step = cap // 8 * 8 if cap >= 8 else cap

@@ -276,3 +276,36 @@ def fid_towers_dense_wgrad(ctx, towers, dE, M, F, dw=None):
     rc = lib().fv_fid_towers_dense_wgrad(ctx.handle, x0, x1, x2, per, ptr(dE), M, F, ptr(dw))
     ctx.check(rc, 'fv_fid_towers_dense_wgrad')
     return dw
+
+
+def recon_dense_head(ctx, ids, w, bias):
+    """ids (N,64), w (F,64), bias (F,) -> (u (N,64) = relu(l2_normalize(ids)), x (N,F) = u . w^T + bias)."""
+    N, F = ids.shape[0], w.shape[0]
+    u = torch.empty((N, 64), dtype=torch.float32, device=ids.device)
+    x = torch.empty((N, F), dtype=torch.float32, device=ids.device)
+    ctx.check(lib().fv_recon_dense_head(ctx.handle, ptr(ids.contiguous()), N, F, ptr(w.contiguous()), ptr(bias.contiguous()), ptr(u), ptr(x)),
+              'fv_recon_dense_head')
+    return u, x
+
+
+def l2norm_affine(ctx, x, scale, shift, skip=None, leaky=0.1, keep_d=True):
+    """x (rows,C) [, skip (rows,C)] -> (y, d): d = x - skip (None without skip or with keep_d=False), y = BN-folded l2-normalised
+    leaky_relu(d) (fv_l2norm_affine)."""
+    rows, C = x.shape
+    y = torch.empty_like(x)
+    d = torch.empty_like(x) if (skip is not None and keep_d) else None
+    ctx.check(lib().fv_l2norm_affine(ctx.handle, ptr(x), _p(skip), _p(d), ptr(scale), ptr(shift), ptr(y), rows, C, float(leaky)),
+              'fv_l2norm_affine')
+    return y, d
+
+
+def conv2d_transpose(ctx, x, w, stride=1):
+    """x (B,Hin,Win,Cout), w OHWI (Cout,k,k,Cin) of the conv layer whose kernel the transposed conv carries
+    -> (B,Hin*stride,Win*stride,Cin): Keras' Conv2DTranspose(Cin, k, strides=stride, padding='same', use_bias=False)."""
+    B, Hin, Win, cout = x.shape
+    k, cin = w.shape[1], w.shape[3]
+    wt = transpose_weights(ctx, w)
+    out = torch.empty((B, Hin * stride, Win * stride, cin), dtype=torch.float32, device=x.device)
+    rc = lib().fv_conv2d_transpose(ctx.handle, ptr(x.contiguous()), ptr(wt), B, Hin, Win, cin, cout, k, stride, ptr(out))
+    ctx.check(rc, 'fv_conv2d_transpose')
+    return out

@@ -543,6 +543,45 @@ typedef struct {
 int fv_fid_pair_dists(fv_ctx* ctx, const float* ids, int64_t n_ids, const fv_pair_block* blocks, int n_blocks,
                       const float* thresholds, int n_th, float* dists, int64_t n_dists, int64_t* counts);
 
+/* ------------------------------------------------------------------ FaceIdentifier: the reconstruction model
+ * create_face_reconst_model (fi.py:1155-1488): a facial ID [64] back through the network to an image [S][S][3].
+ *   head : u = relu(l2_normalize(ids)) (x * rsqrt(max(sum x^2, 1e-12)));  x = u . K^T + b, K the dense1 kernel [F][64],
+ *          b [F];  reshaped to [g][g][1024] NHWC, g = S / 32, F = g^2 * 1024;  skip = x.
+ *   stage(l), l a base layer (Cin -> Cout, k, stride):  y = BN_l(l2_normalize_channels(leaky_relu(x, 0.1))) over the Cout
+ *          channels of every pixel (same rsqrt(max(., 1e-12)): an all-zero pixel stays zero; BN_l inference-mode with eps 1e-3
+ *          and its OWN gamma / beta / mean / variance), then x = Conv2DTranspose(Cin, k, strides, 'same', no bias) of y with layer
+ *          l's kernel.  Stride 1: the layer's data-gradient (fv_conv2d_dgrad).  Stride 2: out[h] = sum_{2i + r = h} in[i] w[r],
+ *          r = 0..2, the gradient of a 'same'-padded ((0, 1)) stride-2 conv -- NOT the data-gradient of this network's stride-2
+ *          layers, which pad (1, 1) (sum_{2i + r - 1 = h}).
+ *   order: layers 51 .. 2: a stride-2 layer is one stage, then skip = x; the others come as a residual block's 3x3 then its 1x1:
+ *          two stages, then x = x - skip, skip = x.  Then stage(1), stage(0); no activation on the [S][S][3] output.
+ * Flat parameter layout: the 52 conv kernels at their fv_layer w_off (the gamma / beta slots between them are unused), then K
+ * [F][64], then b [F], then per layer l = 0..51 gamma, beta, moving mean, moving variance of ITS BN ([4][Cout_l], layers in order).
+ * Keras itself is not importable in this build's environment: the model is pinned against a float64 restatement of the above. */
+int64_t fv_recon_param_count(int image_size);   /* 0 unless image_size is a positive multiple of 32 */
+size_t fv_recon_workspace_bytes(int batch, int image_size);
+/* ids [batch][64] -> out [batch][S][S][3].  The transposed kernel images and the folded BN scale / shift are made in the workspace
+ * on EVERY call (nothing is cached in the context: `params` may change between calls); three rotating activation buffers; the
+ * tail-split scratch of the conv launcher is lent out of the workspace for the call.  No atomics: the same call gives the same
+ * bits.  Batch bound as fv_forward_infer (batch * S * S * 32 < 2^29). */
+int fv_recon_forward(fv_ctx* ctx, const float* params, const float* ids, int batch, int image_size, void* workspace,
+                     size_t workspace_bytes, float* out);
+/* The model's kernels as single operators (parity tests).
+ * fv_recon_dense_head: ids [rows][64] -> u [rows][64] = relu(l2_normalize(ids)) and out [rows][F] = u . w^T + bias, w [F][64],
+ *   bias [F], F % 256 == 0; each element one fp32 chain over the 64 columns in order, the bias added last.
+ * fv_l2norm_affine: rows pixels of C floats, C one of 32, 64, 128, 256, 512, 1024 (FV_ERR_INVALID otherwise, nothing written):
+ *   d = x - skip (skip NULL: d = x), l = leaky_relu(d, leaky), y = l * (1 / sqrt(max(sum_c l^2, 1e-12))) * scale[c] + shift[c].
+ *   d_out (may be NULL) receives d and may be x itself; y must be a buffer of its own.  A pixel's bits do not depend on rows.
+ * fv_conv2d_transpose: x [B][Hin][Win][cout] -> out [B][Hin*stride][Win*stride][cin] = Conv2DTranspose(cin, ksize, stride, 'same')
+ *   with the kernel of a conv layer cin -> cout given as its fv_transpose_weights image w_t [cin][ksize^2][cout]; cout % 32 == 0.
+ *   ksize 1 / stride 1 and ksize 3 / stride 1 or 2 (the stride-2 alignment described above).  cin == 3 (needs cout == 32,
+ *   ksize 3, stride 1, Hin % 8 == 0, Win % 32 == 0) runs the direct vector-FMA kernel; any other cin the matrix-core tiles. */
+int fv_recon_dense_head(fv_ctx* ctx, const float* ids, int rows, int64_t F, const float* w, const float* bias, float* u, float* out);
+int fv_l2norm_affine(fv_ctx* ctx, const float* x, const float* skip, float* d_out, const float* scale, const float* shift,
+                     float* y, int64_t rows, int C, float leaky);
+int fv_conv2d_transpose(fv_ctx* ctx, const float* x, const float* w_t, int B, int Hin, int Win, int cin, int cout, int ksize,
+                        int stride, float* out);
+
 /* ------------------------------------------------------------------ secondary: three-scale YOLOv3
  * (SURVEY 8a-17/18).  The reference builds this graph in make_yolov3_model (yd.py:217-311) and
  * runs it only from yolov3_detect.py:_main_ (COCO demo: yd.py:596-598 decode, do_nms); FaceDetector
