@@ -6,8 +6,10 @@ variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, f
 (fi.py:994-1153) and `main` (fi.py:1715-1760) for the modes it dispatches, and the data mode (`create_db_fi` /
 `save_extracted_face`, fi.py:78-280) that cuts the face crops and writes the subject db everything else reads.  The hot path is
 the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_gather_u8_f32,
-fv_fid_match, fv_fid_pair_dists, fv_draw_prims_u8); this module holds the
-weights and drives it.  fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
+fv_fid_match, fv_fid_pair_dists, fv_fid_mine_negatives, fv_draw_prims_u8); this module holds the
+weights and drives it.  fi_conf.hps['triplet_mining'] ('semi_hard' / 'hardest'; not in the reference, off unless asked for) has
+train() choose every triplet's negative from the model's current facial IDs.
+fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
 The reconstruction model (`create_face_reconst_model`, fi.py:1155-1488) is ReconModel over fv_recon_forward; the
@@ -40,6 +42,7 @@ from .model import Model
 from .weights import NUM_BASE_LAYERS
 
 ALPHA = 0.2                     # fi.py:66
+TRIPLET_MARGIN = ALPHA          # the loss's margin is the mining band's width: one number
 DENSE1_DIM = 64                 # the loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76)
 RESOURCE_TYPE_UCCS = 'uccs'
 RESOURCE_TYPE_VGGFACE2 = 'vggface2'
@@ -639,6 +642,107 @@ def fid_pair_dists(ctx, ids, blocks, thresholds, n_dists=None, counts=None):
     return (None if dists is None else dists[:int(n_dists)]), counts
 
 
+# ----------------------------------------------------------------------------- triplet mining
+MINING_MODES = {'semi_hard': 0, 'hardest': 1}                 # fv_fid_mine_negatives' mode
+MINE_PB = 8                      # FV_MINE_PB of include/fv_hotpath.h: positives of one anchor that share a scan of the rows
+# fv_fid_mine_negatives' kind: a negative inside the margin band, one at or nearer than the positive, one beyond the band, none
+KIND_SEMI_HARD, KIND_VIOLATING, KIND_EASY, KIND_NONE = 0, 1, 2, 3
+
+
+def mining_mode(hps):
+    """hps['triplet_mining'] -> None (absent, None or 'none': the reference's triplets) or 'semi_hard' / 'hardest'; ValueError for
+    anything else, and for a hps['mining_every'] that is not an int >= 1.  Needs no device."""
+    mode = hps.get('triplet_mining')
+    if mode is None or mode == 'none':
+        return None
+    if mode not in MINING_MODES:
+        raise ValueError('fi_conf.hps.triplet_mining %r is not valid (available: none, %s)' % (mode, ', '.join(sorted(MINING_MODES))))
+    every = hps.get('mining_every', 1)
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError('fi_conf.hps.mining_every must be an int >= 1, got %r' % (every,))
+    return mode
+
+
+def refuse_mining_on_ranks(hps, ranks):
+    """Mining on more than one rank is not served: every rank would have to train on the same mined list (ranks that cut it
+    differently skip different batches and hang in a collective), which needs a broadcast and a run on two GPUs to prove."""
+    if int(ranks) > 1 and mining_mode(hps) is not None:
+        raise NotImplementedError('fi_conf.hps.triplet_mining with multi_gpu and %d ranks is not implemented: train on one GPU, '
+                                  'or without mining' % int(ranks))
+
+
+def subject_codes(subject_ids):
+    """Subject ids of a db (ints for UCCS, strings for VGGFace2) -> int32 codes for fv_fid_mine_negatives: -1 stays -1 (an unknown
+    identity), every other id gets the position of its first appearance."""
+    code, out = {}, np.empty(len(subject_ids), np.int32)
+    for k, sid in enumerate(subject_ids):
+        if not isinstance(sid, str) and sid == -1:
+            out[k] = -1
+        else:
+            out[k] = code.setdefault(sid, len(code))
+    return out
+
+
+def triplet_groups(pairs, sort=False):
+    """(anchor slot, positive slot) pairs -> (anchors, pos_off, positives, order), fv_fid_mine_negatives' group table: every run
+    of consecutive equal anchors is one group (an anchor that recurs later starts another).  Output j of the operator belongs to
+    pairs[order[j]].  sort: the pairs are first ordered by anchor (stably), so that every anchor is one group whatever the order
+    of the list -- the operator's outputs do not depend on the grouping, only its time does."""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    order = np.argsort(pairs[:, 0], kind='stable') if sort else np.arange(len(pairs))
+    a, p = pairs[order, 0], pairs[order, 1]
+    starts = np.flatnonzero(np.concatenate([[True], a[1:] != a[:-1]])) if len(a) else np.zeros(0, np.int64)
+    pos_off = np.concatenate([starts, [len(a)]]).astype(np.int32)
+    return a[starts].astype(np.int32), pos_off, p.astype(np.int32), order.astype(np.int64)
+
+
+def mined_rows(pairs_labels, neg_slot, kind, labels, drop_easy):
+    """The triplet rows -- (anchor, positive, negative) labels -- train() cuts into batches: pair k of pairs_labels with the
+    label of slot neg_slot[k]; a pair without a negative (KIND_NONE) is left out, with drop_easy also one whose negative lies
+    beyond the margin (KIND_EASY: loss 0, gradient 0)."""
+    out = []
+    for (a, p), n, k in zip(pairs_labels, neg_slot, kind):
+        if k == KIND_NONE or (drop_easy and k == KIND_EASY):
+            continue
+        out.append((a, p, labels[int(n)]))
+    return out
+
+
+def fid_mine_negatives(ctx, ids, subjects, anchors, pos_off, positives, margin=TRIPLET_MARGIN, mode='semi_hard'):
+    """fv_fid_mine_negatives: ids (n, 64) float32 and subjects (n,) int32 CUDA tensors, the group table anchors (g,), pos_off
+    (g + 1,), positives (t,) int32 on the host -> (neg_index int32, kind int32, d_ap float64, d_an float64) CUDA tensors of t
+    (stream-ordered).  mode: 'semi_hard' / 'hardest' (or 0 / 1)."""
+    if not torch.is_tensor(ids) or ids.dtype != torch.float32 or ids.dim() != 2 or ids.shape[1] != DENSE1_DIM:
+        raise ValueError('fid_mine_negatives expects float32 (n, 64) ids')
+    if not torch.is_tensor(subjects) or subjects.dtype != torch.int32 or subjects.shape != (ids.shape[0],):
+        raise ValueError('fid_mine_negatives expects int32 (n,) subjects, one per row of ids')
+    table = []
+    for name, v in (('anchors', anchors), ('pos_off', pos_off), ('positives', positives)):
+        v = np.asarray(v)
+        if v.dtype != np.int32 or v.ndim != 1:
+            raise ValueError('fid_mine_negatives expects a one-dimensional int32 array as %s' % name)
+        table.append(np.ascontiguousarray(v))
+    a, off, pos = table
+    if len(off) != len(a) + 1:
+        raise ValueError('fid_mine_negatives expects one offset per group and one more (%d groups, %d offsets)' % (len(a), len(off)))
+    mode = MINING_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(mode, bool) or not isinstance(mode, int):
+        raise ValueError('fid_mine_negatives: mode %r (available: %s)' % (mode, ', '.join(sorted(MINING_MODES))))
+    if not ids.is_cuda or subjects.device != ids.device or ids.device.index != ctx.device:
+        raise ValueError('fid_mine_negatives expects ids and subjects on the context\'s device (cuda:%d)' % ctx.device)
+    x, sub = ids.contiguous(), subjects.contiguous()
+    t = len(pos)
+    neg = torch.empty(t, dtype=torch.int32, device=x.device)
+    kind = torch.empty(t, dtype=torch.int32, device=x.device)
+    d_ap = torch.empty(t, dtype=torch.float64, device=x.device)
+    d_an = torch.empty(t, dtype=torch.float64, device=x.device)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    ctx.check(lib().fv_fid_mine_negatives(ctx.handle, ptr(x), ptr(sub), int(x.shape[0]), a.ctypes.data_as(i32p),
+                                          off.ctypes.data_as(i32p), len(a), pos.ctypes.data_as(i32p), t, float(margin), mode,
+                                          ptr(neg), ptr(kind), ptr(d_ap), ptr(d_an)), 'fv_fid_mine_negatives')
+    return neg, kind, d_ap, d_an
+
+
 def letterbox_crops(ctx, images, crops, image_size, out=None):
     """fv_letterbox_crops: images = (device uint8 buffer, offsets, hw) of a batch (letterbox_batch_device's `keep`), crops = list
     of (image index, y0, x0, rows, cols) -> (n, S, S, 3) float32 CUDA tensor."""
@@ -1020,6 +1124,8 @@ class FaceIdentifier(object):
         # multi_gpu: one process per GPU (main() starts them); a FaceIdentifier made in a process without WORLD_SIZE is one rank
         self.world = int(os.environ.get('WORLD_SIZE', 1)) if self.conf.get('multi_gpu') else 1
         self.rank = int(os.environ.get('RANK', 0)) if self.world > 1 else 0
+        self.mining = mining_mode(self.hps)          # ValueError for a value that is not served, before a device is touched
+        self.last_mining = None
         if device is None:           # FV_DEVICE: several ranks on ONE device, to rehearse N > 1 on a one-GPU box (gloo transport)
             device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
         self.model = FidModel(self.image_size, device)
@@ -1096,14 +1202,15 @@ class FaceIdentifier(object):
         With more than one rank (multi_gpu): rank 0 builds, shuffles and pickles the triplet list and the others read it; every
         rank walks the same batch order and trains on its slice of each batch (slice_triplets) through
         parallel.DataParallelTrainer; a batch with fewer triplets than ranks is skipped on all ranks; rank 0 prints the loss of
-        the merged batches and saves the model."""
+        the merged batches and saves the model.
+        hps['triplet_mining'] ('semi_hard' / 'hardest'; one rank only): at the start of every epoch e with e % hps['mining_every']
+        == 0 (default 1) the negatives are mined anew (mine_triplets; hps['mining_drop_easy'], default true, leaves out the
+        triplets whose loss is already 0) and one line is printed; the epoch's batches are cut from the mined rows as rows()
+        cuts the sequence's list, and min(hps['step'], batches) of them run in shuffled order.  The pickle stays the reference's
+        list.  Without the key nothing here differs from the above."""
         from .parallel import DataParallelTrainer
-        if self.conf['resource_type'] == RESOURCE_TYPE_UCCS:
-            sequence = self.TrainingSequence
-        elif self.conf['resource_type'] == RESOURCE_TYPE_VGGFACE2:
-            sequence = self.TrainingSequenceVGGFace2
-        else:
-            raise ValueError('resource type is not valid.')
+        refuse_mining_on_ranks(self.hps, self.world)
+        sequence = self._sequence()
         trainer = DataParallelTrainer(self.model, world_size=self.world, rank=self.rank)
         # one triplet list for all ranks: rank 0 writes the pickle, the others load it once it is complete
         if self.rank == 0:
@@ -1117,10 +1224,17 @@ class FaceIdentifier(object):
         # one rank: the global numpy stream, as before; several: one seeded generator, the same batch order on every rank
         rng = np.random.default_rng(0) if self.world > 1 else np.random
         try:
+            batch_rows, n_batches = tr_gen.rows, len(tr_gen)
             for e in range(epochs):
                 losses = []
-                order = [int(i) for i in rng.permutation(len(tr_gen))[:steps]]
-                parts = [slice_triplets(tr_gen.rows(i), self.world, self.rank) for i in order]
+                if self.mining is not None and e % int(h.get('mining_every', 1)) == 0:
+                    mined, _ = self.mine_triplets(bool(h.get('mining_drop_easy', True)), tr_gen, inputs)
+                    bs, c = tr_gen.batch_size, self.last_mining['counts']
+                    print('Mining (%s) - semi-hard: %d, violating: %d, easy: %d, no negative: %d - %.3fs'
+                          % (self.mining, c[0], c[1], c[2], c[3], self.last_mining['seconds']))
+                    batch_rows, n_batches = (lambda i, mined=mined, bs=bs: mined[i * bs:(i + 1) * bs]), num_batches(len(mined), bs)
+                order = [int(i) for i in rng.permutation(n_batches)[:steps]]
+                parts = [slice_triplets(batch_rows(i), self.world, self.rank) for i in order]
                 # crop_store: this epoch's inputs come from the store, in step order (per batch: the next one decodes meanwhile)
                 feed = None if inputs is None else inputs.batches([part[0] for part in parts if part is not None])
                 for i, part in zip(order, parts):
@@ -1145,6 +1259,61 @@ class FaceIdentifier(object):
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
         trainer.shutdown()
+
+    # ------------------------------------------------------------------ triplet mining
+    def _sequence(self):
+        if self.conf['resource_type'] == RESOURCE_TYPE_UCCS:
+            return self.TrainingSequence
+        if self.conf['resource_type'] == RESOURCE_TYPE_VGGFACE2:
+            return self.TrainingSequenceVGGFace2
+        raise ValueError('resource type is not valid.')
+
+    def _db_ids(self, tr_gen, inputs):
+        """Facial IDs (n, 64), on the device, of every row of the sequence's db in list(tr_gen.db.index) order, inference mode, in
+        chunks of at most Engine.max_infer_batch(S) crops.  A resident TripletInputs: gathered from its store (nothing is decoded
+        again); otherwise decoded through _extract_from_store, or on the host when hps['crop_store'] is off."""
+        from .crop_store import RESIDENT
+        from .engine import Engine
+        m, labels = self.model, list(tr_gen.db.index)
+        n, step = len(labels), max(1, Engine.max_infer_batch(self.image_size))
+        if inputs is not None and inputs.tier == RESIDENT:
+            ids = [m.extract_device(inputs.store.gather([inputs.slot_of[label] for label in labels[i:i + step]]))
+                   for i in range(0, n, step)]
+        elif self.hps.get('crop_store', CROP_STORE_DEFAULT):
+            ids = self._extract_from_store([tr_gen.path(label) for label in labels], step)
+        else:
+            ids = [m.extract_device(np.asarray([_imread(tr_gen.path(label)) for label in labels[i:i + step]]))
+                   for i in range(0, n, step)]
+        return torch.cat(ids)
+
+    def mine_triplets(self, drop_easy=False, tr_gen=None, inputs=None):
+        """Every (anchor, positive) pair of the sequence's triplet list, in the list's order, with the negative the current model
+        asks for (fv_fid_mine_negatives with hps['triplet_mining'], 'semi_hard' where that is off; margin TRIPLET_MARGIN) instead
+        of the reference's random one -> (rows, kinds): the (anchor, positive, negative) label triples of mined_rows and, aligned
+        with them, each row's kind (KIND_*).  Pairs whose anchor has subject -1 are left out: unknown identities are not known to
+        be one person.  self.last_mining holds the number of pairs of each kind before anything was dropped, and the wall time.
+        tr_gen / inputs: train()'s sequence and TripletInputs; alone, the sequence is built here (the pickle is read when there
+        is one, written otherwise) and the crops are decoded through a store of their own."""
+        t0 = time.time()
+        if tr_gen is None:
+            sequence = self._sequence()
+            tr_gen = sequence(self.raw_data_path, dict(self.hps), self.nn_arch, load_flag=os.path.exists(sequence.PICKLE_FILE))
+        m = self.model
+        labels = list(tr_gen.db.index)
+        slot_of = {label: k for k, label in enumerate(labels)}
+        subjects = subject_codes(list(tr_gen.db['subject_id']))
+        pairs = [(t[0], t[1]) for t in tr_gen.img_triplet_pairs if subjects[slot_of[t[0]]] >= 0]
+        ids = self._db_ids(tr_gen, inputs)
+        slots = np.asarray([(slot_of[a], slot_of[p]) for a, p in pairs], np.int64).reshape(-1, 2)
+        anchors, pos_off, positives, order = triplet_groups(slots, sort=True)
+        neg, kind, _dap, _dan = fid_mine_negatives(m.ctx, ids, torch.from_numpy(subjects).to(m.dev), anchors, pos_off, positives,
+                                                   TRIPLET_MARGIN, self.mining or 'semi_hard')
+        neg_of, kind_of = np.empty(len(pairs), np.int32), np.empty(len(pairs), np.int32)
+        neg_of[order], kind_of[order] = neg.cpu().numpy(), kind.cpu().numpy()
+        rows = mined_rows(pairs, neg_of, kind_of, labels, drop_easy)
+        kinds = kind_of[(kind_of != KIND_NONE) & ~(bool(drop_easy) & (kind_of == KIND_EASY))]
+        self.last_mining = dict(counts=[int((kind_of == k).sum()) for k in range(4)], seconds=time.time() - t0)
+        return rows, kinds
 
     # ------------------------------------------------------------------ facial-ID database (fi.py:645-770)
     def _extract_db(self):
@@ -1398,6 +1567,7 @@ def main():
         return
     if mode == 'train':
         n = int(conf['fi_conf'].get('num_gpus', 1)) if conf['fi_conf'].get('multi_gpu') else 1
+        refuse_mining_on_ranks(conf['fi_conf'].get('hps', {}), n)         # before a rank is started
         if n > 1 and 'WORLD_SIZE' not in os.environ:
             # multi_gpu_model(model, gpus=num_gpus) (fi.py:348-361) is one process driving num_gpus towers; here it is one process
             # per GPU, started from this one BEFORE it makes any GPU call -- the reference's command line stays what it was

@@ -542,6 +542,30 @@ typedef struct {
 } fv_pair_block;
 int fv_fid_pair_dists(fv_ctx* ctx, const float* ids, int64_t n_ids, const fv_pair_block* blocks, int n_blocks,
                       const float* thresholds, int n_th, float* dists, int64_t n_dists, int64_t* counts);
+/* Triplet negatives mined from the current facial IDs (semi-hard mining, FaceNet section 3.2; the reference draws its negatives
+ * at random, once).  ids [n][64] float32 and subjects [n] int32 (device; ids 16-byte aligned).  The triplets are a group table on
+ * the host: anchors [g], pos_off [g + 1] ascending from 0 to t, positives [t]; triplet j of group q is (anchors[q], positives[j])
+ * for pos_off[q] <= j < pos_off[q + 1].  Outputs (device, one per triplet): neg_index int32, kind int32, d_ap and d_an float64.
+ *   D(i, r) = sqrt of the fp64 sum, in dimension order 0..63, of the squared fp64 differences (fv_fid_match's numerics);
+ *   dap = D(a, p);  hi = dap + margin (one fp64 add);  row r is eligible for anchor a iff subjects[r] >= 0 and subjects[r] !=
+ *   subjects[a];  a row whose D(a, r) is NaN belongs to no class.
+ *   mode 0 (semi-hard): the first class that is not empty --
+ *     kind 0  eligible rows with dap < D < hi:  the minimum of (D, r);
+ *     kind 1  eligible rows with D <= dap:      the largest D, the lowest r among equals (the mildest violating negative);
+ *     kind 2  eligible rows with D >= hi:       the minimum of (D, r);
+ *     kind 3  none, or dap is NaN:              neg_index -1, d_an +inf.
+ *   mode 1 (hardest): the minimum of (D, r) over the eligible rows whose D is not NaN; kind says by the same three inequalities
+ *     where that row fell; kind 3 as above.
+ * d_ap is dap (one quiet NaN, sign and payload clear, when it is NaN); d_an is the chosen row's D.  Every choice is an extremum
+ * under a total order: a triplet's outputs depend on ids, subjects, a, p, margin and mode alone, not on the grouping, the launch
+ * split or the other triplets.  No atomics.  A group longer than FV_MINE_PB positives is served in parts of that many, each part
+ * one scan of the rows.  The whole table is checked before anything is enqueued: n < 1, t < 0, an index outside [0, n), offsets
+ * that do not ascend from 0 to t, a mode other than 0 / 1 or a margin that is not finite and > 0 is FV_ERR_INVALID and leaves
+ * the outputs untouched.  t == 0 writes nothing.  Returns after the table has been uploaded (the call waits for the stream once). */
+#define FV_MINE_PB 8
+int fv_fid_mine_negatives(fv_ctx* ctx, const float* ids, const int32_t* subjects, int n, const int32_t* anchors,
+                          const int32_t* pos_off, int g, const int32_t* positives, int t, double margin, int mode,
+                          int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an);
 
 /* ------------------------------------------------------------------ FaceIdentifier: the reconstruction model
  * create_face_reconst_model (fi.py:1155-1488): a facial ID [64] back through the network to an image [S][S][3].
