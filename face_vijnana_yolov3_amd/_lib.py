@@ -150,6 +150,9 @@ def _declare(L):
         'fv_fid_dense_l2': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, vp]),
         'fv_fid_towers_dense_l2': (i32, [vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
         'fv_fid_triplet_loss_grad': (i32, [vp, vp, vp, i32, f64, vp, vp, vp]),
+        'fv_fid_batch_triplet_loss_grad': (i32, [vp, vp, vp, vp, i32, f64, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'fv_fid_batch_workspace_bytes': (sz, [i32, i32]),
+        'fv_fid_batch_train_step': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         'fv_fid_towers_dense_dgrad': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i32]),
         'fv_fid_towers_dense_wgrad': (i32, [vp, vp, vp, vp, i32, vp, i32, i64, vp]),
         'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),

@@ -13,7 +13,7 @@ batch decoded by a loader thread while this one trains."""
 import numpy as np
 import torch
 
-RESIDENT, PER_BATCH = 'resident', 'per_batch'
+RESIDENT, PER_BATCH, HOST = 'resident', 'per_batch', 'host'
 LOAD_CHUNK_BYTES = 64 << 20      # decoded RGB per chunk of CropStore.load (123 crops at 416; the coefficients take 1-2x as much)
 
 
@@ -152,21 +152,25 @@ class TripletInputs(object):
     """The inputs of FaceIdentifier.train()'s steps from a CropStore.  path_of: label -> file; labels: every label a triplet
     may name.  Build it once the training workspace exists (store_budget)."""
 
-    def __init__(self, ctx, device, image_size, labels, path_of, batch_size, budget_bytes, threads):
+    def __init__(self, ctx, device, image_size, labels, path_of, batch_size, budget_bytes, threads, slots=None, tier=None):
+        """slots: crops one batch may hold in the per-batch tier (default: the 3 * batch_size of a triplet batch).  tier=HOST: no
+        store at all -- crop_batches reads the files on the host, as the sequence's load() does (hps['crop_store'] off)."""
         from concurrent.futures import ThreadPoolExecutor
         from .postproc import PinnedRing
         self.ctx, self.dev, self.S, self.path_of = ctx, device, int(image_size), path_of
-        self.tier = plan_store(len(labels), image_size, budget_bytes)
+        self.tier = plan_store(len(labels), image_size, budget_bytes) if tier is None else tier
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(threads)))
         try:
-            if self.tier == RESIDENT:
+            if self.tier == HOST:
+                pass
+            elif self.tier == RESIDENT:
                 self.slot_of = {label: k for k, label in enumerate(labels)}
                 self.store = CropStore(ctx, len(labels), image_size, device)
                 self.store.load([path_of(label) for label in labels], list(range(len(labels))), self.pool)
             else:
                 check_sizes([path_of(label) for label in labels], image_size, self.pool)
                 ring = PinnedRing(2)
-                self.stores = [CropStore(ctx, 3 * int(batch_size), image_size, device, ring) for _ in range(2)]
+                self.stores = [CropStore(ctx, 3 * int(batch_size) if slots is None else int(slots), image_size, device, ring) for _ in range(2)]
         except Exception:
             self.close()
             raise
@@ -185,19 +189,47 @@ class TripletInputs(object):
                 idx = [self.slot_of[t[c]] for c in range(3) for t in rows]
                 yield self._split(self.store.gather(idx), len(rows))
             return
-        from concurrent.futures import ThreadPoolExecutor
 
         def decode(k):
             unique, ia, ip, in_ = batch_slots(batches_of_rows[k])
             store = self.stores[k % 2]
             return store.decode([self.path_of(label) for label in unique], list(range(len(unique))), self.pool), (ia, ip, in_)
+        for store, idx, rows in self._ring_batches(decode, batches_of_rows):
+            yield self._split(store.gather(np.concatenate(idx)), len(rows))
+
+    def crop_batches(self, batches_of_labels):
+        """Generator: one [n][S][S][3] tensor per batch of labels (distinct within a batch), in order, for a step that embeds
+        every crop once.  Resident: one fv_gather_u8_f32; per batch: the two ring stores, the next batch decoding meanwhile;
+        HOST: the files read on the host, uint8 (the model divides by 255, the same floats)."""
+        if self.tier == HOST:
+            from .face_identification import _imread
+            for batch in batches_of_labels:
+                yield np.asarray([_imread(self.path_of(label)) for label in batch])
+            return
+        if self.tier == RESIDENT:
+            for batch in batches_of_labels:
+                yield self.store.gather([self.slot_of[label] for label in batch])
+            return
+
+        def decode(k):
+            batch = batches_of_labels[k]
+            if len(batch) > self.stores[k % 2].data.shape[0]:
+                raise ValueError('a batch of %d crops, the per-batch stores hold %d' % (len(batch), self.stores[k % 2].data.shape[0]))
+            return self.stores[k % 2].decode([self.path_of(label) for label in batch], list(range(len(batch))), self.pool), len(batch)
+        for store, n, _batch in self._ring_batches(decode, batches_of_labels):
+            yield store.gather(np.arange(n, dtype=np.int32))
+
+    def _ring_batches(self, decode, batches):
+        """Generator over the per-batch tier: decode(k) runs on a loader thread one batch ahead -> (the store batch k was staged
+        in, what decode returned beside the decoded chunk, batches[k])."""
+        from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=1) as one:          # one-deep prefetch, as FaceDetector._detect_files
-            pending = one.submit(decode, 0) if batches_of_rows else None
-            for k, rows in enumerate(batches_of_rows):
-                decoded, idx = pending.result()
-                if k + 1 < len(batches_of_rows):
+            pending = one.submit(decode, 0) if batches else None
+            for k, rows in enumerate(batches):
+                decoded, more = pending.result()
+                if k + 1 < len(batches):
                     pending = one.submit(decode, k + 1)
                 # store k % 2 was last read by the gather of batch k - 2, enqueued on this stream before this staging
                 store = self.stores[k % 2]
                 store.stage(decoded)
-                yield self._split(store.gather(np.concatenate(idx)), len(rows))
+                yield store, more, rows

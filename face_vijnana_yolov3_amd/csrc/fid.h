@@ -11,6 +11,29 @@ constexpr int FID_KC = 256;    // F per forward partial: fixed, so a row's summa
 // maps [per][F] read (written) in place, tower-major.
 struct FidRows { float* p[3]; int per; };
 
+// wave-wide fp64 sum (butterfly), the value of lane 0 broadcast so that every lane holds the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return __shfl(v, 0);
+}
+
+// d pre of one row from d u: back through l2_normalize (the rsqrt factor s is a constant where sum x^2 <= 1e-12) and ReLU (TF's
+// ReluGrad: passes only where pre > 0).  `weight` multiplies the fp64 result once, where it is rounded to float: a power of two
+// scales the stored value exactly.
+__device__ __forceinline__ float l2_relu_bwd(float y, double du, double weight) {
+    const double r = y > 0.f ? (double)y : 0.0;
+    const double ss = wave_sum(r * r);
+    double dr;
+    if (ss > 1e-12) {
+        const double s = 1.0 / sqrt(ss), uu = r * s;
+        dr = s * (du - uu * wave_sum(uu * du));
+    } else {
+        dr = du * 1e6;
+    }
+    return y > 0.f ? (float)(dr * weight) : 0.f;
+}
+
 inline long long fv_fid_chunks(long long F) { return F / FID_KC; }
 // part [F / FID_KC][M][64]: per-chunk partial products of X . W
 int fv_fid_dense_fwd(fv_ctx* ctx, FidRows X, int M, long long F, const float* W, float* part);
@@ -19,6 +42,13 @@ int fv_fid_dense_finish(fv_ctx* ctx, const float* part, long long chunks, int M,
 // triplet loss over B triplets (rows b, B + b, 2B + b of pre / u): loss = their unweighted mean; dE [3B][64] = loss_weight *
 // dL / d pre, dbias [64] = its column sums.  loss_weight must be finite and > 0.
 int fv_fid_triplet(fv_ctx* ctx, const float* pre, const float* u, int B, float* loss, float* dE, float* dbias, double loss_weight);
+// batch triplet loss over M labelled rows (fid_batch.hip): every row of a known subject is an anchor with its hardest positive and a
+// mined negative of the batch (mode 0: the nearest, 1: semi-hard); include/fv_hotpath.h, fv_fid_batch_triplet_loss_grad, has the
+// contract.  1 <= M <= FID_BATCH_MAX; u 16-byte aligned.
+constexpr int FID_BATCH_MAX = 1024;
+int fv_fid_batch_triplet(fv_ctx* ctx, const float* pre, const float* u, const int32_t* subjects, int M, double margin, int mode,
+                         double loss_weight, float* loss, float* dE, float* dbias, int32_t* pos_index, int32_t* neg_index, int32_t* kind,
+                         double* d_ap, double* d_an);
 // dX = dE . W^T, written (not added) into the rows of dX
 int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const float* W, FidRows dX);
 // The reconstruction model's head: u [M][64] = relu(l2_normalize(ids)), x [M][F] = u . W^T + bias (W the dense kernel [F][64])

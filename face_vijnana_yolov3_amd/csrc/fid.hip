@@ -63,13 +63,6 @@ __global__ __launch_bounds__(256) void fid_dense_fwd_kernel(FidRows X, int M, lo
     }
 }
 
-// wave-wide fp64 sum (butterfly), the value of lane 0 broadcast so that every lane holds the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return __shfl(v, 0);
-}
-
 // one workgroup per row: wave g sums the partials of chunks [g * n / 16, (g + 1) * n / 16) in order (fp64), wave 0 adds the 16 sums
 // in wave order, + bias, ReLU, x * rsqrt(max(sum x^2, 1e-12)) (TF 1.13 l2_normalize).  The order depends on the chunk count alone.
 constexpr int FIN_WAVES = 16;
@@ -94,22 +87,6 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void fid_dense_finish_kernel(const 
     const double inv = 1.0 / sqrt(ss > 1e-12 ? ss : 1e-12);
     if (pre) pre[(long long)m * FID_DIM + n] = y;
     u[(long long)m * FID_DIM + n] = (float)((double)r * inv);
-}
-
-// d pre of one row from d u: back through l2_normalize (the rsqrt factor s is a constant where sum x^2 <= 1e-12) and ReLU (TF's
-// ReluGrad: passes only where pre > 0).  `weight` multiplies the fp64 result once, where it is rounded to float: a power of two
-// scales the stored value exactly.
-__device__ __forceinline__ float l2_relu_bwd(float y, double du, double weight) {
-    const double r = y > 0.f ? (double)y : 0.0;
-    const double ss = wave_sum(r * r);
-    double dr;
-    if (ss > 1e-12) {
-        const double s = 1.0 / sqrt(ss), uu = r * s;
-        dr = s * (du - uu * wave_sum(uu * du));
-    } else {
-        dr = du * 1e6;
-    }
-    return y > 0.f ? (float)(dr * weight) : 0.f;
 }
 
 // Triplet loss mean_b max(|a - p| - |a - n| + 0.2, 0) (fi.py:72-76) and its gradient.  Wave w takes the triplets b = w, w + 4, ...

@@ -52,6 +52,20 @@ TrainWs make_train(void* base, int B, int S) {
     return w;
 }
 
+// One training plan over the M images of a labelled batch, then the dense layer's M rows and the loss's selection.
+struct BatchWs { Plan t; float *part, *pre, *u, *dE; size_t bytes; };
+BatchWs make_batch(void* base, int M, int S) {
+    BatchWs w{};
+    w.t = make_plan(base, M, S, true);
+    Carver c = carver_at(base, w.t.bytes);
+    w.part = c.take((size_t)fv_fid_chunks(feat_floats(S)) * M * FID_DIM);
+    w.pre = c.take((size_t)M * FID_DIM);
+    w.u = c.take((size_t)M * FID_DIM);
+    w.dE = c.take((size_t)M * FID_DIM);
+    w.bytes = c.off;
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -64,6 +78,11 @@ int64_t fv_fid_param_count(int image_size) {
 size_t fv_fid_workspace_bytes(int batch, int image_size, int training) {
     if (batch < 1 || image_size < 32 || image_size % 32) return 0;
     return training ? make_train(nullptr, batch, image_size).bytes : make_extract(nullptr, batch, image_size).bytes;
+}
+
+size_t fv_fid_batch_workspace_bytes(int M, int image_size) {
+    if (M < 1 || M > FID_BATCH_MAX || image_size < 32 || image_size % 32) return 0;
+    return make_batch(nullptr, M, image_size).bytes;
 }
 
 int64_t fv_fid_dense_partial_floats(int rows, int64_t F) {
@@ -171,6 +190,53 @@ int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, cons
         if (int rc = pipe.finish()) return rc;
     }
     return FV_OK;
+}
+
+int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* subjects, int M,
+                            int image_size, int mode, double margin, void* workspace, size_t workspace_bytes, float* grads, float* loss,
+                            int32_t* pos_index, int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, params && bn_state && x && subjects && workspace && grads && loss && pos_index && neg_index && kind && d_ap && d_an,
+               "fid_batch_train_step: NULL buffer");
+    FV_REQUIRE(ctx, M <= FID_BATCH_MAX, "fid_batch_train_step: M %d beyond the loss's %d rows", M, FID_BATCH_MAX);
+    FV_REQUIRE(ctx, mode == 0 || mode == 1, "fid_batch_train_step: mode %d (0 batch hard, 1 batch semi-hard)", mode);
+    FV_REQUIRE(ctx, std::isfinite(margin) && margin > 0.0, "fid_batch_train_step: margin %g is not finite and > 0", margin);
+    if (int rc = check_batch(ctx, "fid_batch_train_step", M, image_size)) return rc;
+    BatchWs w = make_batch(workspace, M, image_size);
+    if (w.bytes > workspace_bytes)
+        return fv_fail(ctx, FV_ERR_WORKSPACE, "fid_batch_train_step: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    Plan& p = w.t;
+    TailLend lend(ctx, p.tail, p.tail_floats);
+    EmaReset ema_reset{ctx};   // the one update of the moving statistics is update ctx->bn_ema_step, as the caller set it
+    const Net& N = net();
+    const long long F = feat_floats(image_size);
+    const int64_t dense_off = base_param_count();
+
+    FV_HIP(ctx, hipMemsetAsync(grads, 0, (size_t)fv_fid_param_count(image_size) * sizeof(float), ctx->stream));
+    FV_HIP(ctx, hipMemsetAsync(p.k.slots[0], 0, p.k.slots_bytes, ctx->stream));
+    if (int rc = fv_ew_pad_rows(ctx, params + N.L[0].w_off, p.w0p, 32, 27, 32)) return rc;
+    if (int rc = transpose_weights(ctx, N.L, params, p.k.wt, HEAD_PAD)) return rc;
+
+    // accumulate_bn as fv_fid_train_step sets it: d-beta / d-gamma are added to the zeroed vector
+    const Train t{ctx, N.L, p.k, M, image_size, params, bn_state, grads, true};
+    const float* cur = x;
+    const float* skip = nullptr;
+    for (int l = 0; l < NB; ++l) {
+        const auto& d = N.L[l];
+        if (d.role == 1) skip = cur;
+        if (int rc = train_bn_forward(t, l, cur, l == 0 ? p.w0p : params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
+        cur = p.k.a[l];
+    }
+    const FidRows X{{p.k.a[NB - 1], nullptr, nullptr}, M};
+    if (int rc = fv_fid_dense_fwd(ctx, X, M, F, params + dense_off, w.part)) return rc;
+    if (int rc = fv_fid_dense_finish(ctx, w.part, fv_fid_chunks(F), M, params + dense_off + F * FID_DIM, w.pre, w.u)) return rc;
+    if (int rc = fv_fid_batch_triplet(ctx, w.pre, w.u, subjects, M, margin, mode, 1.0, loss, w.dE, grads + dense_off + F * FID_DIM,
+                                      pos_index, neg_index, kind, d_ap, d_an)) return rc;
+    if (int rc = fv_fid_dense_wgrad(ctx, X, w.dE, M, F, grads + dense_off)) return rc;
+    if (int rc = fv_fid_dense_dgrad(ctx, w.dE, M, F, params + dense_off, FidRows{{p.G[0], nullptr, nullptr}, M})) return rc;
+    WgradPipe pipe(t, nullptr, nullptr, p.G[2], p.G[3]);
+    if (int rc = base_backward(pipe, NB, x, p.G, {}, false)) return rc;
+    return pipe.finish();
 }
 
 }  // extern "C"

@@ -322,6 +322,14 @@ int fv_fid_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, int 
     return fv_fid_triplet(ctx, pre, u, B, loss, dE, dbias, grad_weight);
 }
 
+int fv_fid_batch_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, const int32_t* subjects, int M, double margin,
+                                   int mode, double loss_weight, float* loss, float* dE, float* dbias, int32_t* pos_index,
+                                   int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an) {
+    if (!ctx) return FV_ERR_INVALID;
+    return fv_fid_batch_triplet(ctx, pre, u, subjects, M, margin, mode, loss_weight, loss, dE, dbias, pos_index, neg_index, kind, d_ap,
+                                d_an);
+}
+
 int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
                               int per) {
     if (!ctx) return FV_ERR_INVALID;

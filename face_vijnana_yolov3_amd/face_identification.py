@@ -6,9 +6,11 @@ variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, f
 (fi.py:994-1153) and `main` (fi.py:1715-1760) for the modes it dispatches, and the data mode (`create_db_fi` /
 `save_extracted_face`, fi.py:78-280) that cuts the face crops and writes the subject db everything else reads.  The hot path is
 the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_gather_u8_f32,
-fv_fid_match, fv_fid_pair_dists, fv_fid_mine_negatives, fv_draw_prims_u8); this module holds the
+fv_fid_match, fv_fid_pair_dists, fv_fid_mine_negatives, fv_fid_batch_train_step, fv_draw_prims_u8); this module holds the
 weights and drives it.  fi_conf.hps['triplet_mining'] ('semi_hard' / 'hardest'; not in the reference, off unless asked for) has
-train() choose every triplet's negative from the model's current facial IDs.
+train() choose every triplet's negative from the model's current facial IDs (DESIGN.md section 21);
+fi_conf.hps['batch_mining'] ('batch_hard' / 'batch_semi_hard'; likewise opt-in) trains on batches of P subjects x K crops through
+one tower and forms the triplets inside each batch.
 fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
@@ -43,6 +45,8 @@ from .weights import NUM_BASE_LAYERS
 
 ALPHA = 0.2                     # fi.py:66
 TRIPLET_MARGIN = ALPHA          # the loss's margin is the mining band's width: one number
+BATCH_MINING_MODES = {'batch_hard': 0, 'batch_semi_hard': 1}   # fv_fid_batch_triplet_loss_grad's mode
+BATCH_MAX_ROWS = 1024           # rows one fv_fid_batch_triplet_loss_grad call takes
 DENSE1_DIM = 64                 # the loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76)
 RESOURCE_TYPE_UCCS = 'uccs'
 RESOURCE_TYPE_VGGFACE2 = 'vggface2'
@@ -145,6 +149,55 @@ class FidModel(Model):
 
     def train_on_batch(self, xa, xp, xn, lr, beta_1, beta_2, decay=0.0):
         loss = self.forward_backward(xa, xp, xn)
+        self.adam_step(lr, beta_1, beta_2, decay)
+        return loss
+
+    # ------------------------------------------------------------------ training on a labelled batch
+    def _batch_workspace(self, M):
+        """The workspace of fv_fid_batch_train_step, under a key of its own: the triplet step's and extraction's stay.  One buffer,
+        grown to the largest batch so far (a PK batch is short where a subject has fewer than K crops)."""
+        n = int(lib().fv_fid_batch_workspace_bytes(M, self.image_size))
+        if n == 0:
+            raise FvError('unsupported batch/image_size %r' % ((M, self.image_size),))
+        key = (0, self.image_size, 'labelled_batch')
+        if key not in self._ws or self._ws[key].numel() < n:
+            self._ws.pop(key, None)
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
+        return self._ws[key]
+
+    def forward_backward_batch(self, x, subjects, mode='batch_hard', margin=None):
+        """One tower over the labelled batch x (M,S,S,3), subjects (M,) int32 (< 0: an unknown identity), triplets mined inside
+        the batch (fv_fid_batch_train_step; mode 'batch_hard' / 'batch_semi_hard' or 0 / 1; margin: TRIPLET_MARGIN): gradients
+        in self.grads, ONE update of the BN moving statistics; returns the loss as a 1-element CUDA tensor (no host sync).
+        self.batch_selection keeps pos_index, neg_index, kind (int32), d_ap, d_an (float64), CUDA tensors of M."""
+        self.ensure_optimizer()
+        x = self._as_input(x)
+        M = x.shape[0]
+        sub = torch.as_tensor(np.asarray(subjects) if not torch.is_tensor(subjects) else subjects)
+        sub = sub.to(device=self.dev, dtype=torch.int32).contiguous()
+        if sub.dim() != 1 or sub.shape[0] != M:
+            raise ValueError('forward_backward_batch expects one subject per image (%d images, subjects of shape %r)' % (M, tuple(sub.shape)))
+        if M > BATCH_MAX_ROWS:
+            raise ValueError('forward_backward_batch takes at most %d images, got %d' % (BATCH_MAX_ROWS, M))
+        code = BATCH_MINING_MODES.get(mode, mode)
+        if isinstance(code, bool) or code not in (0, 1):
+            raise ValueError('forward_backward_batch: mode %r (available: %s)' % (mode, ', '.join(sorted(BATCH_MINING_MODES))))
+        ws = self._batch_workspace(M)
+        sel = dict(pos_index=torch.empty(M, dtype=torch.int32, device=self.dev), neg_index=torch.empty(M, dtype=torch.int32, device=self.dev),
+                   kind=torch.empty(M, dtype=torch.int32, device=self.dev), d_ap=torch.empty(M, dtype=torch.float64, device=self.dev),
+                   d_an=torch.empty(M, dtype=torch.float64, device=self.dev))
+        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
+        rc = lib().fv_fid_batch_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), ptr(sub), M, self.image_size,
+                                           int(code), float(TRIPLET_MARGIN if margin is None else margin), ptr(ws), ws.numel(),
+                                           ptr(self.grads), ptr(self._loss), ptr(sel['pos_index']), ptr(sel['neg_index']),
+                                           ptr(sel['kind']), ptr(sel['d_ap']), ptr(sel['d_an']))
+        self.ctx.check(rc, 'fv_fid_batch_train_step')
+        self.bn_updates += 1
+        self.batch_selection = sel
+        return self._loss
+
+    def train_on_labelled_batch(self, x, subjects, mode, lr, beta_1, beta_2, decay=0.0, margin=None):
+        loss = self.forward_backward_batch(x, subjects, mode, margin)
         self.adam_step(lr, beta_1, beta_2, decay)
         return loss
 
@@ -669,6 +722,71 @@ def refuse_mining_on_ranks(hps, ranks):
     if int(ranks) > 1 and mining_mode(hps) is not None:
         raise NotImplementedError('fi_conf.hps.triplet_mining with multi_gpu and %d ranks is not implemented: train on one GPU, '
                                   'or without mining' % int(ranks))
+    # in-batch mining across ranks needs an all-gather of the facial IDs (every anchor sees the merged batch) and two GPUs to prove
+    if int(ranks) > 1 and batch_mining_mode(hps) is not None:
+        raise NotImplementedError('fi_conf.hps.batch_mining with multi_gpu and %d ranks is not implemented: train on one GPU, '
+                                  'or without in-batch mining' % int(ranks))
+
+
+def batch_mining_mode(hps):
+    """hps['batch_mining'] -> None (absent, None or 'none') or 'batch_hard' / 'batch_semi_hard'; ValueError for anything else."""
+    mode = hps.get('batch_mining')
+    if mode is None or mode == 'none':
+        return None
+    if not isinstance(mode, str) or mode not in BATCH_MINING_MODES:
+        raise ValueError('fi_conf.hps.batch_mining %r is not valid (available: none, %s)' % (mode, ', '.join(sorted(BATCH_MINING_MODES))))
+    return mode
+
+
+def _hps_int(hps, key, default, least):
+    v = hps.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+        raise ValueError('fi_conf.hps.%s must be an int >= %d, got %r' % (key, least, v))
+    return int(v)
+
+
+def batch_mining_conf(hps, image_size):
+    """hps -> None (no in-batch mining) or dict(mode, P, K, seed): hps['batch_mining'], pk_crops (K, default 4), pk_subjects (P,
+    default max(2, 3 * batch_size // K): the tower images of the reference's step), pk_seed (default 0).  ValueError for a value
+    that is not served, for batch_mining together with triplet_mining, and for P * K beyond what one call takes at image_size.
+    Needs no device."""
+    mode = batch_mining_mode(hps)
+    if mode is None:
+        return None
+    if mining_mode(hps) is not None:
+        raise ValueError('fi_conf.hps.batch_mining and fi_conf.hps.triplet_mining are two ways to choose the negatives: set one of them')
+    K = _hps_int(hps, 'pk_crops', 4, 2)
+    P = _hps_int(hps, 'pk_subjects', max(2, 3 * int(hps['batch_size']) // K), 2)
+    seed = _hps_int(hps, 'pk_seed', 0, 0)
+    most = min(BATCH_MAX_ROWS, Model.max_infer_batch(image_size))
+    if P * K > most:
+        raise ValueError('fi_conf.hps: pk_subjects * pk_crops = %d images, one step at image_size %d takes at most %d'
+                         % (P * K, int(image_size), most))
+    return dict(mode=mode, P=P, K=K, seed=seed)
+
+
+def pk_batches(codes, P, K, rng):
+    """One epoch of PK batches (FaceNet section 3.2; Hermans et al.): codes: one subject code per db row (subject_codes), rng: a
+    numpy Generator.  The subjects of a code >= 0 with at least 2 rows are shuffled and cut into groups of P (a last group of fewer
+    than 2 subjects is dropped: it has no negatives); of every subject of a group min(K, its rows) rows are drawn without
+    replacement -> lists of db row positions, a subject's rows side by side.  A pure function of its arguments and rng's state."""
+    rows_of = {}
+    for pos, c in enumerate(np.asarray(codes).tolist()):
+        if c >= 0:
+            rows_of.setdefault(c, []).append(pos)
+    eligible = [c for c in sorted(rows_of) if len(rows_of[c]) >= 2]
+    order = rng.permutation(len(eligible))
+    out = []
+    for g in range(0, len(order), int(P)):
+        group = [eligible[j] for j in order[g:g + int(P)]]
+        if len(group) < 2:
+            continue
+        batch = []
+        for c in group:
+            rows = rows_of[c]
+            batch += [rows[j] for j in rng.permutation(len(rows))[:int(K)]]
+        out.append(batch)
+    return out
 
 
 def subject_codes(subject_ids):
@@ -1126,6 +1244,8 @@ class FaceIdentifier(object):
         self.rank = int(os.environ.get('RANK', 0)) if self.world > 1 else 0
         self.mining = mining_mode(self.hps)          # ValueError for a value that is not served, before a device is touched
         self.last_mining = None
+        self.batch_mining = batch_mining_conf(self.hps, self.image_size)       # likewise
+        self.last_batch_mining = None
         if device is None:           # FV_DEVICE: several ranks on ONE device, to rehearse N > 1 on a one-GPU box (gloo transport)
             device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
         self.model = FidModel(self.image_size, device)
@@ -1220,6 +1340,13 @@ class FaceIdentifier(object):
             tr_gen = sequence(self.raw_data_path, self.hps, self.nn_arch, load_flag=True)
         h = self.hps
         steps, epochs = int(h['step']), int(h['epochs'])
+        pk = batch_mining_conf(h, self.image_size) if batch_mining_mode(h) is not None else None
+        if pk is not None:                 # one rank (refused above otherwise): no collective below
+            self._train_pk(tr_gen, pk, steps, epochs)
+            print('Save the model.')
+            self.model.save(self.MODEL_PATH)
+            trainer.shutdown()
+            return
         inputs = self._triplet_inputs(tr_gen)
         # one rank: the global numpy stream, as before; several: one seeded generator, the same batch order on every rank
         rng = np.random.default_rng(0) if self.world > 1 else np.random
@@ -1259,6 +1386,50 @@ class FaceIdentifier(object):
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
         trainer.shutdown()
+
+    def _train_pk(self, tr_gen, pk, steps, epochs):
+        """train() with hps['batch_mining']: every epoch draws its PK batches (pk_batches, one generator
+        seeded with pk_seed for the whole run -- never the global stream), runs min(steps, batches) of them through
+        FidModel.train_on_labelled_batch, the crops fed by TripletInputs.crop_batches, and prints the mean loss and, summed over
+        the epoch, the anchors of each kind and how many had a hinge that passes a gradient.  Nothing is read back before the
+        epoch's last step is in the queue.  self.last_batch_mining: the batches (db row positions) of every epoch, the last
+        epoch's counts."""
+        from .crop_store import HOST, TripletInputs, store_budget
+        m, h, S = self.model, self.hps, self.image_size
+        labels = list(tr_gen.db.index)
+        codes = subject_codes(list(tr_gen.db['subject_id']))
+        rng = np.random.default_rng(pk['seed'])
+        rows_most = pk['P'] * pk['K']
+        m.ensure_optimizer()
+        m._batch_workspace(rows_most)      # before the store's budget is taken from what is free
+        if h.get('crop_store', CROP_STORE_DEFAULT):
+            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, store_budget(h, m.dev),
+                                   self._loader_threads(), slots=max(3 * tr_gen.batch_size, rows_most))
+        else:
+            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, 0, self._loader_threads(), tier=HOST)
+        self.last_batch_mining = dict(batches=[], counts=None, active=None)
+        try:
+            for e in range(epochs):
+                batches = pk_batches(codes, pk['P'], pk['K'], rng)[:steps]
+                self.last_batch_mining['batches'].append(batches)
+                losses = []
+                counts = torch.zeros(4, dtype=torch.int64, device=m.dev)
+                active = torch.zeros((), dtype=torch.int64, device=m.dev)
+                feed = inputs.crop_batches([[labels[r] for r in b] for b in batches])
+                for b, x in zip(batches, feed):
+                    loss = m.train_on_labelled_batch(x, codes[b], pk['mode'], h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0))
+                    losses.append(loss.clone())
+                    sel = m.batch_selection
+                    valid = sel['kind'] != KIND_NONE
+                    counts += torch.bincount(sel['kind'].to(torch.int64), minlength=4)[:4]
+                    active += (valid & (sel['d_ap'] - sel['d_an'] + TRIPLET_MARGIN >= 0)).sum()     # NaN >= 0 is False
+                c = [int(v) for v in counts.cpu()]
+                self.last_batch_mining.update(counts=c, active=int(active.cpu()))
+                mean = float(torch.cat(losses).double().mean().cpu()) if losses else float('nan')
+                print('Epoch %d/%d - loss: %.4f - anchors (%s) semi-hard: %d, violating: %d, easy: %d, without a triplet: %d, active: %d'
+                      % (e + 1, epochs, mean, pk['mode'], c[0], c[1], c[2], c[3], self.last_batch_mining['active']))
+        finally:
+            inputs.close()
 
     # ------------------------------------------------------------------ triplet mining (DESIGN.md section 21)
     def _sequence(self):

@@ -262,6 +262,22 @@ def fid_triplet_loss_grad(ctx, pre, u, grad_weight=1.0, dE=None, dbias=None):
     return loss, dE, dbias
 
 
+def fid_batch_triplet_loss_grad(ctx, pre, u, subjects, margin=0.2, mode=0, grad_weight=1.0, out=None):
+    """pre, u (M, 64) float32, subjects (M,) int32; mode 0 batch hard, 1 batch semi-hard -> dict(loss (1,), dE (M, 64), dbias (64,),
+    pos_index, neg_index, kind (M,) int32, d_ap, d_an (M,) float64).  out: buffers to write into, by those names."""
+    M = pre.shape[0]
+    out = dict(out or {})
+    new = lambda name, shape, dtype: out[name] if name in out else torch.empty(shape, dtype=dtype, device=pre.device)
+    o = dict(loss=new('loss', (1,), torch.float32), dE=new('dE', (M, 64), torch.float32), dbias=new('dbias', (64,), torch.float32),
+             pos_index=new('pos_index', (M,), torch.int32), neg_index=new('neg_index', (M,), torch.int32),
+             kind=new('kind', (M,), torch.int32), d_ap=new('d_ap', (M,), torch.float64), d_an=new('d_an', (M,), torch.float64))
+    rc = lib().fv_fid_batch_triplet_loss_grad(ctx.handle, ptr(pre), ptr(u), ptr(subjects), M, float(margin), int(mode), float(grad_weight),
+                                              ptr(o['loss']), ptr(o['dE']), ptr(o['dbias']), ptr(o['pos_index']), ptr(o['neg_index']),
+                                              ptr(o['kind']), ptr(o['d_ap']), ptr(o['d_an']))
+    ctx.check(rc, 'fv_fid_batch_triplet_loss_grad')
+    return o
+
+
 def fid_towers_dense_dgrad(ctx, dE, w, towers, M):
     """dE (M, 64), w (F, 64): writes rows m of dE . w^T into towers[m // per][m % per]."""
     (d0, d1, d2), per = _towers(towers)

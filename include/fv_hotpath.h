@@ -512,6 +512,42 @@ int fv_fid_towers_dense_l2(fv_ctx* ctx, const float* x0, const float* x1, const 
  * grad_weight finite and > 0. */
 int fv_fid_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, int B, double grad_weight, float* loss, float* dE,
                              float* dbias);
+/* Batch triplet loss with in-batch mining (FaceNet section 3.2 online mining; Hermans et al., "batch hard"): pre / u [M][64] as the
+ * dense call returns them, subjects [M] int32 (device; u 16-byte aligned), 1 <= M <= 1024.  Every row of a known subject is an
+ * anchor; its triplet is formed inside the batch.
+ *   D(i, r): the distance of fv_fid_match and fv_fid_mine_negatives (sqrt of the fp64 sum, in dimension order, of the squared fp64
+ *   differences).  Row r is a positive candidate of anchor i iff r != i and subjects[r] == subjects[i] >= 0, a negative candidate
+ *   iff subjects[r] >= 0 and subjects[r] != subjects[i]; a row of subject < 0 is never an anchor, a positive or a negative; a row
+ *   whose D(i, r) is NaN belongs to no class.
+ *   positive p_i: the candidate with the largest D, the lowest r among equals; dap = D(i, p_i).
+ *   negative n_i: mode 0 (batch hard) the minimum of (D, r) over the negative candidates; mode 1 (batch semi-hard) the row that
+ *   fv_fid_mine_negatives' mode 0 table picks for (dap, margin) among them (semi-hard nearest, else the mildest violating, else
+ *   the nearest easy).  kind: 0 / 1 / 2 by that table's three inequalities, in both modes.
+ *   An anchor is valid iff it has both; otherwise pos_index = neg_index = -1, kind = 3, d_ap one quiet NaN (sign and payload
+ *   clear), d_an +inf, and it contributes nothing.
+ *   loss (device float) = (1 / V) sum over the V valid anchors, in anchor order (fp64), of max(h_i, 0), h_i = dap - dan + margin;
+ *   V == 0: loss 0, dE and dbias exactly 0, FV_OK.
+ *   gradient, with the definitions stated at fv_fid_train_step: an anchor with h_i >= 0 adds c ((u_i - u_p) / dap - (u_i - u_n) / dan)
+ *   to row i, -c (u_i - u_p) / dap to row p_i and c (u_i - u_n) / dan to row n_i, c = 1 / V (a distance of exactly 0: 0).  Row r's
+ *   total is one fp64 sum in a fixed order -- its own anchor term, then for i = 0 .. M-1 the positive and then the negative term
+ *   anchor i sends to r (gathered by the row's owner: no atomics) -- taken back through l2_normalize and ReLU as in
+ *   fv_fid_triplet_loss_grad; loss_weight (finite, > 0) multiplies once where the value is rounded to float.  dE [M][64];
+ *   dbias [64] = the column sums of the stored dE in fp64, in row order.
+ * The same inputs give the same bits on every call.  Checked before anything is enqueued: a NULL buffer, M outside [1, 1024], a
+ * mode other than 0 / 1, a margin or loss_weight that is not finite and > 0 is FV_ERR_INVALID and leaves the outputs untouched. */
+int fv_fid_batch_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u, const int32_t* subjects, int M, double margin,
+                                   int mode, double loss_weight, float* loss, float* dE, float* dbias, int32_t* pos_index,
+                                   int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an);
+/* One training step on a labelled batch: x [M][S][S][3] and subjects [M] (device) go through ONE tower -- the 52 base layers in
+ * training-mode BN over all M images (one set of batch statistics, one update of the moving statistics: with
+ * fv_set_bn_zero_debias_step(ctx, k) update k alone), the dense layer and l2_normalize over the M rows,
+ * fv_fid_batch_triplet_loss_grad with loss_weight 1, the dense gradients and one backward of the base.  `grads` (the
+ * fv_fid_param_count layout) is overwritten; loss and the five selection outputs are device buffers as above.  M: the batch bound
+ * of fv_fid_extract and at most 1024, both checked before anything is enqueued.  Reproducibility as fv_fid_train_step. */
+size_t fv_fid_batch_workspace_bytes(int M, int image_size);
+int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* subjects, int M,
+                            int image_size, int mode, double margin, void* workspace, size_t workspace_bytes, float* grads,
+                            float* loss, int32_t* pos_index, int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an);
 /* dX = dE . w^T ([M][64] x [F][64]^T) stored into the towers' rows; each element one fp32 chain over the 64 columns in order. */
 int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
                               int per);

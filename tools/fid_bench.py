@@ -5,6 +5,12 @@ step and the same step through parallel.DataParallelTrainer with the bucket path
 launches no kernel at one rank: what the callbacks and the stream traffic cost).  Prints one JSON line.
 
     python tools/fid_bench.py [--iters N]
+    python tools/fid_bench.py --only batch_step [--iters N]
+
+batch_step: alternating in this process, three blocks each of the three-tower B = 13 triplet step and of the
+one-tower M = 39 labelled-batch step (fv_fid_batch_train_step + fv_adam_step; 13 subjects of 3 crops), the host clock around
+blocks that end in a synchronise, all blocks reported; then the per-launch device time of the batch loss's three kernels at
+M = 39, 96 and 1024 next to fid_triplet_kernel at B = 13, and the loss's share of the M = 39 step.
 """
 import argparse
 import json
@@ -65,14 +71,65 @@ def bucket_path_cost(m, xs, iters, params0, state0, rounds=3):
     return res
 
 
+BATCH_KERNELS = ('fid_batch_select_kernel', 'fid_batch_grad_kernel', 'fid_batch_finish_kernel')
+
+
+def profiled_us(m, fn, names):
+    """Per-launch device time (us) of the named kernels over one call of fn, after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    m.ctx.profile(True)
+    fn()
+    recs = m.ctx.profile_collect()
+    m.ctx.profile(False)
+    return {k: round(1e3 * recs[k]['ms'] / recs[k]['launches'], 2) for k in names if k in recs}
+
+
+def batch_step(m, g, iters, rounds=3):
+    from face_vijnana_yolov3_amd import ops
+    state0, params0 = m.state.clone(), m.params.clone()
+    B, P, K = 13, 13, 3
+    xs = [torch.rand((B, S, S, 3), generator=g, device='cuda') for _ in range(3)]
+    x = torch.cat(xs)
+    subjects = torch.arange(P, dtype=torch.int32, device='cuda').repeat_interleave(K)
+    ms = dict(three_tower_b13=[], one_tower_m39=[])
+    for r in range(rounds):
+        for name, step in (('three_tower_b13', lambda: m.train_on_batch(*xs, 1e-6, 0.99, 0.99)),
+                           ('one_tower_m39', lambda: m.train_on_labelled_batch(x, subjects, 'batch_semi_hard', 1e-6, 0.99, 0.99))):
+            ms[name].append(round(1e3 * timed(step, iters, 1 if r == 0 else 0), 2))
+            m.params.copy_(params0); m.state.copy_(state0)
+    out = dict(image_size=S, iters_per_block=iters, step_ms_blocks=ms)
+    out['triplet_kernel_us_b13'] = profiled_us(m, lambda: m.forward_backward(*xs), ('fid_triplet_kernel',))
+    out['batch_loss_us_in_step_m39'] = profiled_us(m, lambda: m.forward_backward_batch(x, subjects, 'batch_semi_hard'), BATCH_KERNELS)
+    m.params.copy_(params0); m.state.copy_(state0)
+    loss_us = sum(out['batch_loss_us_in_step_m39'].values())
+    out['batch_loss_share_of_step'] = round(loss_us / (1e3 * min(ms['one_tower_m39'])), 5)
+    alone = {}
+    for M in (39, 96, 1024):
+        pre = torch.randn((M, 64), generator=g, device='cuda')
+        r = torch.relu(pre)
+        u = r / r.norm(dim=1, keepdim=True).clamp_min(1e-6)
+        sub = (torch.arange(M, device='cuda') % max(1, M // 6)).to(torch.int32)
+        for mode in (0, 1):
+            us = profiled_us(m, lambda: ops.fid_batch_triplet_loss_grad(m.ctx, pre, u, sub, 0.2, mode), BATCH_KERNELS)
+            us['total'] = round(sum(us.values()), 2)
+            alone['m%d_mode%d' % (M, mode)] = us
+    out['batch_loss_us_alone'] = alone
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--only', choices=['batch_step'], default=None)
     args = ap.parse_args()
     m = FidModel(S, 0)
     m.init_synthetic(seed=7)
     m.init_dense()
     g = torch.Generator(device='cuda').manual_seed(0)
+    if args.only == 'batch_step':
+        print(json.dumps(batch_step(m, g, args.iters)))
+        return
     out = dict(image_size=S)
     for B in (1, 48):
         x = torch.rand((B, S, S, 3), generator=g, device='cuda')
