@@ -109,6 +109,9 @@ def _declare(L):
         'fv_bn_act_slots': (i32, [vp, vp, vp, i32, i64, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, f32]),
         'fv_conv2d_dgrad_bnred': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32]),
         'fv_bn_bwd_slots': (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp, i32, i32, vp, vp, vp]),
+        'fv_conv2d_forward_slots_bn_in': (i32, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32]),
+        'fv_conv2d_wgrad_bn_in': (i32, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        'fv_conv2d_wgrad_bn_bwd': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         'fv_mse_loss_grad': (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         'fv_fd_loss_grad': (i32, [vp, vp, vp, i32, i32, vp, vp]),
         'fv_upsample_concat': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32]),
@@ -202,7 +205,7 @@ class Context:
 
     def set_option(self, key, value):
         """fv_set_option: a tuning switch of include/fv_hotpath.h ('overlap', 'tail_split', 'conv_waves8', 'conv1x1_persist',
-        'conv_bm64', 'conv_small', 'conv_halo', 'conv0_direct', 'wgrad_fused_taps')."""
+        'conv_bm64', 'conv_small', 'conv_halo', 'conv0_direct', 'wgrad_fused_taps', 'early_bn_fused')."""
         self.check(lib().fv_set_option(self._h, key.encode(), int(value)), 'fv_set_option(%s)' % key)
 
     def get_option(self, key):

@@ -82,8 +82,18 @@ const FvOption* find_option(const char* key) {
 }
 }  // namespace
 
+// "early_bn_fused" is the one option with parts: 0 off, 1 all of them (the default), or 2 * (a mask of FV_EARLY_*) for the A/B
+// of one part -- 2 the forward alone, 4 the weight-gradient alone, 8 dz(0) alone, and their sums
+static bool is_early_bn(const char* key) { return key && std::string(key) == "early_bn_fused"; }
+
 int fv_set_option(fv_ctx* ctx, const char* key, long long value) {
     if (!ctx) return FV_ERR_INVALID;
+    if (is_early_bn(key)) {
+        if (value < 0 || value > 2 * FV_EARLY_ALL || (value > 1 && (value & 1)))
+            return fv_fail(ctx, FV_ERR_INVALID, "fv_set_option: early_bn_fused takes 0, 1 or an even mask up to %d (got %lld)", 2 * FV_EARLY_ALL, value);
+        ctx->early_bn = value == 1 ? FV_EARLY_ALL : (int)(value >> 1);
+        return FV_OK;
+    }
     const FvOption* o = find_option(key);
     if (!o) return fv_fail(ctx, FV_ERR_INVALID, "fv_set_option: unknown option '%s'", key ? key : "(null)");
     ctx->*(o->member) = value != 0;
@@ -92,6 +102,7 @@ int fv_set_option(fv_ctx* ctx, const char* key, long long value) {
 
 int fv_get_option(fv_ctx* ctx, const char* key, long long* value) {
     if (!ctx || !value) return FV_ERR_INVALID;
+    if (is_early_bn(key)) { *value = ctx->early_bn == FV_EARLY_ALL ? 1 : 2 * ctx->early_bn; return FV_OK; }
     const FvOption* o = find_option(key);
     if (!o) return fv_fail(ctx, FV_ERR_INVALID, "fv_get_option: unknown option '%s'", key ? key : "(null)");
     *value = ctx->*(o->member) ? 1 : 0;
@@ -178,8 +189,11 @@ int fv_create(int device, void* stream, fv_ctx** out) {
             if (end == std::string::npos) end = spec.size();
             const std::string item = spec.substr(pos, end - pos);
             const size_t eq = item.find('=');
-            if (eq != std::string::npos)
-                if (const FvOption* o = find_option(item.substr(0, eq).c_str())) c->*(o->member) = item[eq + 1] != '0';
+            if (eq != std::string::npos) {
+                const std::string key = item.substr(0, eq);
+                if (is_early_bn(key.c_str())) (void)fv_set_option(c, key.c_str(), atoll(item.c_str() + eq + 1));   // (a bad value is ignored)
+                else if (const FvOption* o = find_option(key.c_str())) c->*(o->member) = item[eq + 1] != '0';
+            }
             pos = end + 1;
         }
     }

@@ -40,9 +40,14 @@ struct fv_ctx {
     bool conv_small = true;      // option "conv_small": conv_small_kernel for small-M inference launches (fv_conv_small_plan)
     bool conv_bm64 = true;       // option "conv_bm64": 64-row tiles for small-M inference launches (fv_conv_bm64)
     bool conv1x1_persist = true; // option "conv1x1_persist": conv1x1_mfma.hip for 1x1 launches with more than 512 tiles
+    // option "early_bn_fused": the first layers' BN passes folded into their halo-kernel consumers (schedule.h).  A bit mask of the
+    // parts: FV_EARLY_FWD conv9_mfma.hip reads z(0) / z(2), FV_EARLY_WGRAD wgrad9_mfma.hip does, FV_EARLY_DZ0 wgrad0_mfma.hip forms dz(0)
+    int early_bn = 7;
     bool conv0_direct = true;    // option "conv0_direct": vector-FMA first layer (conv0_direct.hip) instead of the gather kernel
     ~fv_ctx();
 };
+
+enum { FV_EARLY_FWD = 1, FV_EARLY_WGRAD = 2, FV_EARLY_DZ0 = 4, FV_EARLY_ALL = 7 };
 
 // RAII: brackets one kernel launch with HIP events when profiling is enabled.
 struct FvProfScope {

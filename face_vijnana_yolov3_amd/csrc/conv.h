@@ -34,6 +34,10 @@ struct FvConvArgs {
     double* bn_slots;
     int bn_nslot;
     float bn_leaky;
+    // BN-on-load (conv9_mfma.hip alone): x is the producing layer's raw conv output z and the kernel stages
+    // LeakyReLU(z * in_scale + in_shift) (per input channel) in its place; padding stays zero.  NULL: x is read as it is.
+    const float *in_scale, *in_shift;
+    float in_leaky;
     int B, Hin, Win, Cin;
     int Hl, Wl;
     int Hout, Wout, Nout;
@@ -92,6 +96,18 @@ struct FvWgradArgs {
     const float* x;
     const float* dy;
     float* dw;
+    // BN-on-load of x (wgrad9_mfma.hip alone), as FvConvArgs::in_scale
+    const float *x_scale, *x_shift;
+    float x_leaky;
+    // BN-backward apply on load of dy (wgrad0_mfma.hip alone): dy is g, the gradient w.r.t. the output of the BN + LeakyReLU
+    // layer whose pre-BN tensor is bn_z (both rows of N floats), and the kernel stages dz as bn_bwd_apply_slots_kernel forms it:
+    // every workgroup sums bn_slots [bn_nslot][2][N] first, workgroup 0 stores (bn_accumulate: adds) d-beta / d-gamma
+    const float *bn_z, *bn_scale, *bn_shift, *bn_mean, *bn_invstd;
+    const double* bn_slots;
+    int bn_nslot;
+    float bn_inv_count, bn_leaky;
+    float *bn_dbeta, *bn_dgamma;
+    int bn_accumulate;
     int B, Hin, Win, Cin;  // x dims
     int Hl, Wl, N;         // dy lattice and used channels
     int Ndy;               // channel stride of dy (>= N)

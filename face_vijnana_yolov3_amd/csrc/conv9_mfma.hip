@@ -12,7 +12,13 @@
 // channel halves, one 32x32 accumulator each; K order = the generic kernel's (tap-major, inside every 8 channels
 // 0,4,1,5,2,6,3,7), so z is BIT-IDENTICAL to conv_kernel<64,...>.  The statistics are summed per unit in fp32, across units
 // in fp64 registers, and added to one slot per workgroup at the end (the generic kernel adds per tile).
+//
+// BN-on-load (a.in_scale): x is the producing layer's raw conv output and stage() writes LeakyReLU(x * scale + shift) -- every
+// halo element is staged exactly once per unit, so the producer's activation need not exist in memory.  A thread stages one
+// fixed group of four channels (slot index f = tid + NTH p, NTH a multiple of 8), so its constants are eight registers; slots
+// outside the image must stay 0.0 (not LeakyReLU(shift)): issue() keeps their validity as a bit mask for stage().
 #include "conv.h"
+#include "elementwise.h"
 
 namespace {
 
@@ -62,22 +68,40 @@ __global__ __launch_bounds__(NTH, 1) void conv9_fwd_kernel(const FvConvArgs a, i
         x_rc[p] = ((f < NXF ? hr : 1 << 12) << 8) | hc;
         x_rel[p] = (unsigned)((hr * a.Win + hc) * CC + c4 * 4) * 4u;
     }
+    static_assert(NTH % 8 == 0 && NX <= 32, "a thread stages one channel group; one validity bit per slot");
+    const bool bn = a.in_scale != nullptr;
+    float4 bsc = make_float4(0.f, 0.f, 0.f, 0.f), bsh = bsc;
+    if (bn) {
+        bsc = *reinterpret_cast<const float4*>(a.in_scale + (tid & 7) * 4);
+        bsh = *reinterpret_cast<const float4*>(a.in_shift + (tid & 7) * 4);
+    }
     u32x4 rx[NX];
+    unsigned rx_ok = 0;                     // bit p: slot p of the halo in rx lies inside the image
     auto issue = [&](int u) {
         const int uc = u % units_w, t = u / units_w, ur = t % units_h, b = t / units_h;
         const int ih0 = ur * UR * S - 1, iw0 = uc * UC * S - 1;
         const unsigned base_x = (unsigned)(((b * a.Hin + ih0) * a.Win + iw0) * CC) * 4u;      // modular when ih0 / iw0 = -1
+        rx_ok = 0;
 #pragma unroll
         for (int p = 0; p < NX; ++p) {
             const bool ok = ((unsigned)(ih0 + (x_rc[p] >> 8)) < (unsigned)a.Hin) & ((unsigned)(iw0 + (x_rc[p] & 255)) < (unsigned)a.Win);
             rx[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, ok ? base_x + x_rel[p] : OOB, 0, 0);
+            rx_ok |= (unsigned)ok << p;
         }
     };
     auto stage = [&]() {
 #pragma unroll
         for (int p = 0; p < NX; ++p) {
             const int f = tid + NTH * p;
-            if (NTH * p + NTH <= NXF || f < NXF) *reinterpret_cast<u32x4*>(&x_l[(f >> 3) * LDX + (f & 7) * 4]) = rx[p];
+            u32x4 v = rx[p];
+            if (bn) {
+                const float4 y = fv_bn_leaky4(make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])),
+                                              bsc, bsh, a.in_leaky);
+                const bool ok = (rx_ok >> p) & 1;
+                v[0] = ok ? __float_as_uint(y.x) : 0u; v[1] = ok ? __float_as_uint(y.y) : 0u;
+                v[2] = ok ? __float_as_uint(y.z) : 0u; v[3] = ok ? __float_as_uint(y.w) : 0u;
+            }
+            if (NTH * p + NTH <= NXF || f < NXF) *reinterpret_cast<u32x4*>(&x_l[(f >> 3) * LDX + (f & 7) * 4]) = v;
         }
     };
 
@@ -167,6 +191,7 @@ bool fv_conv9_fwd_ok(const FvConvArgs& a) {
     if (a.epi != FV_EPI_STATS || !a.stat_slots || a.stat_nslot < 1) return false;
     if ((a.is != 1 && a.is != 2) || a.os != 1 || a.Hout != a.Hl || a.Wout != a.Wl || a.oph[0] || a.opw[0]) return false;
     if (a.Hl * a.is != a.Hin || a.Wl * a.is != a.Win || a.taps[0].n != 9) return false;
+    if ((a.in_scale != nullptr) != (a.in_shift != nullptr)) return false;
     // masked edge stores use the 32-bit byte offset 0x80000000 as "outside": it must lie beyond the output tensor
     if ((long long)a.B * a.Hout * a.Wout * a.Nout * 4 >= (1ll << 31)) return false;
     for (int t = 0; t < 9; ++t)

@@ -474,6 +474,7 @@ int fv_conv_launch(fv_ctx* ctx, const FvConvArgs& a) {
                "conv: fused BN-backward reduction needs its layer's tensors, 16-byte rows and a plain (+add) epilogue");
     FV_REQUIRE(ctx, a.ksplit <= 1 || (a.epi == 0 && a.nclass == 1 && a.Cin % BK == 0), "conv: split-K stores raw partials only");
     if (ctx->conv_halo && fv_conv9_fwd_ok(a)) return fv_conv9_fwd_launch(ctx, a);
+    FV_REQUIRE(ctx, !a.in_scale, "conv: BN-on-load needs the halo kernel (conv9_mfma.hip), which does not take this launch");
     if (ctx->conv_halo && fv_dgrad9s2_ok(a)) return fv_dgrad9s2_launch(ctx, a);
     const bool gather = a.Cin % BK != 0;
     if (gather) {

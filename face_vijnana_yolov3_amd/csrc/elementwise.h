@@ -2,6 +2,53 @@
 #pragma once
 #include "common.h"
 
+// ---- device expressions shared between the BN passes (elementwise.hip) and the halo kernels that apply them on load
+// (conv9_mfma.hip, wgrad9_mfma.hip, wgrad0_mfma.hip): one definition each, so the fused and the materialised form give the same
+// bits (the library is built with -ffp-contract=off).
+
+// a = LeakyReLU(z * scale + shift)
+__device__ __forceinline__ float fv_bn_leaky(float z, float sc, float sh, float leaky) {
+    const float v = z * sc + sh;
+    return v > 0.f ? v : v * leaky;
+}
+__device__ __forceinline__ float4 fv_bn_leaky4(float4 v, const float4& sc, const float4& sh, float leaky) {
+    v.x = fv_bn_leaky(v.x, sc.x, sh.x, leaky); v.y = fv_bn_leaky(v.y, sc.y, sh.y, leaky);
+    v.z = fv_bn_leaky(v.z, sc.z, sh.z, leaky); v.w = fv_bn_leaky(v.w, sc.w, sh.w, leaky);
+    return v;
+}
+
+// dz = scale * (gy - dbeta/M - xhat * dgamma/M), gy = g * LeakyReLU'(z * scale + shift)
+__device__ __forceinline__ float fv_bn_bwd_dz(float g, float z, float sc, float sh, float mu, float is, float db, float dg,
+                                              float inv_count, float leaky) {
+    const float gy = (z * sc + sh) > 0.f ? g : g * leaky;
+    return sc * (gy - db * inv_count - (z - mu) * is * (dg * inv_count));
+}
+__device__ __forceinline__ float4 fv_bn_bwd_dz4(const float4& g, const float4& z, const float4& sc, const float4& sh, const float4& mu,
+                                                const float4& is, const float4& db, const float4& dg, float inv_count, float leaky) {
+    float4 o;
+    o.x = fv_bn_bwd_dz(g.x, z.x, sc.x, sh.x, mu.x, is.x, db.x, dg.x, inv_count, leaky);
+    o.y = fv_bn_bwd_dz(g.y, z.y, sc.y, sh.y, mu.y, is.y, db.y, dg.y, inv_count, leaky);
+    o.z = fv_bn_bwd_dz(g.z, z.z, sc.z, sh.z, mu.z, is.z, db.z, dg.z, inv_count, leaky);
+    o.w = fv_bn_bwd_dz(g.w, z.w, sc.w, sh.w, mu.w, is.w, db.w, dg.w, inv_count, leaky);
+    return o;
+}
+
+// Totals of the [nslot][2][C] fp64 accumulator slots by a 256-thread workgroup for C < 256 dividing 256: the 256 / C thread
+// groups take every (256 / C)-th slot of a channel, thread c < C then adds the groups' partials in ascending order -- one fixed
+// order wherever the slots are summed.  Valid in threads tid < C on return; contains one barrier, s_part is [2][256].
+__device__ __forceinline__ void fv_bn_slot_totals(const double* __restrict__ slots, int nslot, int C, int tid, double (*s_part)[256],
+                                                  double& a, double& b) {
+    const int G = 256 / C, g = tid / C, c = tid % C;
+    a = 0.0; b = 0.0;
+    for (int k = g; k < nslot; k += G) { a += slots[(size_t)(2 * k) * C + c]; b += slots[(size_t)(2 * k + 1) * C + c]; }
+    s_part[0][tid] = a; s_part[1][tid] = b;
+    __syncthreads();
+    if (tid < C) {
+        a = 0.0; b = 0.0;
+        for (int j = 0; j < G; ++j) { a += s_part[0][j * C + tid]; b += s_part[1][j * C + tid]; }
+    }
+}
+
 int fv_ew_bn_finalize(fv_ctx* ctx, const float* psum, const float* psq, int mtiles, int C, double count, const float* gamma,
                       const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                       float* moving_mean, float* moving_var);
@@ -28,6 +75,10 @@ int fv_ew_bn_stat_slots(int C);
 int fv_ew_bn_act_stats(fv_ctx* ctx, const float* z, const double* slots, int nslot, double count, const float* gamma,
                        const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                        float* moving_mean, float* moving_var, const float* skip, float* out, long long rows, int C, float leaky);
+// the statistics part of fv_ew_bn_act_stats alone (one workgroup): for a layer whose consumers apply scale/shift + LeakyReLU on load
+int fv_ew_bn_stats_publish(fv_ctx* ctx, const double* slots, int nslot, double count, const float* gamma, const float* beta, float eps,
+                           float momentum, float* mean, float* invstd, float* scale, float* shift, float* moving_mean, float* moving_var,
+                           int C);
 int fv_ew_transpose_ntc(fv_ctx* ctx, const float* src, float* dst, int N, int T, int C, int Npad);
 // the same for up to 64 layers in one launch; offsets in floats from the two base pointers
 int fv_ew_transpose_all(fv_ctx* ctx, const float* src_base, float* dst_base, int nlayers, const long long* src_off,

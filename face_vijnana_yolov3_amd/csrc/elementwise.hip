@@ -89,29 +89,23 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float4* __restrict__ 
     int cg = (int)(i % c4n);
     for (; i < n4; i += stride, cg += cstep, cg -= cg >= c4n ? c4n : 0) {
         const int c = cg << 2;
-        float4 v = z[i];
         const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
-        v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-        v.x = v.x > 0.f ? v.x : v.x * leaky; v.y = v.y > 0.f ? v.y : v.y * leaky;
-        v.z = v.z > 0.f ? v.z : v.z * leaky; v.w = v.w > 0.f ? v.w : v.w * leaky;
+        float4 v = fv_bn_leaky4(z[i], sc, sh, leaky);
         if (skip) { float4 s = skip[i]; v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
         out[i] = v;
     }
 }
 
-// The same pass fed by the conv epilogue's accumulator slots (conv.h stat_slots): every workgroup first
-// turns the slots into scale/shift for all C channels (fixed summation order over the slots, fp64,
-// 16 loads per thread) and keeps them in LDS; workgroup 0 also publishes mean / invstd / scale / shift
-// for the backward pass and updates the moving statistics -- no finalize launch in between.
-__global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restrict__ z, const double* __restrict__ slots, int nslot,
-                                                           double count, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float eps, float ema_old, float ema_new, float* __restrict__ mean_out,
-                                                           float* __restrict__ invstd_out, float* __restrict__ scale_out,
-                                                           float* __restrict__ shift_out, float* __restrict__ moving_mean,
-                                                           float* __restrict__ moving_var, const float4* __restrict__ skip,
-                                                           float4* __restrict__ out, long long n4, int C, float leaky) {
-    __shared__ __attribute__((aligned(16))) float s_sc[1024], s_sh[1024];
-    __shared__ double s_part[2][256];
+// Accumulator slots of the conv epilogue (conv.h stat_slots) -> scale/shift of all C channels in LDS: fixed summation order
+// over the slots, fp64, 16 loads per thread.  `publish` (one workgroup per launch): also mean / invstd / scale / shift for the
+// backward pass and the update of the moving statistics.  The caller's barrier makes s_sc / s_sh visible.
+__device__ __forceinline__ void bn_slots_to_affine(const double* __restrict__ slots, int nslot, double count,
+                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                   float ema_old, float ema_new, float* __restrict__ mean_out,
+                                                   float* __restrict__ invstd_out, float* __restrict__ scale_out,
+                                                   float* __restrict__ shift_out, float* __restrict__ moving_mean,
+                                                   float* __restrict__ moving_var, int C, bool publish, float* s_sc, float* s_sh,
+                                                   double (*s_part)[256]) {
     const int tid = threadIdx.x;
     auto finish = [&](int c, double s, double q) {
         const double mean = s / count;
@@ -120,7 +114,7 @@ __global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restr
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         const float sc = gamma[c] * invstd, sh = beta[c] - (float)mean * sc;
         s_sc[c] = sc; s_sh[c] = sh;
-        if (blockIdx.x == 0) {
+        if (publish) {
             mean_out[c] = (float)mean; invstd_out[c] = invstd; scale_out[c] = sc; shift_out[c] = sh;
             if (moving_mean) {   // Keras 2.2.4 BatchNormalization: EMA of batch mean and of var * n/(n-(1+eps))
                 const double corr = count / (count - (1.0 + (double)eps));
@@ -137,18 +131,26 @@ __global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restr
         }
     } else {
         // C < 256 (a power of two >= 32 here): 256 / C thread groups share the slots of a channel
-        const int G = 256 / C, g = tid / C, c = tid % C;
-        double s = 0.0, q = 0.0;
-        if (g < G)
-            for (int k = g; k < nslot; k += G) { s += slots[(size_t)(2 * k) * C + c]; q += slots[(size_t)(2 * k + 1) * C + c]; }
-        s_part[0][tid] = s; s_part[1][tid] = q;
-        __syncthreads();
-        if (tid < C) {
-            s = 0.0; q = 0.0;
-            for (int j = 0; j < G; ++j) { s += s_part[0][j * C + tid]; q += s_part[1][j * C + tid]; }
-            finish(tid, s, q);
-        }
+        double s, q;
+        fv_bn_slot_totals(slots, nslot, C, tid, s_part, s, q);
+        if (tid < C) finish(tid, s, q);
     }
+}
+
+// The normalise pass fed by the slots: every workgroup first turns them into scale/shift and keeps those in LDS; workgroup 0
+// also publishes -- no finalize launch in between.
+__global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restrict__ z, const double* __restrict__ slots, int nslot,
+                                                           double count, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float eps, float ema_old, float ema_new, float* __restrict__ mean_out,
+                                                           float* __restrict__ invstd_out, float* __restrict__ scale_out,
+                                                           float* __restrict__ shift_out, float* __restrict__ moving_mean,
+                                                           float* __restrict__ moving_var, const float4* __restrict__ skip,
+                                                           float4* __restrict__ out, long long n4, int C, float leaky) {
+    __shared__ __attribute__((aligned(16))) float s_sc[1024], s_sh[1024];
+    __shared__ double s_part[2][256];
+    const int tid = threadIdx.x;
+    bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
+                       moving_var, C, blockIdx.x == 0, s_sc, s_sh, s_part);
     __syncthreads();
     const int c4n = C >> 2;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -157,14 +159,25 @@ __global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restr
     int cg = (int)(i % c4n);
     for (; i < n4; i += stride, cg += cstep, cg -= cg >= c4n ? c4n : 0) {
         const int c = cg << 2;
-        float4 v = z[i];
         const float4 sc = *reinterpret_cast<const float4*>(s_sc + c), sh = *reinterpret_cast<const float4*>(s_sh + c);
-        v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-        v.x = v.x > 0.f ? v.x : v.x * leaky; v.y = v.y > 0.f ? v.y : v.y * leaky;
-        v.z = v.z > 0.f ? v.z : v.z * leaky; v.w = v.w > 0.f ? v.w : v.w * leaky;
+        float4 v = fv_bn_leaky4(z[i], sc, sh, leaky);
         if (skip) { float4 sk = skip[i]; v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w; }
         out[i] = v;
     }
+}
+
+// The statistics of a layer whose activation is not materialised (its consumers apply scale/shift on load): the prologue of
+// bn_act_stats_kernel alone, one workgroup -- the same device code, so scale / shift are the same bits.
+__global__ __launch_bounds__(256) void bn_stats_publish_kernel(const double* __restrict__ slots, int nslot, double count,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                               float ema_old, float ema_new, float* __restrict__ mean_out,
+                                                               float* __restrict__ invstd_out, float* __restrict__ scale_out,
+                                                               float* __restrict__ shift_out, float* __restrict__ moving_mean,
+                                                               float* __restrict__ moving_var, int C) {
+    __shared__ __attribute__((aligned(16))) float s_sc[1024], s_sh[1024];
+    __shared__ double s_part[2][256];
+    bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
+                       moving_var, C, true, s_sc, s_sh, s_part);
 }
 
 // ---------------------------------------------------------------- BN + leaky backward
@@ -298,16 +311,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_slots_kernel(const float4* _
             finish(c, a, b);
         }
     } else {
-        const int G = 256 / C, gi = tid / C, c = tid % C;
-        double a = 0.0, b = 0.0;
-        for (int k = gi; k < nslot; k += G) { a += slots[(size_t)(2 * k) * C + c]; b += slots[(size_t)(2 * k + 1) * C + c]; }
-        s_part[0][tid] = a; s_part[1][tid] = b;
-        __syncthreads();
-        if (tid < C) {
-            a = 0.0; b = 0.0;
-            for (int j = 0; j < G; ++j) { a += s_part[0][j * C + tid]; b += s_part[1][j * C + tid]; }
-            finish(tid, a, b);
-        }
+        double a, b;
+        fv_bn_slot_totals(slots, nslot, C, tid, s_part, a, b);
+        if (tid < C) finish(tid, a, b);
     }
     __syncthreads();
     const int c4n = C >> 2;
@@ -321,13 +327,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_slots_kernel(const float4* _
         const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
         const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
         const float4 db = *reinterpret_cast<const float4*>(s_db + c), dg = *reinterpret_cast<const float4*>(s_dg + c);
-        float4 o;
-        float gy;
-        gy = (zv.x * sc.x + sh.x) > 0.f ? gv.x : gv.x * leaky; o.x = sc.x * (gy - db.x * inv_count - (zv.x - mu.x) * is.x * (dg.x * inv_count));
-        gy = (zv.y * sc.y + sh.y) > 0.f ? gv.y : gv.y * leaky; o.y = sc.y * (gy - db.y * inv_count - (zv.y - mu.y) * is.y * (dg.y * inv_count));
-        gy = (zv.z * sc.z + sh.z) > 0.f ? gv.z : gv.z * leaky; o.z = sc.z * (gy - db.z * inv_count - (zv.z - mu.z) * is.z * (dg.z * inv_count));
-        gy = (zv.w * sc.w + sh.w) > 0.f ? gv.w : gv.w * leaky; o.w = sc.w * (gy - db.w * inv_count - (zv.w - mu.w) * is.w * (dg.w * inv_count));
-        dz[i] = o;
+        dz[i] = fv_bn_bwd_dz4(gv, zv, sc, sh, mu, is, db, dg, inv_count, leaky);
     }
 }
 
@@ -661,6 +661,20 @@ int fv_ew_bn_act_stats(fv_ctx* ctx, const float* z, const double* slots, int nsl
     hipLaunchKernelGGL(bn_act_stats_kernel, dim3(grid_for(n4, 256, 256 * 4)), dim3(256), 0, ctx->stream, (const float4*)z, slots, nslot,
                        count, gamma, beta, eps, ema_old, ema_new, mean, invstd, scale, shift, moving_mean, moving_var, (const float4*)skip,
                        (float4*)out, n4, C, leaky);
+    FV_LAUNCH_CHECK(ctx);
+    return FV_OK;
+}
+
+int fv_ew_bn_stats_publish(fv_ctx* ctx, const double* slots, int nslot, double count, const float* gamma, const float* beta, float eps,
+                           float momentum, float* mean, float* invstd, float* scale, float* shift, float* moving_mean, float* moving_var,
+                           int C) {
+    FV_REQUIRE(ctx, C % 4 == 0 && C <= 1024 && (C >= 256 || 256 % C == 0), "bn_stats_publish: C must be a multiple of 4, <= 1024, and divide 256 when below it");
+    FV_REQUIRE(ctx, nslot >= 1 && slots, "bn_stats_publish: no accumulator slots");
+    FvProfScope ps(ctx, "bn_stats_publish_kernel", 0.0, 16.0 * nslot * C);
+    float ema_old, ema_new;
+    bn_ema_coeff(ctx, momentum, &ema_old, &ema_new);
+    hipLaunchKernelGGL(bn_stats_publish_kernel, dim3(1), dim3(256), 0, ctx->stream, slots, nslot, count, gamma, beta, eps, ema_old, ema_new,
+                       mean, invstd, scale, shift, moving_mean, moving_var, C);
     FV_LAUNCH_CHECK(ctx);
     return FV_OK;
 }

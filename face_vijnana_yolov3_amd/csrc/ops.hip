@@ -14,22 +14,46 @@ static void fwd_taps(int ksize, FvTaps& t) {
         for (int q = 0; q < 3; ++q) { int i = r * 3 + q; t.dh[i] = r - 1; t.dw[i] = q - 1; t.wslot[i] = i; }
 }
 
-int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H, int W, int cin, int cout, int ksize,
-                       int stride, int epi, const float* scale, const float* shift, float leaky, const float* addend,
-                       float* out, float* psum, float* psq, int ksplit, double* stat_slots, int stat_nslot) {
-    FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "conv: unsupported k=%d s=%d", ksize, stride);
-    FV_REQUIRE(ctx, H % stride == 0 && W % stride == 0, "conv: H,W must be divisible by the stride");
-    FvConvArgs a{};
-    a.x = x; a.w = w; a.out = out; a.addend = addend; a.scale = scale; a.shift = shift; a.psum = psum; a.psq = psq;
+static bool fwd_shape_ok(int H, int W, int ksize, int stride) {
+    return ((ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2))) && H % stride == 0 && W % stride == 0;
+}
+
+// the launch description of a forward conv; the tensors and the inference-tiling choices are the caller's
+static void fwd_args(FvConvArgs& a, int B, int H, int W, int cin, int cout, int ksize, int stride, int epi, int ksplit,
+                     double* stat_slots, int stat_nslot) {
     a.B = B; a.Hin = H; a.Win = W; a.Cin = cin;
     a.Hl = H / stride; a.Wl = W / stride; a.Hout = a.Hl; a.Wout = a.Wl; a.Nout = cout;
     a.is = stride; a.os = 1; a.Tw = ksize * ksize; a.M = B * a.Hl * a.Wl;
-    a.epi = epi; a.leaky = leaky; a.nclass = 1;
+    a.epi = epi; a.nclass = 1;
     fwd_taps(ksize, a.taps[0]);
     if (cin % 32 != 0) a.Tw = 1;  // packed [cout][32] first-layer weights
     a.alg_flops = 2.0 * a.M * cout * (double)(ksize * ksize * cin);
     a.ksplit = ksplit; a.split_stride = (long long)a.M * cout;
     a.stat_slots = stat_slots; a.stat_nslot = stat_nslot;
+}
+
+bool fv_op_conv_forward_takes_bn_in(fv_ctx* ctx, int B, int H, int W, int cin, int cout, int ksize, int stride) {
+    if (!fwd_shape_ok(H, W, ksize, stride)) return false;
+    static double any_slot;   // the predicate asks only whether slots are given
+    FvConvArgs a{};
+    fwd_args(a, B, H, W, cin, cout, ksize, stride, FV_EPI_STATS, 1, &any_slot, 1);
+    // fv_conv_launch's own bound on the input tensor (one 2 GiB buffer descriptor), then its first dispatch
+    return (long long)B * H * W * cin < (1ll << 29) && ctx->conv_halo && fv_conv9_fwd_ok(a);
+}
+
+int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H, int W, int cin, int cout, int ksize,
+                       int stride, int epi, const float* scale, const float* shift, float leaky, const float* addend,
+                       float* out, float* psum, float* psq, int ksplit, double* stat_slots, int stat_nslot, const FvBnIn* bn_in) {
+    FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "conv: unsupported k=%d s=%d", ksize, stride);
+    FV_REQUIRE(ctx, H % stride == 0 && W % stride == 0, "conv: H,W must be divisible by the stride");
+    FvConvArgs a{};
+    a.x = x; a.w = w; a.out = out; a.addend = addend; a.scale = scale; a.shift = shift; a.psum = psum; a.psq = psq;
+    a.leaky = leaky;
+    if (bn_in) {
+        FV_REQUIRE(ctx, bn_in->scale && bn_in->shift, "conv: BN-on-load needs scale and shift");
+        a.in_scale = bn_in->scale; a.in_shift = bn_in->shift; a.in_leaky = bn_in->leaky;
+    }
+    fwd_args(a, B, H, W, cin, cout, ksize, stride, epi, ksplit, stat_slots, stat_nslot);
     // inference epilogues only: the training forward keeps one tiling whatever the batch (its statistics are per-tile sums)
     a.small = (ctx->conv_small && ksplit <= 1 && !(epi & FV_EPI_STATS) && cin % 32 == 0) ? fv_conv_small_plan(a.M, cout, cin, ksize * ksize) : 0;
     a.narrow = (!a.small && ksize == 1 && ksplit <= 1 && !(epi & FV_EPI_STATS) && cin % 32 == 0 && fv_conv_narrow(a.M, cout, cin / 32)) ? 1 : 0;
@@ -94,16 +118,52 @@ int fv_op_conv_dgrad(fv_ctx* ctx, const float* dy, const float* w_t, int B, int 
     return fv_conv_launch(ctx, a);
 }
 
-int fv_op_conv_wgrad(fv_ctx* ctx, const float* x, const float* dy, int B, int H, int W, int cin, int cout, int dy_stride,
-                     int ksize, int stride, float* dw) {
-    FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "wgrad: unsupported k=%d s=%d", ksize, stride);
-    FvWgradArgs a{};
-    a.x = x; a.dy = dy; a.dw = dw;
+static void wgrad_args(FvWgradArgs& a, int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride) {
     a.B = B; a.Hin = H; a.Win = W; a.Cin = cin;
     a.Hl = H / stride; a.Wl = W / stride; a.N = cout; a.Ndy = dy_stride;
     a.is = stride; a.Tw = ksize * ksize; a.M = B * a.Hl * a.Wl;
     fwd_taps(ksize, a.taps);
     a.alg_flops = 2.0 * a.M * cout * (double)(ksize * ksize * cin);
+}
+
+// fv_wgrad_launch's own checks on the sizes (2 GiB buffer descriptors), which come before its dispatch
+static bool wgrad_sizes_ok(const FvWgradArgs& a, int H, int W, int ksize, int stride) {
+    return fwd_shape_ok(H, W, ksize, stride) && a.M > 0 && a.N > 0 && a.Ndy >= a.N && a.Ndy % 4 == 0 &&
+           (long long)a.B * a.Hin * a.Win * a.Cin < (1ll << 29) && (long long)a.M * a.Ndy < (1ll << 29);
+}
+
+bool fv_op_conv_wgrad_takes_bn_in(fv_ctx* ctx, int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride) {
+    FvWgradArgs a{};
+    wgrad_args(a, B, H, W, cin, cout, dy_stride, ksize, stride);
+    return wgrad_sizes_ok(a, H, W, ksize, stride) && cin % 32 == 0 && ctx->wgrad_fused_taps && fv_wgrad9_ok(a);
+}
+
+bool fv_op_conv_wgrad_takes_bn_dy(fv_ctx* ctx, int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride) {
+    FvWgradArgs a{};
+    wgrad_args(a, B, H, W, cin, cout, dy_stride, ksize, stride);
+    // (the pointers of the mode are the caller's: what is asked here is the shape; 32 channels per pixel of g and z alike)
+    return wgrad_sizes_ok(a, H, W, ksize, stride) && cin % 32 != 0 && 9 * cin <= 32 && dy_stride == cout && ctx->wgrad_fused_taps &&
+           fv_wgrad0_ok(a);
+}
+
+int fv_op_conv_wgrad(fv_ctx* ctx, const float* x, const float* dy, int B, int H, int W, int cin, int cout, int dy_stride,
+                     int ksize, int stride, float* dw, const FvBnIn* bn_in, const FvBnDy* bn_dy) {
+    FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "wgrad: unsupported k=%d s=%d", ksize, stride);
+    FvWgradArgs a{};
+    a.x = x; a.dy = dy; a.dw = dw;
+    wgrad_args(a, B, H, W, cin, cout, dy_stride, ksize, stride);
+    if (bn_in) {
+        FV_REQUIRE(ctx, bn_in->scale && bn_in->shift, "wgrad: BN-on-load needs scale and shift");
+        a.x_scale = bn_in->scale; a.x_shift = bn_in->shift; a.x_leaky = bn_in->leaky;
+    }
+    if (bn_dy) {
+        FV_REQUIRE(ctx, bn_dy->z && bn_dy->scale && bn_dy->shift && bn_dy->mean && bn_dy->invstd && bn_dy->slots && bn_dy->nslot >= 1 &&
+                            bn_dy->dbeta && bn_dy->dgamma, "wgrad: the fused BN-backward apply needs its layer's tensors");
+        a.bn_z = bn_dy->z; a.bn_scale = bn_dy->scale; a.bn_shift = bn_dy->shift; a.bn_mean = bn_dy->mean; a.bn_invstd = bn_dy->invstd;
+        a.bn_slots = bn_dy->slots; a.bn_nslot = bn_dy->nslot; a.bn_leaky = bn_dy->leaky;
+        a.bn_inv_count = (float)(1.0 / (double)a.M);      // as fv_ew_bn_bwd forms it: rows = B * H * W
+        a.bn_dbeta = bn_dy->dbeta; a.bn_dgamma = bn_dy->dgamma; a.bn_accumulate = bn_dy->accumulate ? 1 : 0;
+    }
     return fv_wgrad_launch(ctx, a);
 }
 
@@ -217,6 +277,44 @@ int fv_bn_bwd_slots(fv_ctx* ctx, const float* g, const float* z, const float* sc
     FV_REQUIRE(ctx, g && z && scale && shift && mean && invstd && dbeta && dgamma && dz && rows > 0, "bn_bwd_slots: NULL buffer");
     return fv_ew_bn_bwd(ctx, g, z, scale, shift, mean, invstd, rows, C, leaky, nullptr, nullptr, dbeta, dgamma, dz, slots, nslot,
                         reduced != 0);
+}
+
+int fv_conv2d_forward_slots_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky,
+                                  const float* w, int B, int H, int W, int cin, int cout, int ksize, int stride, float* z, double* slots,
+                                  int nslot) {
+    if (!ctx) return FV_ERR_INVALID;
+    if (int rc = slots_ok(ctx, slots, nslot, cout, "conv2d_forward_slots_bn_in")) return rc;
+    FV_REQUIRE(ctx, z_in && in_scale && in_shift && w && z, "conv2d_forward_slots_bn_in: NULL buffer");
+    FV_REQUIRE(ctx, fv_op_conv_forward_takes_bn_in(ctx, B, H, W, cin, cout, ksize, stride),
+               "conv2d_forward_slots_bn_in: only the halo kernel applies BN on load (3x3, 32 -> 64 channels, stride 1 or 2, option "
+               "conv_halo); it does not take B=%d H=%d W=%d cin=%d cout=%d k=%d s=%d", B, H, W, cin, cout, ksize, stride);
+    const FvBnIn bi{in_scale, in_shift, leaky};
+    return fv_op_conv_forward(ctx, z_in, w, B, H, W, cin, cout, ksize, stride, FV_EPI_STATS, nullptr, nullptr, 0.f, nullptr, z, nullptr,
+                              nullptr, 1, slots, nslot, &bi);
+}
+
+int fv_conv2d_wgrad_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky, const float* dy,
+                          int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride, float* dw) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, z_in && in_scale && in_shift && dy && dw, "conv2d_wgrad_bn_in: NULL buffer");
+    FV_REQUIRE(ctx, fv_op_conv_wgrad_takes_bn_in(ctx, B, H, W, cin, cout, dy_stride, ksize, stride),
+               "conv2d_wgrad_bn_in: only the halo kernel applies BN on load (3x3, 32 -> 64 channels, stride 1 or 2, option "
+               "wgrad_fused_taps); it does not take B=%d H=%d W=%d cin=%d cout=%d k=%d s=%d", B, H, W, cin, cout, ksize, stride);
+    const FvBnIn bi{in_scale, in_shift, leaky};
+    return fv_op_conv_wgrad(ctx, z_in, dy, B, H, W, cin, cout, dy_stride, ksize, stride, dw, &bi);
+}
+
+int fv_conv2d_wgrad_bn_bwd(fv_ctx* ctx, const float* x, const float* g, const float* z, const float* scale, const float* shift,
+                           const float* mean, const float* invstd, float leaky, const double* slots, int nslot, int B, int H, int W,
+                           int cin, int cout, int ksize, int stride, int accumulate, float* dbeta, float* dgamma, float* dw) {
+    if (!ctx) return FV_ERR_INVALID;
+    if (int rc = slots_ok(ctx, slots, nslot, cout, "conv2d_wgrad_bn_bwd")) return rc;
+    FV_REQUIRE(ctx, x && g && z && scale && shift && mean && invstd && dbeta && dgamma && dw, "conv2d_wgrad_bn_bwd: NULL buffer");
+    FV_REQUIRE(ctx, fv_op_conv_wgrad_takes_bn_dy(ctx, B, H, W, cin, cout, cout, ksize, stride),
+               "conv2d_wgrad_bn_bwd: only the first layer's halo kernel applies the BN-backward on load (3x3 stride 1, 3 -> 32 channels, "
+               "option wgrad_fused_taps); it does not take B=%d H=%d W=%d cin=%d cout=%d k=%d s=%d", B, H, W, cin, cout, ksize, stride);
+    const FvBnDy bd{z, scale, shift, mean, invstd, slots, nslot, leaky, dbeta, dgamma, accumulate != 0};
+    return fv_op_conv_wgrad(ctx, x, g, B, H, W, cin, cout, cout, ksize, stride, dw, nullptr, &bd);
 }
 
 int fv_mse_loss_grad(fv_ctx* ctx, const float* yp, const float* yt, int rows, int C, int c_pad, float* loss, float* dy,

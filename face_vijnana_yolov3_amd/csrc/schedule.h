@@ -216,15 +216,43 @@ struct Train {
     bool accumulate_bn = false;   // d-beta / d-gamma are added to `grads` (towers sharing one BN layer), not stored
 };
 
+// Option "early_bn_fused" (DESIGN.md 4.3): where the readers of a(l - 1) are halo kernels, which stage every input element once,
+// they apply layer l - 1's scale/shift + LeakyReLU while staging z(l - 1), and a(l - 1) is not written at all when BOTH its
+// readers do: the forward and the weight-gradient of layer l.  That is a(0) and a(2) in all three graphs (conv_1 and conv_3, the
+// 32 -> 64 channel 3x3 layers); no skip, route or head reads those two.  Decided from the launchers' own predicates under the
+// context's options, the same way in the forward and the backward pass of one call.
+struct EarlyIn {
+    bool fwd = false, wgrad = false;   // layer l's forward / weight-gradient reads z(l - 1)
+    bool virt() const { return fwd && wgrad; }
+};
+EarlyIn early_in(const Train& t, int l, const float* in) {
+    EarlyIn e;
+    if (l < 1 || l >= (int)t.L.size() || !t.ctx->early_bn) return e;
+    const auto &d = t.L[l], &dp = t.L[l - 1];
+    // the input is a(l - 1) of a BN layer without a residual add, and not the skip kept for a residual block
+    if (!d.has_bn || !dp.has_bn || dp.role == 2 || d.role == 1 || in != t.k.a[l - 1]) return e;
+    const int H = t.S / d.in_div;
+    e.fwd = (t.ctx->early_bn & FV_EARLY_FWD) && fv_op_conv_forward_takes_bn_in(t.ctx, t.B, H, H, d.cin, d.cout, d.ksize, d.stride);
+    e.wgrad = (t.ctx->early_bn & FV_EARLY_WGRAD) && fv_op_conv_wgrad_takes_bn_in(t.ctx, t.B, H, H, d.cin, d.cout, d.cout, d.ksize, d.stride);
+    return e;
+}
+
 // Training forward of BN layer l: the conv adds its column sums to the fp64 accumulator slots and the normalise pass reduces
-// them itself -- two launches per layer (the per-operator API keeps the partial-row form + fv_bn_finalize).
+// them itself -- two launches per layer (the per-operator API keeps the partial-row form + fv_bn_finalize).  `in` is a(l - 1) as
+// the caller's graph names it; a(l) stays unwritten when layer l + 1 reads z(l) in both passes (the caller hands a(l) on as ever).
 int train_bn_forward(const Train& t, int l, const float* in, const float* w, const float* skip) {
     const auto& d = t.L[l];
     const int H = t.S / d.in_div, Ho = t.S / d.out_div;
     const long long rows = (long long)t.B * Ho * Ho;
     const int ns = fv_ew_bn_stat_slots(d.cout);
-    if (int rc = fv_op_conv_forward(t.ctx, in, w, t.B, H, H, d.cin, d.cout, d.ksize, d.stride, FV_EPI_STATS, nullptr, nullptr, 0.f, nullptr,
-                                    t.k.z[l], nullptr, nullptr, 1, t.k.slots[l], ns)) return rc;
+    const bool from_z = early_in(t, l, in).fwd;
+    const FvBnIn bi{from_z ? t.k.scale[l - 1] : nullptr, from_z ? t.k.shift[l - 1] : nullptr, LEAKY};
+    if (int rc = fv_op_conv_forward(t.ctx, from_z ? t.k.z[l - 1] : in, w, t.B, H, H, d.cin, d.cout, d.ksize, d.stride, FV_EPI_STATS, nullptr,
+                                    nullptr, 0.f, nullptr, t.k.z[l], nullptr, nullptr, 1, t.k.slots[l], ns, from_z ? &bi : nullptr)) return rc;
+    if (!skip && early_in(t, l + 1, t.k.a[l]).virt())
+        return fv_ew_bn_stats_publish(t.ctx, t.k.slots[l], ns, (double)rows, t.params + d.gamma_off, t.params + d.beta_off, BN_EPS,
+                                      BN_MOMENTUM, t.k.mean[l], t.k.invstd[l], t.k.scale[l], t.k.shift[l], t.bn_state + d.mean_off,
+                                      t.bn_state + d.var_off, d.cout);
     return fv_ew_bn_act_stats(t.ctx, t.k.z[l], t.k.slots[l], ns, (double)rows, t.params + d.gamma_off, t.params + d.beta_off, BN_EPS,
                               BN_MOMENTUM, t.k.mean[l], t.k.invstd[l], t.k.scale[l], t.k.shift[l], t.bn_state + d.mean_off,
                               t.bn_state + d.var_off, skip, t.k.a[l], rows, d.cout, LEAKY);
@@ -271,21 +299,22 @@ struct WgradPipe {
         return FV_OK;
     }
     // weight-gradient of layer l from its input xin and its output gradient dy (rows of ndy floats), in the current slot
-    int submit(int l, const float* xin, const float* dy, int ndy) {
+    // (bn_in: xin is z(l - 1), normalised on load; bn_dy: dy is g(l) and the kernel forms dz(l) on load and writes d-beta / d-gamma)
+    int submit(int l, const float* xin, const float* dy, int ndy, const FvBnIn* bn_in = nullptr, const FvBnDy* bn_dy = nullptr) {
         fv_ctx* ctx = t.ctx;
         const auto& d = t.L[l];
         const int H = t.S / d.in_div, s = slot;
         const int64_t cnt = (int64_t)d.cout * d.ksize * d.ksize * d.cin + (d.has_bn ? 2 : 1) * d.cout;
         slot ^= 1;
         if (!ov) {
-            if (int rc = fv_op_conv_wgrad(ctx, xin, dy, t.B, H, H, d.cin, d.cout, ndy, d.ksize, d.stride, t.grads + d.w_off)) return rc;
+            if (int rc = fv_op_conv_wgrad(ctx, xin, dy, t.B, H, H, d.cin, d.cout, ndy, d.ksize, d.stride, t.grads + d.w_off, bn_in, bn_dy)) return rc;
             if (on_bucket) on_bucket(user, d.w_off, cnt);
             return FV_OK;
         }
         FV_HIP(ctx, hipEventRecord(ctx->ev_dz[s], main_stream));
         FV_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_dz[s], 0));
         ctx->stream = ctx->side;
-        const int rc = fv_op_conv_wgrad(ctx, xin, dy, t.B, H, H, d.cin, d.cout, ndy, d.ksize, d.stride, t.grads + d.w_off);
+        const int rc = fv_op_conv_wgrad(ctx, xin, dy, t.B, H, H, d.cin, d.cout, ndy, d.ksize, d.stride, t.grads + d.w_off, bn_in, bn_dy);
         ctx->stream = main_stream;
         if (rc) return rc;
         // ev_wg is recorded BEFORE an early callback: it guards the reuse of the dz buffer, which needs the weight-gradient alone --
@@ -315,7 +344,14 @@ int linear_layer_backward(WgradPipe& pipe, int l, int lin, const float* dy, int 
 }
 
 // BN layer l: its output gradient g (d-beta/d-gamma already reduced into its slots unless !reduced) -> dz -> dW (side stream);
-// then, unless g_out is NULL, the data-gradient into g_out (+ addend), reducing for layer lred.
+// then, unless g_out is NULL, the data-gradient into g_out (+ addend), reducing for layer lred.  xin is a(l - 1) as the graph names
+// it (the weight-gradient reads z(l - 1) instead where early_in says so).
+//
+// A layer without a data-gradient whose reduction is done (the first layer) needs dz for its weight-gradient alone: with option
+// "early_bn_fused" wgrad0_mfma.hip forms it on load from g and z, and no dz is written.  That launch reads g -- one of the
+// caller's gradient buffers -- and z(l) on the SIDE stream, so the compute stream waits for it here, before anything after this
+// layer can rewrite either (both outstanding weight-gradients are joined, the older first: ranges stay in descending order).
+// d-beta / d-gamma then come from the side stream together with dW; the layer's range is reported after ev_wg as ever.
 int bn_layer_backward(WgradPipe& pipe, int l, const float* g, bool reduced, const float* xin, float* g_out, const float* addend,
                       int lred) {
     const Train& t = pipe.t;
@@ -323,11 +359,21 @@ int bn_layer_backward(WgradPipe& pipe, int l, const float* g, bool reduced, cons
     const int H = t.S / d.in_div, Ho = t.S / d.out_div;
     const long long rows = (long long)t.B * Ho * Ho;
     if (int rc = pipe.join(pipe.slot)) return rc;
+    const bool from_z = early_in(t, l, xin).wgrad;
+    const FvBnIn bi{from_z ? t.k.scale[l - 1] : nullptr, from_z ? t.k.shift[l - 1] : nullptr, LEAKY};
+    if (from_z) xin = t.k.z[l - 1];
+    if (!g_out && reduced && (t.ctx->early_bn & FV_EARLY_DZ0) &&
+        fv_op_conv_wgrad_takes_bn_dy(t.ctx, t.B, H, H, d.cin, d.cout, d.cout, d.ksize, d.stride)) {
+        const FvBnDy bd{t.k.z[l], t.k.scale[l], t.k.shift[l], t.k.mean[l], t.k.invstd[l], t.k.bslots[l], fv_ew_bn_stat_slots(d.cout), LEAKY,
+                        t.grads + d.beta_off, t.grads + d.gamma_off, t.accumulate_bn};
+        if (int rc = pipe.submit(l, xin, g, d.cout, from_z ? &bi : nullptr, &bd)) return rc;
+        return pipe.finish();
+    }
     float* dz = pipe.dz[pipe.slot];
     if (int rc = fv_ew_bn_bwd(t.ctx, g, t.k.z[l], t.k.scale[l], t.k.shift[l], t.k.mean[l], t.k.invstd[l], rows, d.cout, LEAKY, nullptr,
                               nullptr, t.grads + d.beta_off, t.grads + d.gamma_off, dz, t.k.bslots[l], fv_ew_bn_stat_slots(d.cout),
                               reduced, t.accumulate_bn)) return rc;
-    if (int rc = pipe.submit(l, xin, dz, d.cout)) return rc;
+    if (int rc = pipe.submit(l, xin, dz, d.cout, from_z ? &bi : nullptr)) return rc;
     if (!g_out) return FV_OK;
     FvBnRed b;
     return fv_op_conv_dgrad(t.ctx, dz, t.k.wt[l], t.B, H, H, d.cin, d.cout, d.ksize, d.stride, addend, g_out, bn_red(t, lred, b));

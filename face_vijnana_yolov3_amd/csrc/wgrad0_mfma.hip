@@ -10,7 +10,16 @@
 // 32 k-pairs, one MFMA each: A' = dy[pixel][n], B' = the lane's patch slot (tap, channel) read from the halo at a per-lane
 // constant + compile-time offset (slots 27..31 read the zero pad word).  Waves never exchange partial sums: each adds its
 // own 32 x 27 tile with float atomics when its workgroup has walked its unit range (the caller zeroes dw once per step).
+//
+// Fused BN-backward apply (a.bn_z): the first layer has no data-gradient, so this kernel is the only reader of its dz.  In
+// this mode dy is g (the gradient of the layer's activation) and the kernel loads the g tile and the z tile and stages
+// dz = fv_bn_bwd_dz(g, z, ...) -- what bn_bwd_apply_slots_kernel would have written, bit for bit; the kernel's vector units
+// are idle otherwise.  Every workgroup first sums the layer's d-beta / d-gamma slots in that kernel's order and workgroup 0
+// writes them out.  A thread stages one fixed group of four channels (NTH is a multiple of 8): its constants live in
+// registers.  Pixels beyond the lattice must stage 0.0, which the formula does not give for g = z = 0: issue() leaves a
+// validity mask for stage().
 #include "conv.h"
+#include "elementwise.h"
 
 namespace {
 
@@ -47,6 +56,33 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
     // zero pad word of every halo pixel (never overwritten)
     for (int i = tid; i < HR * HC; i += NTH) x_l[i * 4 + 3] = 0.0f;
 
+    static_assert(NTH == 256 && NTH % 8 == 0, "fv_bn_slot_totals is a 256-thread reduction; a thread stages one channel group");
+    const bool bn = a.bn_z != nullptr;
+    const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(bn ? a.bn_z : a.dy), 0, (int)((unsigned)a.M * a.Ndy * 4u), 0x00020000);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 ksc = zero4, ksh = zero4, kmu = zero4, kis = zero4, kdb = zero4, kdg = zero4;
+    if (bn) {
+        // d-beta / d-gamma totals of the 32 channels, through the dy tile's LDS (nothing is staged yet)
+        double (*s_part)[256] = reinterpret_cast<double (*)[256]>(dy_l);
+        float* s_tot = dy_l + 2 * 256 * 2;                                    // [2][CN], behind s_part
+        double sa, sb;
+        fv_bn_slot_totals(a.bn_slots, a.bn_nslot, CN, tid, s_part, sa, sb);
+        if (tid < CN) {
+            s_tot[tid] = (float)sa; s_tot[CN + tid] = (float)sb;
+            if (blockIdx.x == 0) {
+                if (a.bn_accumulate) { a.bn_dbeta[tid] += (float)sa; a.bn_dgamma[tid] += (float)sb; }
+                else { a.bn_dbeta[tid] = (float)sa; a.bn_dgamma[tid] = (float)sb; }
+            }
+        }
+        __syncthreads();
+        const int c = (tid & 7) * 4;
+        ksc = *reinterpret_cast<const float4*>(a.bn_scale + c); ksh = *reinterpret_cast<const float4*>(a.bn_shift + c);
+        kmu = *reinterpret_cast<const float4*>(a.bn_mean + c); kis = *reinterpret_cast<const float4*>(a.bn_invstd + c);
+        kdb = *reinterpret_cast<const float4*>(s_tot + c); kdg = *reinterpret_cast<const float4*>(s_tot + CN + c);
+        __syncthreads();                                                      // before stage() overwrites the tile
+    }
+
     unsigned dy_rel[NDY]; int dy_rc[NDY];        // slot p: pixel (row << 8 | col) of the unit, byte offset relative to the unit origin
 #pragma unroll
     for (int p = 0; p < NDY; ++p) {
@@ -68,18 +104,22 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 
-    u32x4 ry[NDY];
+    u32x4 ry[NDY], rz[NDY];
     unsigned rx[NX];
+    unsigned ry_ok = 0;                          // bit p: slot p of the dy tile lies inside the lattice
     auto issue = [&](int u) {
         const int uc = u % units_w, t = u / units_w, ur = t % units_h, b = t / units_h;
         const int h0 = ur * UR, w0 = uc * UC;
         const unsigned base_y = (unsigned)(((b * a.Hl + h0) * a.Wl + w0) * a.Ndy) * 4u;
         const unsigned base_x = (unsigned)(((b * a.Hin + h0 - 1) * a.Win + w0 - 1) * CI) * 4u;      // modular at the image border
         const int lim_r = a.Hl - h0, lim_c = a.Wl - w0;
+        ry_ok = 0;
 #pragma unroll
         for (int p = 0; p < NDY; ++p) {
             const bool ok = ((dy_rc[p] >> 8) < lim_r) & ((dy_rc[p] & 255) < lim_c);
             ry[p] = __builtin_amdgcn_raw_buffer_load_b128(yr, ok ? base_y + dy_rel[p] : OOB, 0, 0);
+            if (bn) rz[p] = __builtin_amdgcn_raw_buffer_load_b128(zr, ok ? base_y + dy_rel[p] : OOB, 0, 0);   // (Ndy == CN: z has g's layout)
+            ry_ok |= (unsigned)ok << p;
         }
 #pragma unroll
         for (int p = 0; p < NX; ++p) {
@@ -91,7 +131,18 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
 #pragma unroll
         for (int p = 0; p < NDY; ++p) {
             const int f = tid + NTH * p;
-            *reinterpret_cast<u32x4*>(&dy_l[(f >> 3) * LDY + (f & 7) * 4]) = ry[p];
+            u32x4 v = ry[p];
+            if (bn) {
+                const u32x4 zv = rz[p];
+                const float4 o = fv_bn_bwd_dz4(
+                    make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])),
+                    make_float4(__uint_as_float(zv[0]), __uint_as_float(zv[1]), __uint_as_float(zv[2]), __uint_as_float(zv[3])),
+                    ksc, ksh, kmu, kis, kdb, kdg, a.bn_inv_count, a.bn_leaky);
+                const bool ok = (ry_ok >> p) & 1;
+                v[0] = ok ? __float_as_uint(o.x) : 0u; v[1] = ok ? __float_as_uint(o.y) : 0u;
+                v[2] = ok ? __float_as_uint(o.z) : 0u; v[3] = ok ? __float_as_uint(o.w) : 0u;
+            }
+            *reinterpret_cast<u32x4*>(&dy_l[(f >> 3) * LDY + (f & 7) * 4]) = v;
         }
 #pragma unroll
         for (int p = 0; p < NX; ++p)
@@ -137,6 +188,10 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
 }  // namespace
 
 bool fv_wgrad0_ok(const FvWgradArgs& a) {
+    if (a.x_scale || a.x_shift) return false;
+    // fused BN-backward apply: z is read at g's offsets, so g has exactly the layer's 32 channels per pixel
+    if (a.bn_z && !(a.Ndy == CN && a.bn_scale && a.bn_shift && a.bn_mean && a.bn_invstd && a.bn_slots && a.bn_nslot >= 1 &&
+                    a.bn_dbeta && a.bn_dgamma)) return false;
     return a.Cin == CI && a.N == CN && a.Ndy >= CN && (a.Ndy & 3) == 0 && a.is == 1 && a.Hl == a.Hin && a.Wl == a.Win && a.taps.n == 9;
 }
 
@@ -146,7 +201,7 @@ int fv_wgrad0_launch(fv_ctx* ctx, const FvWgradArgs& a) {
     FV_REQUIRE(ctx, n_units < (1ll << 30), "wgrad0: too many units");
     const int grid = n_units < 768 ? (int)n_units : 768;   // three workgroups per CU, contiguous unit ranges
     FvProfScope ps(ctx, "wgrad0_kernel", a.alg_flops,
-                   4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + (double)a.M * a.N + (double)a.N * 27));
+                   4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + (double)a.M * a.N * (a.bn_z ? 2 : 1) + (double)a.N * 27));
     hipLaunchKernelGGL(wgrad0_kernel, dim3(grid), dim3(NTH), 0, ctx->stream, a, units_w, units_h, (int)n_units);
     FV_LAUNCH_CHECK(ctx);
     return FV_OK;

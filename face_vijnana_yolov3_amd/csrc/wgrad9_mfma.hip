@@ -16,7 +16,11 @@
 //     barriers; out-of-image halo pixels and pixels beyond the lattice come back as zeros from the buffer descriptor
 //   * a workgroup walks a contiguous range of units (grid = 256 workgroups, one per CU) and adds its 64 x 288
 //     partial tile with float atomics at the end, like the generic kernel (the caller zeroes dw once per step)
+//   * BN-on-load (a.x_scale): x is the producing layer's raw conv output and stage() writes LeakyReLU(x * scale + shift), once
+//     per halo element and unit, exactly as conv9_mfma.hip does (a thread's slots share one group of four channels; halo
+//     slots outside the image stay 0.0 through the validity mask issue() leaves)
 #include "conv.h"
+#include "elementwise.h"
 
 namespace {
 
@@ -77,7 +81,15 @@ __global__ __launch_bounds__(NTH, 1) void wgrad9_kernel(const FvWgradArgs a, int
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
 
+    static_assert(NTH % 8 == 0 && NX <= 32, "a thread stages one channel group of x; one validity bit per slot");
+    const bool bn = a.x_scale != nullptr;
+    float4 bsc = make_float4(0.f, 0.f, 0.f, 0.f), bsh = bsc;
+    if (bn) {
+        bsc = *reinterpret_cast<const float4*>(a.x_scale + (tid & 7) * 4);
+        bsh = *reinterpret_cast<const float4*>(a.x_shift + (tid & 7) * 4);
+    }
     u32x4 ry[NDY], rx[NX];
+    unsigned rx_ok = 0;                     // bit p: slot p of the halo in rx lies inside the image
     // unit u -> image, first output row / column; loads of its dy tile and x halo into registers
     auto issue = [&](int u) {
         const int uc = u % units_w, t = u / units_w, ur = t % units_h, b = t / units_h;
@@ -91,10 +103,12 @@ __global__ __launch_bounds__(NTH, 1) void wgrad9_kernel(const FvWgradArgs a, int
             const bool ok = ((dy_rc[p] >> 8) < lim_r) & ((dy_rc[p] & 255) < lim_c);
             ry[p] = __builtin_amdgcn_raw_buffer_load_b128(yr, ok ? base_y + dy_rel[p] : OOB, 0, 0);
         }
+        rx_ok = 0;
 #pragma unroll
         for (int p = 0; p < NX; ++p) {
             const bool ok = ((unsigned)(ih0 + (x_rc[p] >> 8)) < (unsigned)a.Hin) & ((unsigned)(iw0 + (x_rc[p] & 255)) < (unsigned)a.Win);
             rx[p] = __builtin_amdgcn_raw_buffer_load_b128(xr, ok ? base_x + x_rel[p] : OOB, 0, 0);
+            rx_ok |= (unsigned)ok << p;
         }
     };
     auto stage = [&]() {     // (LDS addresses recomputed here: two fewer registers per slot than keeping them)
@@ -106,7 +120,15 @@ __global__ __launch_bounds__(NTH, 1) void wgrad9_kernel(const FvWgradArgs a, int
 #pragma unroll
         for (int p = 0; p < NX; ++p) {
             const int f = tid + NTH * p;
-            if (NTH * p + NTH <= NXF || f < NXF) *reinterpret_cast<u32x4*>(&x_l[(f >> 3) * LDX + (f & 7) * 4]) = rx[p];
+            u32x4 v = rx[p];
+            if (bn) {
+                const float4 y = fv_bn_leaky4(make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])),
+                                              bsc, bsh, a.x_leaky);
+                const bool ok = (rx_ok >> p) & 1;
+                v[0] = ok ? __float_as_uint(y.x) : 0u; v[1] = ok ? __float_as_uint(y.y) : 0u;
+                v[2] = ok ? __float_as_uint(y.z) : 0u; v[3] = ok ? __float_as_uint(y.w) : 0u;
+            }
+            if (NTH * p + NTH <= NXF || f < NXF) *reinterpret_cast<u32x4*>(&x_l[(f >> 3) * LDX + (f & 7) * 4]) = v;
         }
     };
 
@@ -158,6 +180,7 @@ __global__ __launch_bounds__(NTH, 1) void wgrad9_kernel(const FvWgradArgs a, int
 bool fv_wgrad9_ok(const FvWgradArgs& a) {
     if (a.Cin != CC || a.N != CN || a.Ndy < CN || (a.Ndy & 3) || a.Tw != 9 || a.taps.n != 9) return false;
     if (a.is != 1 && a.is != 2) return false;
+    if ((a.x_scale != nullptr) != (a.x_shift != nullptr) || a.bn_z) return false;
     if (a.Hl * a.is != a.Hin || a.Wl * a.is != a.Win) return false;
     for (int t = 0; t < 9; ++t)
         if (a.taps.dh[t] != t / 3 - 1 || a.taps.dw[t] != t % 3 - 1 || a.taps.wslot[t] != t) return false;

@@ -391,14 +391,18 @@ int fv_wgrad_launch(fv_ctx* ctx, const FvWgradArgs& a) {
     FV_REQUIRE(ctx, (long long)a.B * a.Hin * a.Win * a.Cin < (1ll << 29) && (long long)a.M * a.Ndy < (1ll << 29),
                "wgrad: tensor exceeds 2^29 elements (2 GiB buffer descriptor)");
     if (a.Cin % 32 != 0) {
+        FV_REQUIRE(ctx, !a.x_scale, "wgrad: BN-on-load is for the 32-channel halo kernel (wgrad9_mfma.hip)");
         FV_REQUIRE(ctx, 9 * a.Cin <= 32 && a.is == 1 && a.Hl == a.Hin && a.Wl == a.Win && a.taps.n == 9,
                    "wgrad: Cin=%d only supported as 3x3 stride-1 pad-1 with 9*Cin<=32", a.Cin);
         if (ctx->wgrad_fused_taps && fv_wgrad0_ok(a)) return fv_wgrad0_launch(ctx, a);
+        FV_REQUIRE(ctx, !a.bn_z, "wgrad: the fused BN-backward apply needs the halo kernel (wgrad0_mfma.hip), which does not take this launch");
         if (a.N > 32) return launch_w<64, 32, false, true>(ctx, a);
         return launch_w<32, 32, false, true>(ctx, a);
     }
     FV_REQUIRE(ctx, a.taps.n >= 1 && a.taps.n <= 9, "wgrad: bad tap count");
+    FV_REQUIRE(ctx, !a.bn_z, "wgrad: the fused BN-backward apply is the first layer's (wgrad0_mfma.hip)");
     if (ctx->wgrad_fused_taps && fv_wgrad9_ok(a)) return fv_wgrad9_launch(ctx, a);
+    FV_REQUIRE(ctx, !a.x_scale, "wgrad: BN-on-load needs the halo kernel (wgrad9_mfma.hip), which does not take this launch");
     if (ctx->wgrad_fused_taps && fv_wgrad1_ok(a)) return fv_wgrad1_launch(ctx, a);
     if (a.N >= 128 && a.Cin % 128 == 0) return launch_w<128, 128, true, false>(ctx, a);
     const bool n64 = a.N > 32, c64 = a.Cin % 64 == 0;

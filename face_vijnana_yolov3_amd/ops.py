@@ -152,6 +152,45 @@ def bn_bwd_slots(ctx, g, z, scale, shift, mean, invstd, slots, reduced, leaky=0.
     return dz, dgamma, dbeta
 
 
+# ------------------------------------------------------------------ the BN passes folded into halo kernels (option early_bn_fused)
+def conv2d_forward_slots_bn_in(ctx, z_in, in_scale, in_shift, w, stride, slots, leaky=0.1):
+    """conv2d_forward_slots of leaky(z_in*in_scale+in_shift), formed while the halo kernel stages z_in (3x3, 32 -> 64 channels)."""
+    B, H, W, cin = z_in.shape
+    cout, k = w.shape[0], w.shape[1]
+    z = torch.empty((B, H // stride, W // stride, cout), dtype=torch.float32, device=z_in.device)
+    rc = lib().fv_conv2d_forward_slots_bn_in(ctx.handle, ptr(z_in.contiguous()), ptr(in_scale), ptr(in_shift), leaky, ptr(w.contiguous()),
+                                             B, H, W, cin, cout, k, stride, ptr(z), ptr(slots), slots.shape[0])
+    ctx.check(rc, 'fv_conv2d_forward_slots_bn_in')
+    return z
+
+
+def conv2d_wgrad_bn_in(ctx, z_in, in_scale, in_shift, dy, cout, ksize, stride=1, leaky=0.1):
+    """conv2d_wgrad with x = leaky(z_in*in_scale+in_shift) formed on load (3x3, 32 -> 64 channels)."""
+    B, H, W, cin = z_in.shape
+    dw = torch.zeros((cout, ksize, ksize, cin), dtype=torch.float32, device=z_in.device)
+    rc = lib().fv_conv2d_wgrad_bn_in(ctx.handle, ptr(z_in.contiguous()), ptr(in_scale), ptr(in_shift), leaky, ptr(dy.contiguous()), B, H, W,
+                                     cin, cout, dy.shape[3], ksize, stride, ptr(dw))
+    ctx.check(rc, 'fv_conv2d_wgrad_bn_in')
+    return dw
+
+
+def conv2d_wgrad_bn_bwd(ctx, x, g, z, scale, shift, mean, invstd, slots, dbeta=None, dgamma=None, leaky=0.1):
+    """First layer: bn_bwd_slots(reduced) + conv2d_wgrad in one kernel.  dbeta / dgamma given: the slot sums are ADDED to them.
+    Returns dw, dgamma, dbeta."""
+    B, H, W, cin = x.shape
+    C = z.shape[-1]
+    accumulate = dbeta is not None
+    if not accumulate:
+        dbeta = torch.empty(C, dtype=torch.float32, device=z.device)
+        dgamma = torch.empty_like(dbeta)
+    dw = torch.zeros((C, 3, 3, cin), dtype=torch.float32, device=z.device)
+    rc = lib().fv_conv2d_wgrad_bn_bwd(ctx.handle, ptr(x.contiguous()), ptr(g.contiguous()), ptr(z), ptr(scale), ptr(shift), ptr(mean),
+                                      ptr(invstd), leaky, ptr(slots), slots.shape[0], B, H, W, cin, C, 3, 1, 1 if accumulate else 0,
+                                      ptr(dbeta), ptr(dgamma), ptr(dw))
+    ctx.check(rc, 'fv_conv2d_wgrad_bn_bwd')
+    return dw, dgamma, dbeta
+
+
 def mse_loss_grad(ctx, yp, yt, c_pad=32):
     C = yp.shape[-1]
     rows = yp.numel() // C

@@ -92,6 +92,12 @@ int fv_set_bn_zero_debias_step(fv_ctx* ctx, long long step);
  *                       statistics are the same sums in another (fp64) order.
  *   "conv0_direct"      first layer (3 -> 32 channels) as a direct vector-FMA kernel when W % 32 == 0 and H % 8 == 0 instead of
  *                       the matrix-core gather kernel.  Bit-identical.
+ *   "early_bn_fused"    the BN passes of the first layers folded into their halo-kernel consumers: conv_1 / conv_3 (forward and
+ *                       weight-gradient) read z(0) / z(2) and apply scale/shift + LeakyReLU while staging, so a(0) / a(2) are not
+ *                       written; the first layer's weight-gradient forms dz(0) from g(0) and z(0) while staging, so dz(0) is not
+ *                       written either.  Needs "conv_halo" / "wgrad_fused_taps" (otherwise the passes run as before).  Same bits
+ *                       per element; d-beta / d-gamma of layer 0 are made on the side stream.  0 off, 1 on; for A/B runs of one
+ *                       part an even value selects parts: 2 forward on load, 4 weight-gradient on load, 8 dz(0), or their sums.
  *   "wgrad_fused_taps"  weight-gradients of conv_0 / conv_1 / conv_2 / conv_3 from halo tiles / streaming units (wgrad0, wgrad1,
  *                       wgrad9) instead of the generic kernel.  Same products, other float-atomic summation order.
  * Unknown keys return FV_ERR_INVALID.  The environment variable FV_OPTIONS="key=0,key=1" sets initial values at fv_create. */
@@ -209,6 +215,9 @@ int fv_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float
  * offset_bytes is relative to the workspace pointer given to fv_train_step with the same batch /
  * image_size.  The parity tests read z / scale / shift back to learn which LeakyReLU slope the GPU took
  * for every element, so that the float64 oracle can be evaluated on the same side of each kink. */
+/* With option "early_bn_fused" (the default) the step does not write a of layers 0 and 2 where their readers -- forward and
+ * weight-gradient of conv_1 / conv_3 -- apply the BN on load: the two tensors keep their place in the workspace (its layout does
+ * not depend on the context) but hold no data; z, mean, invstd, scale and shift of those layers are published as ever. */
 int fv_train_workspace_tensor(int batch, int image_size, int layer, int which, size_t* offset_bytes,
                               int64_t* count);
 
@@ -289,6 +298,24 @@ int fv_conv2d_dgrad_bnred(fv_ctx* ctx, const float* dy, const float* w_t, int B,
 int fv_bn_bwd_slots(fv_ctx* ctx, const float* g, const float* z, const float* scale, const float* shift,
                     const float* mean, const float* invstd, int64_t rows, int C, float leaky, double* slots,
                     int nslot, int reduced, float* dbeta, float* dgamma, float* dz);
+/* ---- the BN passes folded into halo kernels (option "early_bn_fused"), as single operators.  Each returns FV_ERR_INVALID when
+ * the halo kernel that has the mode does not take the shape: there is no other implementation to fall back to.
+ * fv_conv2d_forward_slots whose input is LeakyReLU(z_in*in_scale+in_shift), formed while z_in [B][H][W][cin] is staged (zero
+ * padding stays zero): 3x3, 32 -> 64 channels, stride 1 or 2.  z is bit-identical to fv_bn_act + fv_conv2d_forward_slots. */
+int fv_conv2d_forward_slots_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky,
+                                  const float* w, int B, int H, int W, int cin, int cout, int ksize, int stride, float* z,
+                                  double* slots, int nslot);
+/* fv_conv2d_wgrad with the same input transform (same shapes). */
+int fv_conv2d_wgrad_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky,
+                          const float* dy, int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride,
+                          float* dw);
+/* fv_bn_bwd_slots(reduced = 1) + fv_conv2d_wgrad of the first layer (3x3 stride 1, 3 -> 32 channels) in one kernel: dz is formed
+ * from g and z [B][H][W][cout] while they are staged and never stored; d-beta / d-gamma = slot sums, stored or (accumulate != 0)
+ * added to what dbeta / dgamma hold.  dw is ACCUMULATED (zero it first). */
+int fv_conv2d_wgrad_bn_bwd(fv_ctx* ctx, const float* x, const float* g, const float* z, const float* scale, const float* shift,
+                           const float* mean, const float* invstd, float leaky, const double* slots, int nslot, int B, int H,
+                           int W, int cin, int cout, int ksize, int stride, int accumulate, float* dbeta, float* dgamma,
+                           float* dw);
 /* loss = mean((yp-yt)^2) over [rows][C]; dy [rows][c_pad] = 2(yp-yt)/(rows*C) zero padded;
  * dbias[C] = column sums of dy (may be NULL). */
 int fv_mse_loss_grad(fv_ctx* ctx, const float* yp, const float* yt, int rows, int C, int c_pad,
