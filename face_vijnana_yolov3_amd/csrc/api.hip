@@ -58,7 +58,7 @@ FvProfScope::~FvProfScope() {
 
 extern "C" {
 
-int fv_abi_version(void) { return 4; }   // 4: the FaceIdentifier entry points (fv_fid_*); 3: fv_set_option / fv_get_option replace the per-switch setters
+int fv_abi_version(void) { return 4; }   // 4: the FaceIdentifier entry points (fv_fid_*), and additively every entry point since (latest: fv_letterbox_augment_batch); 3: fv_set_option / fv_get_option replace the per-switch setters
 
 // Tuning options (include/fv_hotpath.h, "tuning"): every switch is a bool member of the context; all default to on.
 namespace {

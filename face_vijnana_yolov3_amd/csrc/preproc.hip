@@ -7,6 +7,7 @@
 // bicubic kernel (a = -0.75, half-pixel centres, replicated border) in float32 -- "parity
 // unpinned" against cv2 itself, which is not installed here.
 // HBM-bound: reads each source pixel ~(scale^2 x 16) times through L1/L2, writes 12 B per pixel.
+#include <cmath>
 #include "common.h"
 
 namespace {
@@ -184,6 +185,141 @@ __global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsi
     }
 }
 
+// Training augmentation (hps['augment']): letterbox_crops_kernel for ONE crop per image, letterboxed into a T x T box
+// at (oy, ox) of the otherwise zero S x S canvas, the finished canvas optionally mirrored (x -> S - 1 - x) and the pixel's colour
+// distorted in HSV, in the same pass.  The resampling is letterbox_crops_kernel's -- the same expressions in the same order -- so
+// without colour the box holds that kernel's bits.  A workgroup makes LBA_TW x LBA_TH output pixels: the fp64 source coordinate and
+// the four weights of each of its columns and rows are computed once (80 threads) into LDS; then every thread makes four pixels
+// of one column (64 columns x 4 rows per pass, the passes unrolled so that their loads are in flight together), the tile is staged
+// in LDS and stored as 16-byte chunks on consecutive lanes (768 B per row segment).
+constexpr int LBA_MAX = 64;         // images per launch: the table travels in the kernel arguments (64 x 52 B); longer batches are chunked
+constexpr int LBA_TW = 64, LBA_TH = 16, LBA_ROWS = 4;       // tile; rows per pass (256 threads = 64 columns x 4 rows)
+constexpr int LBA_OUT = -2147483647 - 1;  // a column / row outside the placed content
+struct LbaTable { long long off[LBA_MAX]; int pitch[LBA_MAX], h[LBA_MAX], w[LBA_MAX], w_p[LBA_MAX], h_p[LBA_MAX], top[LBA_MAX],
+                  left[LBA_MAX], mode[LBA_MAX];     // mode: bit 0 = flip, bit 1 = the colour stage runs
+                  float dh[LBA_MAX], sat[LBA_MAX], ex[LBA_MAX]; };
+
+// Darknet's distort_image in float32: clamp, RGB -> HSV (h in turns), h += dh (wrapped), s *= sat, v *= ex, HSV -> RGB, clamp
+__device__ __forceinline__ void lba_colour(float& r, float& g, float& b, float dh, float sat, float ex) {
+    r = fminf(fmaxf(r, 0.f), 1.f); g = fminf(fmaxf(g, 0.f), 1.f); b = fminf(fmaxf(b, 0.f), 1.f);
+    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b)), d = mx - mn;
+    float s = mx == 0.f ? 0.f : d / mx, v = mx, hh = 0.f;
+    if (d != 0.f) hh = r == mx ? (g - b) / d : (g == mx ? 2.f + (b - r) / d : 4.f + (r - g) / d);
+    hh = hh < 0.f ? hh + 6.f : hh;
+    hh = hh / 6.f;
+    hh = hh + dh; hh = hh - floorf(hh);
+    s = s * sat; v = v * ex;
+    const float h6 = 6.f * hh, fl = floorf(h6), f = h6 - fl;
+    const int i = (int)fl % 6;
+    const float p = v * (1.f - s), q = v * (1.f - s * f), t = v * (1.f - s * (1.f - f));
+    switch (i) {
+        case 0: r = v; g = t; b = p; break;
+        case 1: r = q; g = v; b = p; break;
+        case 2: r = p; g = v; b = t; break;
+        case 3: r = p; g = q; b = v; break;
+        case 4: r = t; g = p; b = v; break;
+        default: r = v; g = p; b = q; break;
+    }
+    r = fminf(fmaxf(r, 0.f), 1.f); g = fminf(fmaxf(g, 0.f), 1.f); b = fminf(fmaxf(b, 0.f), 1.f);
+}
+
+__global__ __launch_bounds__(256) void letterbox_augment_kernel(const unsigned char* __restrict__ packed, LbaTable t, int S,
+                                                                float* __restrict__ dst) {
+    __shared__ int col_s[LBA_TW], row_s[LBA_TH];                                  // floor of the source coordinate, or LBA_OUT
+    __shared__ __attribute__((aligned(16))) float col_w[LBA_TW][4], row_w[LBA_TH][4];
+    __shared__ __attribute__((aligned(16))) float out_s[LBA_TH][LBA_TW * 3];
+    const int b = blockIdx.z, x0 = blockIdx.x * LBA_TW, y0 = blockIdx.y * LBA_TH, tid = threadIdx.x;
+    const int h = t.h[b], w = t.w[b], w_p = t.w_p[b], h_p = t.h_p[b], pitch = t.pitch[b], mode = t.mode[b];
+    if (tid < LBA_TW) {
+        const int x = x0 + tid;
+        const int xi = ((mode & 1) ? S - 1 - x : x) - t.left[b];                  // undo the flip, then the placement
+        int s = LBA_OUT;
+        float wx[4] = {0.f, 0.f, 0.f, 0.f};
+        if (x < S && xi >= 0 && xi < w_p) {
+            const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
+            s = (int)floor(fx);
+            cubic_w((float)(fx - s), wx);
+        }
+        col_s[tid] = s;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) col_w[tid][i] = wx[i];
+    } else if (tid < LBA_TW + LBA_TH) {
+        const int j = tid - LBA_TW, y = y0 + j;
+        const int yi = y - t.top[b];
+        int s = LBA_OUT;
+        float wy[4] = {0.f, 0.f, 0.f, 0.f};
+        if (y < S && yi >= 0 && yi < h_p) {
+            const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
+            s = (int)floor(fy);
+            cubic_w((float)(fy - s), wy);
+        }
+        row_s[j] = s;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) row_w[j][i] = wy[i];
+    }
+    __syncthreads();
+    const unsigned char* __restrict__ src = packed + t.off[b];
+    const int lx = tid & (LBA_TW - 1), ly = tid >> 6;
+    const int sx = col_s[lx];
+    const float4 wxv = *reinterpret_cast<const float4*>(col_w[lx]);
+    const float wx[4] = {wxv.x, wxv.y, wxv.z, wxv.w};
+    int xo[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xo[i] = sx == LBA_OUT ? 0 : min(max(sx - 1 + i, 0), w - 1) * 3;
+    // interior columns: the four taps are 12 contiguous bytes of a source row -- one (unaligned) 12-byte load per tap row instead of
+    // twelve byte loads; the values, and the arithmetic on them, are the same
+    const bool inner = sx != LBA_OUT && sx >= 1 && sx + 2 <= w - 1;
+    const float dh = t.dh[b], sat = t.sat[b], ex = t.ex[b];
+#pragma unroll
+    for (int pass = 0; pass < LBA_TH / LBA_ROWS; ++pass) {
+        const int j0 = pass * LBA_ROWS + ly;
+        const int sy = row_s[j0];
+        float r = 0.f, g = 0.f, bl = 0.f;
+        if (sx != LBA_OUT && sy != LBA_OUT) {
+            const float4 wyv = *reinterpret_cast<const float4*>(row_w[j0]);
+            const float wy[4] = {wyv.x, wyv.y, wyv.z, wyv.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int yy = min(max(sy - 1 + j, 0), h - 1);
+                const unsigned char* __restrict__ row = src + (size_t)yy * pitch;
+                float rr = 0.f, gg = 0.f, bb = 0.f;
+                if (inner) {
+                    unsigned v[3];
+                    __builtin_memcpy(v, row + xo[0], 12);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float p0 = (float)((v[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u);
+                        const float p1 = (float)((v[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u);
+                        const float p2 = (float)((v[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u);
+                        rr += wx[i] * p0; gg += wx[i] * p1; bb += wx[i] * p2;
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned char* p = row + xo[i];
+                        rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
+                    }
+                }
+                r += wy[j] * rr; g += wy[j] * gg; bl += wy[j] * bb;
+            }
+            r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); bl *= (1.0f / 255.0f);
+            if (mode & 2) lba_colour(r, g, bl, dh, sat, ex);
+        }
+        out_s[j0][3 * lx] = r; out_s[j0][3 * lx + 1] = g; out_s[j0][3 * lx + 2] = bl;
+    }
+    __syncthreads();
+    // the tile as 16-byte chunks, consecutive lanes on consecutive chunks of a row segment (768 B where the tile is full)
+    constexpr int ROW_Q = LBA_TW * 3 / 4;
+    const int row_q = 3 * min(LBA_TW, S - x0) / 4;                                 // chunks of this tile's row segment (S % 4 == 0)
+#pragma unroll
+    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) {
+        const int rr = q / ROW_Q, k = q - rr * ROW_Q;
+        const int y = y0 + rr;
+        if (y < S && k < row_q)
+            reinterpret_cast<float4*>(dst + (((size_t)b * S + y) * S + x0) * 3)[k] = reinterpret_cast<const float4*>(out_s[rr])[k];
+    }
+}
+
 bool lb_geometry(int h, int w, int S, int* g) {
     int w_p, h_p, pad_t = 0, pad_b = 0, pad_l = 0, pad_r = 0;
     if (w >= h) {   // face_detection.py:120-133
@@ -271,6 +407,54 @@ extern "C" int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int6
         FvProfScope ps(ctx, "letterbox_crops_kernel", 0.0, bytes);
         hipLaunchKernelGGL(letterbox_crops_kernel, dim3((S + 15) / 16, (S + 15) / 16, nc), dim3(256), 0, ctx->stream, packed, t, S,
                            dst + (size_t)c0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+extern "C" int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                          int image_size, const int32_t* place, const float* colour, float* dst) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, packed && offsets && hw && place && dst && n >= 1 && image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
+               "letterbox_augment_batch: bad arguments (image_size a multiple of 4 and dst 16-byte aligned: rows are stored 16 bytes at a time)");
+    const int S = image_size;
+    // every record before anything is enqueued: a bad one leaves dst untouched
+    for (int i = 0; i < n; ++i) {
+        const int H = hw[2 * i], W = hw[2 * i + 1];
+        const int* r = place + 8 * i;
+        const int cy0 = r[0], cx0 = r[1], ch = r[2], cw = r[3], T = r[4], oy = r[5], ox = r[6], flip = r[7];
+        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[i] >= 0, "letterbox_augment_batch: bad image %d", i);
+        FV_REQUIRE(ctx, ch >= 1 && cw >= 1 && cy0 >= 0 && cx0 >= 0 && cy0 <= H - ch && cx0 <= W - cw,
+                   "letterbox_augment_batch: crop (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", cy0, cx0, ch, cw, i, H, W);
+        FV_REQUIRE(ctx, T >= 1 && T <= S && oy >= 0 && ox >= 0 && oy <= S - T && ox <= S - T,
+                   "letterbox_augment_batch: image %d: box of side %d at (y %d, x %d) outside the %d x %d canvas", i, T, oy, ox, S, S);
+        int g[6];
+        FV_REQUIRE(ctx, lb_geometry(ch, cw, T, g), "letterbox_augment_batch: image %d: crop %d x %d too elongated for a box of side %d", i, ch, cw, T);
+        FV_REQUIRE(ctx, flip == 0 || flip == 1, "letterbox_augment_batch: image %d: flip %d is neither 0 nor 1", i, flip);
+        if (colour)
+            FV_REQUIRE(ctx, std::isfinite(colour[3 * i]) && std::isfinite(colour[3 * i + 1]) && std::isfinite(colour[3 * i + 2]),
+                       "letterbox_augment_batch: image %d: colour parameters are not finite", i);
+    }
+    for (int b0 = 0; b0 < n; b0 += LBA_MAX) {
+        const int nb = n - b0 < LBA_MAX ? n - b0 : LBA_MAX;
+        LbaTable t{};
+        double bytes = 0.0;
+        for (int i = 0; i < nb; ++i) {
+            const int W = hw[2 * (b0 + i) + 1];
+            const int* r = place + 8 * (b0 + i);
+            const float* c = colour ? colour + 3 * (b0 + i) : nullptr;
+            int g[6];
+            lb_geometry(r[2], r[3], r[4], g);
+            t.off[i] = offsets[b0 + i] + ((long long)r[0] * W + r[1]) * 3; t.pitch[i] = W * 3;
+            t.h[i] = r[2]; t.w[i] = r[3]; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.top[i] = r[5] + g[2]; t.left[i] = r[6] + g[4];
+            const bool col = c && !(c[0] == 0.f && c[1] == 1.f && c[2] == 1.f);       // exactly (0, 1, 1): the stage is skipped
+            t.mode[i] = r[7] | (col ? 2 : 0);
+            t.dh[i] = col ? c[0] : 0.f; t.sat[i] = col ? c[1] : 1.f; t.ex[i] = col ? c[2] : 1.f;
+            bytes += (double)r[2] * r[3] * 3 + 12.0 * S * S;
+        }
+        FvProfScope ps(ctx, "letterbox_augment_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_augment_kernel, dim3((S + LBA_TW - 1) / LBA_TW, (S + LBA_TH - 1) / LBA_TH, nb), dim3(256), 0,
+                           ctx->stream, packed, t, S, dst + (size_t)b0 * S * S * 3);
         FV_LAUNCH_CHECK(ctx);
     }
     return FV_OK;

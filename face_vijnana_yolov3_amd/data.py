@@ -31,27 +31,56 @@ def letterbox_geometry(h, w, image_size):
     return w_p, h_p, pad_t, pad_b, pad_l, pad_r
 
 
-def encode_gt(faces, h, w, image_size=416, grid=13, channels=6):
-    """Ground-truth tensor of one image (face_detection.py:150-202).
+def identity_placement(h, w, image_size):
+    """The placement of today's letterbox: the whole image in the whole canvas, not mirrored."""
+    return (0, 0, int(h), int(w), int(image_size), 0, 0, 0)
 
-    faces: array-like (n,4) of FACE_X, FACE_Y, FACE_WIDTH, FACE_HEIGHT in csv order; rows with
-    any value <= 0 are skipped; later rows overwrite earlier ones in the same cell."""
-    cell = image_size // grid
-    _, _, pad_t, _, pad_l, _ = letterbox_geometry(h, w, image_size)
-    gt = np.zeros((grid, grid, channels), np.float64)
-    m = w if w >= h else h
-    ox, oy = (0, pad_t) if w >= h else (pad_l, 0)
+
+def _placed_centres(faces, h, w, image_size, placement):
+    """The corner / centre arithmetic both encoders share (face_detection.py:150-202), under a placement
+    (cy0, cx0, ch, cw, T, oy, ox, flip) -- the ch x cw crop at (cy0, cx0) letterboxed into the T x T box at (oy, ox) of the S x S
+    canvas, the canvas then mirrored when flip -- or under None, today's letterbox of the whole image.  Yields
+    (x1, y1, x2, y2, xc, yc, m, T) per kept face.  With m = max(cw, ch) and (pad_t, pad_l) the crop's letterbox padding in T:
+        x1p = int((x1 - cx0) / m * T) + ox + pad_l,  x2p, y1p, y2p likewise,  xc = (x1p + x2p) // 2,  yc = (y1p + y2p) // 2.
+    Under a placement a face is kept only when (xc, yc) lies inside the placed content rectangle (its box is NOT clipped to the
+    crop); a flip then maps xc to S - 1 - xc and changes nothing else.  With identity_placement(h, w, S) every expression
+    reduces to the one of placement None, bit for bit: x1 - 0 is x1, the single non-zero pad is the old offset and T is S."""
+    S = image_size
+    placed = placement is not None
+    cy0, cx0, ch, cw, T, oy, ox, flip = placement if placed else identity_placement(h, w, S)
+    w_p, h_p, pad_t, _, pad_l, _ = letterbox_geometry(ch, cw, T)
+    m = cw if cw >= ch else ch
+    left, top = ox + pad_l, oy + pad_t
     for fx, fy, fw, fh in np.asarray(faces, dtype=np.float64).reshape(-1, 4):
         if not (fx > 0 and fy > 0 and fw > 0 and fh > 0):
             continue
         x1, y1 = int(fx), int(fy)
         x2, y2 = x1 + int(fw) - 1, y1 + int(fh) - 1
-        x1p, x2p = int(x1 / m * image_size) + ox, int(x2 / m * image_size) + ox
-        y1p, y2p = int(y1 / m * image_size) + oy, int(y2 / m * image_size) + oy
+        x1p, x2p = int((x1 - cx0) / m * T) + left, int((x2 - cx0) / m * T) + left
+        y1p, y2p = int((y1 - cy0) / m * T) + top, int((y2 - cy0) / m * T) + top
         xc, yc = (x1p + x2p) // 2, (y1p + y2p) // 2
+        if placed:
+            if not (left <= xc < left + w_p and top <= yc < top + h_p):
+                continue
+            if flip:
+                xc = S - 1 - xc
+        yield x1, y1, x2, y2, xc, yc, m, T
+
+
+def encode_gt(faces, h, w, image_size=416, grid=13, channels=6, placement=None):
+    """Ground-truth tensor of one image (face_detection.py:150-202).
+
+    faces: array-like (n,4) of FACE_X, FACE_Y, FACE_WIDTH, FACE_HEIGHT in csv order; rows with
+    any value <= 0 are skipped; later rows overwrite earlier ones in the same cell.
+    placement: None (the reference's letterbox) or (cy0, cx0, ch, cw, T, oy, ox, flip) as draw_augment returns it
+    (_placed_centres states the arithmetic); the box sizes are then fractions of the canvas, (x2 - x1 + 1) / m * (T / S)."""
+    cell = image_size // grid
+    gt = np.zeros((grid, grid, channels), np.float64)
+    for x1, y1, x2, y2, xc, yc, m, T in _placed_centres(faces, h, w, image_size, placement):
         cx, cy = xc // cell, yc // cell
+        k = T / image_size
         gt[cy, cx, :6] = [1.0, (xc - cx * cell) / cell, (yc - cy * cell) / cell,
-                          (x2 - x1 + 1) / m, (y2 - y1 + 1) / m, 1.0]
+                          (x2 - x1 + 1) / m * k, (y2 - y1 + 1) / m * k, 1.0]
     return gt
 
 
@@ -62,7 +91,8 @@ YOLO_ANCHORS = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 1
 YOLO_ANCHORS_DECODED = ((0, 1), (1, 0), (1, 2), (2, 1))
 
 
-def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_ANCHORS, anchor_keep=YOLO_ANCHORS_DECODED):
+def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_ANCHORS, anchor_keep=YOLO_ANCHORS_DECODED,
+                          placement=None):
     """Ground truth of one image for the three-scale head: [t13, t26, t52], t_s of shape (g_s, g_s, 3*(5+nclass)) float64 with
     g_s = image_size/32 * 2^s, laid out [cell][anchor][tx, ty, tw, th, objectness, classes...] like the network output.
 
@@ -73,22 +103,13 @@ def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_AN
     `anchor_keep` order) among the anchors the reference's decode keeps, and the box is stored in the parametrisation that
     decode_netout (yolov3_detect.py:335-387) inverts: sigma(tx) = offset, anchor_w * exp(tw) = box width in network pixels.
     Offsets are clamped to [0.5/cell, 1 - 0.5/cell] (logit of 0 is -inf; half a pixel is below the decode's int() grain).
-    Objectness 1 and class 0 = 1 at the assigned slot; later rows overwrite earlier ones in the same slot."""
+    Objectness 1 and class 0 = 1 at the assigned slot; later rows overwrite earlier ones in the same slot.
+    placement: as for encode_gt; the box in network pixels is then (x2 - x1 + 1) / m * T."""
     S = int(image_size)
     C = 5 + nclass
     out = [np.zeros((S // 32 << s, S // 32 << s, 3 * C), np.float64) for s in range(3)]
-    _, _, pad_t, _, pad_l, _ = letterbox_geometry(h, w, S)
-    m = w if w >= h else h
-    ox, oy = (0, pad_t) if w >= h else (pad_l, 0)
-    for fx, fy, fw, fh in np.asarray(faces, dtype=np.float64).reshape(-1, 4):
-        if not (fx > 0 and fy > 0 and fw > 0 and fh > 0):
-            continue
-        x1, y1 = int(fx), int(fy)
-        x2, y2 = x1 + int(fw) - 1, y1 + int(fh) - 1
-        x1p, x2p = int(x1 / m * S) + ox, int(x2 / m * S) + ox
-        y1p, y2p = int(y1 / m * S) + oy, int(y2 / m * S) + oy
-        xc, yc = (x1p + x2p) // 2, (y1p + y2p) // 2
-        bw, bh = (x2 - x1 + 1) / m * S, (y2 - y1 + 1) / m * S          # the single-scale targets bw, bh times the network size
+    for x1, y1, x2, y2, xc, yc, m, T in _placed_centres(faces, h, w, S, placement):
+        bw, bh = (x2 - x1 + 1) / m * T, (y2 - y1 + 1) / m * T          # the single-scale targets bw, bh times the network size
         best, best_iou = None, -1.0
         for (s, b) in anchor_keep:
             aw, ah = anchors[s][2 * b], anchors[s][2 * b + 1]
@@ -108,6 +129,93 @@ def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_AN
         t[4] = 1.0; t[5] = 1.0
         out[s][cy, cx, b * C:(b + 1) * C] = t
     return out
+
+
+# ----------------------------------------------------------------------------- training augmentation (hps['augment'])
+AUGMENT_DEFAULTS = {'zoom': [0.75, 1.25], 'flip': 0.5, 'hue': 0.1, 'saturation': 1.5, 'exposure': 1.5, 'seed': 0}
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v)
+
+
+def augment_conf(value):
+    """fd_conf.hps['augment'] -> None (absent, None or false: the reference's fixed letterbox) or the complete parameter dict
+    (true: AUGMENT_DEFAULTS; an object: its keys over the defaults).  ValueError for an unknown key or a value outside its
+    range: zoom [lo, hi] with 0 < lo <= 1 <= hi, flip in [0, 1], hue in [0, 0.5], saturation >= 1, exposure >= 1, seed an
+    int >= 0.  Not in the reference (Darknet's detector recipe); pure host code."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError('fd_conf.hps.augment %r is not valid (false, true or an object with the keys %s)'
+                         % (value, ', '.join(sorted(AUGMENT_DEFAULTS))))
+    unknown = sorted(set(value) - set(AUGMENT_DEFAULTS))
+    if unknown:
+        raise ValueError('fd_conf.hps.augment has unknown key(s) %s (available: %s)' % (', '.join(map(repr, unknown)),
+                                                                                     ', '.join(sorted(AUGMENT_DEFAULTS))))
+    c = dict(AUGMENT_DEFAULTS)
+    c.update(value)
+    z = c['zoom']
+    if not (isinstance(z, (list, tuple)) and len(z) == 2 and all(_is_number(v) for v in z) and 0 < z[0] <= 1 <= z[1]):
+        raise ValueError('fd_conf.hps.augment.zoom %r is not valid ([lo, hi] with 0 < lo <= 1 <= hi)' % (z,))
+    if not (_is_number(c['flip']) and 0 <= c['flip'] <= 1):
+        raise ValueError('fd_conf.hps.augment.flip %r is not valid (a probability in [0, 1])' % (c['flip'],))
+    if not (_is_number(c['hue']) and 0 <= c['hue'] <= 0.5):
+        raise ValueError('fd_conf.hps.augment.hue %r is not valid (turns, in [0, 0.5])' % (c['hue'],))
+    for k in ('saturation', 'exposure'):
+        if not (_is_number(c[k]) and c[k] >= 1):
+            raise ValueError('fd_conf.hps.augment.%s %r is not valid (a number >= 1)' % (k, c[k]))
+    if not (isinstance(c['seed'], int) and not isinstance(c['seed'], bool) and c['seed'] >= 0):
+        raise ValueError('fd_conf.hps.augment.seed %r is not valid (an int >= 0)' % (c['seed'],))
+    c['zoom'] = [float(z[0]), float(z[1])]
+    for k in ('flip', 'hue', 'saturation', 'exposure'):
+        c[k] = float(c[k])
+    return c
+
+
+def draw_augment(aug_conf, epoch, file_index, h, w, S):
+    """The augmentation of image `file_index` (its index in TrainingSequence.file_names; h x w pixels) in epoch `epoch` at network
+    size S -> (placement, colour) = ((cy0, cx0, ch, cw, T, oy, ox, flip), (dh, sat, exp)): what fv_letterbox_augment_batch and
+    encode_gt(..., placement=) take.  aug_conf: augment_conf()'s dict.  A pure function of its arguments -- the batch size, the
+    position in the batch, the rank and the world size do not enter, so every rank and every rerun sees the same augmented
+    dataset.  Draws from rng = np.random.default_rng([seed, epoch, file_index]) in this fixed order (round = Python's round):
+      1. z = rng.uniform(lo, hi)
+      2. z >= 1 (zoom in): cw = max(1, round(w / z)), ch = max(1, round(h / z)); cx0 = rng.integers(0, w - cw + 1), then
+         cy0 = rng.integers(0, h - ch + 1); T = S, ox = oy = 0
+         z < 1 (zoom out): the whole image; T = max(1, round(S * z)); ox = rng.integers(0, S - T + 1), then
+         oy = rng.integers(0, S - T + 1)
+      3. flip = rng.random() < flip probability
+      4. dh = rng.uniform(-hue, hue)
+      5. sat: s = rng.uniform(1, saturation), then 1 / s if rng.random() < 0.5 (Darknet's rand_scale)
+      6. exp: likewise from exposure
+    The crop is letterboxed by letterbox_geometry(ch, cw, T) into the T x T box at (oy, ox) of the zero S x S canvas (aspect
+    preserved), the finished canvas mirrored when flip.  Where that geometry is not feasible (w_p < 1 or h_p < 1) the placement
+    falls back to identity_placement(h, w, S); the colour draw stays."""
+    h, w, S = int(h), int(w), int(S)
+    rng = np.random.default_rng([int(aug_conf['seed']), int(epoch), int(file_index)])
+    lo, hi = aug_conf['zoom']
+    z = float(rng.uniform(lo, hi))
+    if z >= 1:
+        cw, ch = max(1, round(w / z)), max(1, round(h / z))
+        cx0 = int(rng.integers(0, w - cw + 1)); cy0 = int(rng.integers(0, h - ch + 1))
+        T, ox, oy = S, 0, 0
+    else:
+        cy0, cx0, ch, cw = 0, 0, h, w
+        T = max(1, round(S * z))
+        ox = int(rng.integers(0, S - T + 1)); oy = int(rng.integers(0, S - T + 1))
+    flip = int(rng.random() < aug_conf['flip'])
+    dh = float(rng.uniform(-aug_conf['hue'], aug_conf['hue']))
+    scale = []
+    for k in ('saturation', 'exposure'):
+        s = float(rng.uniform(1.0, aug_conf[k]))
+        scale.append(1.0 / s if rng.random() < 0.5 else s)
+    w_p, h_p = letterbox_geometry(ch, cw, T)[:2]
+    placement = (cy0, cx0, ch, cw, T, oy, ox, flip)
+    if w_p < 1 or h_p < 1:
+        placement = identity_placement(h, w, S)
+    return placement, (dh + 0.0, scale[0], scale[1])
 
 
 # ----------------------------------------------------------------------------- bicubic letterbox
@@ -169,11 +277,12 @@ class TrainingSequence(object):
         self.three_scale = nn_arch.get('head', 'single') == 'three_scale'
         self.nclass = int(nn_arch.get('num_classes', 1))
 
-    def encode(self, rows, h, w):
-        """GT of one image: (G,G,6) for the reference's single-scale head, [t13, t26, t52] for the three-scale head."""
+    def encode(self, rows, h, w, placement=None):
+        """GT of one image: (G,G,6) for the reference's single-scale head, [t13, t26, t52] for the three-scale head; placement:
+        an augmented sample's placement (draw_augment), None = the reference's letterbox."""
         if self.three_scale:
-            return encode_gt_three_scale(rows, h, w, self.image_size, self.nclass)
-        return encode_gt(rows, h, w, self.image_size, self.grid, self.nn_arch['bb_info_c_size'])
+            return encode_gt_three_scale(rows, h, w, self.image_size, self.nclass, placement=placement)
+        return encode_gt(rows, h, w, self.image_size, self.grid, self.nn_arch['bb_info_c_size'], placement=placement)
 
     def __len__(self):
         return self.hps['step']

@@ -23,6 +23,9 @@ ratios.csv, the model files).  Differences, all documented in DESIGN.md:
     graph (yolov3_detect.py:217-311) with nn_arch['num_classes'] (default 1) classes: trained with the build's
     objectness / box / class loss on targets from data.encode_gt_three_scale, detected through the reference's
     decode_netout / correct_yolo_boxes / do_nms chain (fv_yolo_decode_nms)
+  * hps['augment'] (not in the reference, off unless asked for; data.augment_conf) gives every training sample a random zoom and
+    translation, a horizontal flip and a hue / saturation / exposure distortion per epoch (Darknet's detector recipe), inside the
+    batch's one letterbox launch (fv_letterbox_augment_batch); train() only
 """
 import glob
 import json
@@ -105,6 +108,7 @@ class FaceDetector(object):
         self.nn_arch = conf['nn_arch']
         self.model_loading = conf['model_loading']
         self.image_size = int(self.nn_arch['image_size'])
+        self.augment = data.augment_conf(self.hps.get('augment'))      # ValueError before a device is touched
         if self.image_size % 32:
             raise ValueError('image_size must be a multiple of 32 (network stride)')
         if int(self.nn_arch.get('bb_info_c_size', 6)) != 6:
@@ -205,6 +209,7 @@ class FaceDetector(object):
                     lv = trainer.merged_loss(loss, item[2])          # collective: every rank calls it
                     if self.rank == 0:
                         print('%d/%d - loss: %.4f' % (k + 1, steps, lv))
+            feeder.set_epoch(epoch)          # hps['augment']: the epoch enters every sample's draw; nothing is prefetched across this line
             run_pipelined(self.model, trainer, feeder, [int(i) for i in order], self.image_size, hp, after_step)
         feeder.close()
         if self.rank == 0:
@@ -493,10 +498,17 @@ class BatchFeeder(object):
     fit_generator(workers=4|8) fd.py:621-627): for batch `index`, this rank's tower slice is JPEG-decoded
     by a thread pool (PIL releases the GIL), its GT tensors are encoded, and the decoded images are
     packed back to back into one pinned host buffer.  Resize + pad happen on the device, in one launch
-    per batch (fv_letterbox_batch).  One batch is prepared ahead while the previous step runs."""
+    per batch (fv_letterbox_batch).  One batch is prepared ahead while the previous step runs.
+
+    seq.hps['augment'] (data.augment_conf): every image's placement and colour parameters are drawn here (data.draw_augment, from
+    the seed, the epoch of set_epoch() and the image's index in seq.file_names), its GT is encoded under that placement, and the two
+    small tables travel with the packed images as ('augment', packed, (place, colour)) for the same one launch
+    (fv_letterbox_augment_batch)."""
 
     def __init__(self, seq, world, rank, threads=8):
         self.seq, self.world, self.rank = seq, world, rank
+        self.augment = data.augment_conf(seq.hps.get('augment'))
+        self.epoch = 0
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.one = ThreadPoolExecutor(max_workers=1)
         self.device_jpeg = bool(seq.hps.get('device_jpeg', True))    # hps.device_jpeg = false: decode with Pillow on the host
@@ -533,6 +545,10 @@ class BatchFeeder(object):
                 self.ring.untake()
             return None
         return ('jpeg', buf, plan), [(i.height, i.width) for i in infos], slot
+
+    def set_epoch(self, epoch):
+        """The epoch the next load() calls draw their augmentation for; call it between epochs, with nothing prefetched."""
+        self.epoch = int(epoch)
 
     def copied(self, slot):
         """Called by the consumer right after it enqueued the H2D copy of the buffer `slot` (on the stream that copies)."""
@@ -580,7 +596,13 @@ class BatchFeeder(object):
             raws = list(self.pool.map(lambda nm: seq.loader(os.path.join(seq.raw_data_path, nm)), mine))
             packed = pack_images(raws, pin=pin)
             shapes = [(r.shape[0], r.shape[1]) for r in raws]
-        enc = [seq.encode(seq.groups[nm].iloc[:, 3:7].values, h, w) for nm, (h, w) in zip(mine, shapes)]
+        if self.augment is not None:
+            first = index * seq.batch_size + lo                       # mine[i] is seq.file_names[first + i]
+            drawn = [data.draw_augment(self.augment, self.epoch, first + i, h, w, seq.image_size) for i, (h, w) in enumerate(shapes)]
+            enc = [seq.encode(seq.groups[nm].iloc[:, 3:7].values, h, w, placement=d[0]) for nm, (h, w), d in zip(mine, shapes, drawn)]
+            packed = ('augment', packed, (np.asarray([d[0] for d in drawn], np.int32), np.asarray([d[1] for d in drawn], np.float32)))
+        else:
+            enc = [seq.encode(seq.groups[nm].iloc[:, 3:7].values, h, w) for nm, (h, w) in zip(mine, shapes)]
         if getattr(seq, 'three_scale', False):      # [t13, t26, t52] per image -> three stacked tensors
             yt = tuple(torch.from_numpy(np.asarray([e[s] for e in enc], np.float32)) for s in range(3))
             yt = tuple(t.pin_memory() for t in yt) if pin else yt
@@ -599,11 +621,19 @@ class BatchFeeder(object):
         self.one.shutdown(); self.pool.shutdown()
 
 
+def split_augment(packed):
+    """BatchFeeder.load's `packed` -> (what letterbox_batch_device takes as packed, its aug tables or None)."""
+    if isinstance(packed[0], str) and packed[0] == 'augment':
+        return packed[1], packed[2]
+    return packed, None
+
+
 def train_on_item(engine, trainer, item, image_size, hp):
     """One optimisation step on what BatchFeeder.load returned, everything on the compute stream: H2D copy, device JPEG
     reconstruction / letterbox, fv_train_step (+ gradient all-reduce when world > 1), Adam.  run_pipelined() is the overlapped form."""
     packed, y, weight, (feeder, slot) = item
-    x, _ = letterbox_batch_device(engine.ctx, None, image_size, engine.dev, packed=packed)
+    packed, aug = split_augment(packed)
+    x, _ = letterbox_batch_device(engine.ctx, None, image_size, engine.dev, packed=packed, aug=aug)
     if slot is not None:
         feeder.copied(slot)
     yd = [t.to(engine.dev, non_blocking=True) for t in y] if isinstance(y, (tuple, list)) else y.to(engine.dev, non_blocking=True)
@@ -625,11 +655,12 @@ class DeviceStager(object):
         if item is None:
             return None
         packed, y, weight, (feeder, slot) = item
+        packed, aug = split_augment(packed)
         main = torch.cuda.current_stream(self.eng.dev)
         with torch.cuda.stream(self.stream):
             self.eng.ctx.set_stream(self.stream.cuda_stream)      # the library's launches of this block go to the staging stream
             try:
-                x, _ = letterbox_batch_device(self.eng.ctx, None, self.S, self.eng.dev, packed=packed)
+                x, _ = letterbox_batch_device(self.eng.ctx, None, self.S, self.eng.dev, packed=packed, aug=aug)
             finally:
                 self.eng.ctx.set_stream(main.cuda_stream)
             if slot is not None:

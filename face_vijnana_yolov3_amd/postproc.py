@@ -148,10 +148,13 @@ def pack_images(raws, pin=True, ring=None):
     return buf, offs, hw
 
 
-def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None, keep=None):
+def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None, keep=None, aug=None):
     """list of uint8 HxWx3 arrays -> ((n,S,S,3) float32 CUDA tensor, [geometry tuples]) in ONE launch
     (fv_letterbox_batch); `packed` = the result of pack_images when a loader thread prepared it.  keep: a list that receives
-    (device uint8 buffer, offsets, hw) -- the batch's decoded images on the device, for a later fv_letterbox_crops."""
+    (device uint8 buffer, offsets, hw) -- the batch's decoded images on the device, for a later fv_letterbox_crops.
+    aug: (place, colour) -- n x 8 int placements and n x 3 float colour parameters (or None) as data.draw_augment draws them: the
+    launch is then fv_letterbox_augment_batch (crop, placement, flip and colour distortion in the same single pass) and the second
+    result is None (the placements ARE the geometry)."""
     import ctypes
     import torch
     if packed is not None and isinstance(packed[0], str) and packed[0] == 'jpeg':
@@ -168,6 +171,23 @@ def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None,
     S = int(image_size)
     if out is None:
         out = torch.empty((n, S, S, 3), dtype=torch.float32, device=device)
+    if aug is not None:
+        place, colour = aug
+        place = np.ascontiguousarray(np.asarray(place, np.int32).reshape(-1))
+        if place.size != 8 * n:
+            raise ValueError('letterbox_batch_device: %d placement values for %d images (8 each)' % (place.size, n))
+        cp = None
+        if colour is not None:
+            colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(-1))
+            if colour.size != 3 * n:
+                raise ValueError('letterbox_batch_device: %d colour values for %d images (3 each)' % (colour.size, n))
+            cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        rc = lib().fv_letterbox_augment_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S,
+                                              place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, ptr(out))
+        ctx.check(rc, 'fv_letterbox_augment_batch')
+        if keep is not None:
+            keep.append((dbuf, list(offs), list(hw)))
+        return out, None
     geom = (ctypes.c_int32 * (6 * n))()
     rc = lib().fv_letterbox_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, ptr(out), geom)
     ctx.check(rc, 'fv_letterbox_batch')

@@ -362,6 +362,20 @@ int fv_letterbox_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offset
  * nothing is enqueued. */
 int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
                        const int32_t* crops, int n, int image_size, float* dst);
+/* fv_letterbox_batch with a per-image placement and colour distortion, for FaceDetector.train with hps['augment'] (not in the
+ * reference; data.draw_augment draws the parameters).  packed / offsets / hw: the n images as for fv_letterbox_batch.  place: HOST
+ * int32 [n][8] records (cy0, cx0, ch, cw, T, oy, ox, flip): the ch x cw crop at (cy0, cx0) of image i is letterboxed as
+ * fv_letterbox_crops letterboxes it at image_size T -- bit-identical to that call -- into the T x T box at row oy, column ox of
+ * the otherwise zero S x S canvas; flip = 1 then mirrors the finished canvas, padding included (x -> S - 1 - x).  colour: HOST float
+ * [n][3] records (dh, sat, exp), or NULL for none; a record that is exactly (0, 1, 1) leaves its image's pixels as resampled.
+ * Otherwise each content pixel is clamped to [0, 1], converted to HSV (v = max, s = (max - min) / max or 0 for black; h in turns
+ * from the usual six-sector form, 0 for grey), h = frac(h + dh), s *= sat, v *= exp, converted back and clamped to [0, 1], all in
+ * float32 (Darknet's distort_image); padding stays 0.  dst: DEVICE float32 [n][S][S][3], 16-byte aligned; image_size a multiple
+ * of 4.  One kernel, one pass, chunks of 64 images per launch, on the context's stream; no atomics: the same call gives the same
+ * bits.  Every record is checked before anything is enqueued -- crop inside its image, 1 <= T <= S, 0 <= oy, ox <= S - T, a
+ * letterboxed side of at least 1, flip 0 or 1, finite colour values -- and a bad one is FV_ERR_INVALID with dst untouched. */
+int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int image_size,
+                               const int32_t* place, const float* colour, float* dst);
 /* Crop + nearest-neighbour letterbox of many face rectangles on uint8, in one call (create_db_fi / save_extracted_face,
  * fi.py:113-161 and 233-274: the slice, cv.resize(INTER_NEAREST), cv.copyMakeBorder(value 0)).  Images and crop records as for
  * fv_letterbox_crops; dst: device uint8 [n][S][S][3], 16-byte aligned; image_size a multiple of 16, at most 4096.  Geometry as
