@@ -110,6 +110,10 @@ def _declare(L):
         'fv_conv2d_dgrad_bnred': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32]),
         'fv_bn_bwd_slots': (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp, i32, i32, vp, vp, vp]),
         'fv_conv2d_forward_slots_bn_in': (i32, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32]),
+        'fv_conv2d_forward_slots_bn_stats_in': (i32, [vp, vp, vp, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32,
+                                                      i32, i32, vp, vp, i32]),
+        'fv_train_bn_in_1x1_plan': (i32, [i32, i32, i32, ctypes.POINTER(ctypes.c_int32), i32]),
+        'fv_yolov3_train_bn_in_1x1_plan': (i32, [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), i32]),
         'fv_conv2d_wgrad_bn_in': (i32, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         'fv_conv2d_wgrad_bn_bwd': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         'fv_mse_loss_grad': (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -207,7 +211,7 @@ class Context:
 
     def set_option(self, key, value):
         """fv_set_option: a tuning switch of include/fv_hotpath.h ('overlap', 'tail_split', 'conv_waves8', 'conv1x1_persist',
-        'conv_bm64', 'conv_small', 'conv_halo', 'conv0_direct', 'wgrad_fused_taps', 'early_bn_fused')."""
+        'conv_bm64', 'conv_small', 'conv_halo', 'conv0_direct', 'wgrad_fused_taps', 'early_bn_fused', 'bn_in_1x1')."""
         self.check(lib().fv_set_option(self._h, key.encode(), int(value)), 'fv_set_option(%s)' % key)
 
     def get_option(self, key):

@@ -86,8 +86,16 @@ const FvOption* find_option(const char* key) {
 // of one part -- 2 the forward alone, 4 the weight-gradient alone, 8 dz(0) alone, and their sums
 static bool is_early_bn(const char* key) { return key && std::string(key) == "early_bn_fused"; }
 
+// "bn_in_1x1": 0 off, 1 on for the shape classes that measured faster (the default), 2 on for every launch the kernel takes
+static bool is_bn_in_1x1(const char* key) { return key && std::string(key) == "bn_in_1x1"; }
+
 int fv_set_option(fv_ctx* ctx, const char* key, long long value) {
     if (!ctx) return FV_ERR_INVALID;
+    if (is_bn_in_1x1(key)) {
+        if (value < 0 || value > 2) return fv_fail(ctx, FV_ERR_INVALID, "fv_set_option: bn_in_1x1 takes 0, 1 or 2 (got %lld)", value);
+        ctx->bn_in_1x1 = (int)value;
+        return FV_OK;
+    }
     if (is_early_bn(key)) {
         if (value < 0 || value > 2 * FV_EARLY_ALL || (value > 1 && (value & 1)))
             return fv_fail(ctx, FV_ERR_INVALID, "fv_set_option: early_bn_fused takes 0, 1 or an even mask up to %d (got %lld)", 2 * FV_EARLY_ALL, value);
@@ -103,6 +111,7 @@ int fv_set_option(fv_ctx* ctx, const char* key, long long value) {
 int fv_get_option(fv_ctx* ctx, const char* key, long long* value) {
     if (!ctx || !value) return FV_ERR_INVALID;
     if (is_early_bn(key)) { *value = ctx->early_bn == FV_EARLY_ALL ? 1 : 2 * ctx->early_bn; return FV_OK; }
+    if (is_bn_in_1x1(key)) { *value = ctx->bn_in_1x1; return FV_OK; }
     const FvOption* o = find_option(key);
     if (!o) return fv_fail(ctx, FV_ERR_INVALID, "fv_get_option: unknown option '%s'", key ? key : "(null)");
     *value = ctx->*(o->member) ? 1 : 0;
@@ -191,7 +200,7 @@ int fv_create(int device, void* stream, fv_ctx** out) {
             const size_t eq = item.find('=');
             if (eq != std::string::npos) {
                 const std::string key = item.substr(0, eq);
-                if (is_early_bn(key.c_str())) (void)fv_set_option(c, key.c_str(), atoll(item.c_str() + eq + 1));   // (a bad value is ignored)
+                if (is_early_bn(key.c_str()) || is_bn_in_1x1(key.c_str())) (void)fv_set_option(c, key.c_str(), atoll(item.c_str() + eq + 1));   // (a bad value is ignored)
                 else if (const FvOption* o = find_option(key.c_str())) c->*(o->member) = item[eq + 1] != '0';
             }
             pos = end + 1;

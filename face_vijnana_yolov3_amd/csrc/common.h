@@ -43,6 +43,9 @@ struct fv_ctx {
     // option "early_bn_fused": the first layers' BN passes folded into their halo-kernel consumers (schedule.h).  A bit mask of the
     // parts: FV_EARLY_FWD conv9_mfma.hip reads z(0) / z(2), FV_EARLY_WGRAD wgrad9_mfma.hip does, FV_EARLY_DZ0 wgrad0_mfma.hip forms dz(0)
     int early_bn = 7;
+    // option "bn_in_1x1": the normalise pass of the layer in front of a residual block's first 1x1 conv runs inside that conv
+    // (conv1x1_mfma.hip, schedule.h).  0 off, 1 the shape classes that measured faster, 2 every launch the kernel takes
+    int bn_in_1x1 = 1;
     bool conv0_direct = true;    // option "conv0_direct": vector-FMA first layer (conv0_direct.hip) instead of the gather kernel
     ~fv_ctx();
 };

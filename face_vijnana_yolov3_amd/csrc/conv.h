@@ -58,6 +58,18 @@ struct FvConvArgs {
     long long split_stride;
     int oph[4], opw[4];
     FvTaps taps[4];
+    // BN-input mode (conv1x1_mfma.hip alone; bi_slots != NULL): x is the producing layer's raw conv output z with its statistics
+    // slots [bi_nslot][2][Cin].  Every workgroup turns the slots into scale / shift as bn_act_stats_kernel does (workgroup 0
+    // publishes bi_mean .. bi_shift and updates the moving statistics), stages LeakyReLU(z * scale + shift) (+ bi_skip) as its A
+    // operand and the workgroups of N tile 0 write those values to bi_a: the producing layer's normalise pass, inside its reader.
+    const double* bi_slots;
+    int bi_nslot;
+    double bi_count;
+    const float *bi_gamma, *bi_beta;
+    float bi_eps, bi_ema_old, bi_ema_new, bi_leaky;
+    float *bi_mean, *bi_invstd, *bi_scale, *bi_shift, *bi_mmean, *bi_mvar;
+    const float* bi_skip;   // same layout as x, may be NULL
+    float* bi_a;            // same layout as x
 };
 
 // Number of M tiles (rows of psum/psq) the conv launch will use for this problem.
@@ -81,6 +93,8 @@ bool fv_dgrad9s2_ok(const FvConvArgs& a);
 int fv_dgrad9s2_launch(fv_ctx* ctx, const FvConvArgs& a);
 // conv1x1_mfma.hip: 1x1 stride-1 launches with more tiles than resident workgroup slots as a persistent GEMM (bit-identical)
 bool fv_conv1x1_persist_ok(const FvConvArgs& a);
+bool fv_conv1x1_bn_in_ok(const FvConvArgs& a);   // the BN-input mode: any number of tiles, Cin <= 512
+bool fv_conv1x1_bn_in_wins(const FvConvArgs& a, bool with_skip);   // ... and measured faster than normalise pass + plain conv
 int fv_conv1x1_persist_launch(fv_ctx* ctx, const FvConvArgs& a);
 // conv_small_mfma.hip: small-M inference launches (batch 1) with the K split inside the workgroup; plan: 0 = not taken, 1..3 = configuration
 int fv_conv_small_plan(int M, int Nout, int Cin, int ntaps);

@@ -473,6 +473,14 @@ int fv_conv_launch(fv_ctx* ctx, const FvConvArgs& a) {
                                                  !(a.epi & (FV_EPI_STATS | FV_EPI_AFFINE | FV_EPI_LEAKY))),
                "conv: fused BN-backward reduction needs its layer's tensors, 16-byte rows and a plain (+add) epilogue");
     FV_REQUIRE(ctx, a.ksplit <= 1 || (a.epi == 0 && a.nclass == 1 && a.Cin % BK == 0), "conv: split-K stores raw partials only");
+    if (a.bi_slots) {   // the BN-input mode lives in one kernel: a launch that kernel does not take is an error, never the plain conv
+        FV_REQUIRE(ctx, !a.in_scale && ctx->conv1x1_persist && fv_conv1x1_bn_in_ok(a),
+                   "conv: the BN-input mode needs the persistent 1x1 kernel (conv1x1_mfma.hip: 1x1 stride 1, statistics epilogue, "
+                   "Cin %% 32 == 0, Cin <= 512, Cout %% 4 == 0, Cout > 32, option conv1x1_persist), which does not take this launch");
+        FV_REQUIRE(ctx, a.bi_nslot >= 1 && a.bi_gamma && a.bi_beta && a.bi_mean && a.bi_invstd && a.bi_scale && a.bi_shift && a.bi_a,
+                   "conv: the BN-input mode needs the producing layer's gamma / beta, its four published vectors and its activation buffer");
+        return fv_conv1x1_persist_launch(ctx, a);
+    }
     if (ctx->conv_halo && fv_conv9_fwd_ok(a)) return fv_conv9_fwd_launch(ctx, a);
     FV_REQUIRE(ctx, !a.in_scale, "conv: BN-on-load needs the halo kernel (conv9_mfma.hip), which does not take this launch");
     if (ctx->conv_halo && fv_dgrad9s2_ok(a)) return fv_dgrad9s2_launch(ctx, a);

@@ -33,19 +33,66 @@ __device__ __forceinline__ float4 fv_bn_bwd_dz4(const float4& g, const float4& z
     return o;
 }
 
-// Totals of the [nslot][2][C] fp64 accumulator slots by a 256-thread workgroup for C < 256 dividing 256: the 256 / C thread
-// groups take every (256 / C)-th slot of a channel, thread c < C then adds the groups' partials in ascending order -- one fixed
-// order wherever the slots are summed.  Valid in threads tid < C on return; contains one barrier, s_part is [2][256].
+// Totals of the [nslot][2][C] fp64 accumulator slots by the first 256 threads of a workgroup of NTH for C < 256: the 256 / C
+// thread groups take every (256 / C)-th slot of a channel, thread c < C then adds the groups' partials in ascending order -- one
+// fixed order wherever the slots are summed.  (C not dividing 256: the threads behind the last whole group idle.)  Valid in
+// threads tid < C on return; contains one barrier, which every thread of the workgroup reaches; s_part is [2][256].
+template <int NTH = 256>
 __device__ __forceinline__ void fv_bn_slot_totals(const double* __restrict__ slots, int nslot, int C, int tid, double (*s_part)[256],
                                                   double& a, double& b) {
     const int G = 256 / C, g = tid / C, c = tid % C;
     a = 0.0; b = 0.0;
-    for (int k = g; k < nslot; k += G) { a += slots[(size_t)(2 * k) * C + c]; b += slots[(size_t)(2 * k + 1) * C + c]; }
-    s_part[0][tid] = a; s_part[1][tid] = b;
+    if (g < G)
+        for (int k = g; k < nslot; k += G) { a += slots[(size_t)(2 * k) * C + c]; b += slots[(size_t)(2 * k + 1) * C + c]; }
+    if (NTH == 256 || tid < 256) { s_part[0][tid] = a; s_part[1][tid] = b; }
     __syncthreads();
     if (tid < C) {
         a = 0.0; b = 0.0;
         for (int j = 0; j < G; ++j) { a += s_part[0][j * C + tid]; b += s_part[1][j * C + tid]; }
+    }
+}
+
+// Accumulator slots of the conv epilogue (conv.h stat_slots) -> scale/shift of all C channels in LDS: fixed summation order
+// over the slots, fp64, 16 loads per thread.  `publish` (one workgroup per launch): also mean / invstd / scale / shift for the
+// backward pass and the update of the moving statistics.  The caller's barrier makes s_sc / s_sh visible.  The first 256 threads
+// of a workgroup of NTH do the work (bn_act_stats_kernel, bn_stats_publish_kernel and the BN-input mode of conv1x1_mfma.hip
+// share this code, so scale / shift are the same bits wherever they are formed).
+template <int NTH = 256>
+__device__ __forceinline__ void fv_bn_slots_to_affine(const double* __restrict__ slots, int nslot, double count,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                      float ema_old, float ema_new, float* __restrict__ mean_out,
+                                                      float* __restrict__ invstd_out, float* __restrict__ scale_out,
+                                                      float* __restrict__ shift_out, float* __restrict__ moving_mean,
+                                                      float* __restrict__ moving_var, int C, bool publish, float* s_sc, float* s_sh,
+                                                      double (*s_part)[256]) {
+    const int tid = threadIdx.x;
+    auto finish = [&](int c, double s, double q) {
+        const double mean = s / count;
+        double var = q / count - mean * mean;
+        if (var < 0.0) var = 0.0;
+        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float sc = gamma[c] * invstd, sh = beta[c] - (float)mean * sc;
+        s_sc[c] = sc; s_sh[c] = sh;
+        if (publish) {
+            mean_out[c] = (float)mean; invstd_out[c] = invstd; scale_out[c] = sc; shift_out[c] = sh;
+            if (moving_mean) {   // Keras 2.2.4 BatchNormalization: EMA of batch mean and of var * n/(n-(1+eps))
+                const double corr = count / (count - (1.0 + (double)eps));
+                moving_mean[c] = ema_old * moving_mean[c] + ema_new * (float)mean;
+                moving_var[c] = ema_old * moving_var[c] + ema_new * (float)(var * corr);
+            }
+        }
+    };
+    if (C >= 256) {
+        for (int c = tid; c < C && (NTH == 256 || tid < 256); c += 256) {
+            double s = 0.0, q = 0.0;
+            for (int k = 0; k < nslot; ++k) { s += slots[(size_t)(2 * k) * C + c]; q += slots[(size_t)(2 * k + 1) * C + c]; }
+            finish(c, s, q);
+        }
+    } else {
+        // C < 256 (a power of two >= 32 here): 256 / C thread groups share the slots of a channel
+        double s, q;
+        fv_bn_slot_totals<NTH>(slots, nslot, C, tid, s_part, s, q);
+        if (tid < C) finish(tid, s, q);
     }
 }
 
@@ -72,6 +119,8 @@ int fv_ew_adam(fv_ctx* ctx, float* p, const float* g, float* m, float* v, long l
 // [nslot][2][C] fp64 accumulator slots (zeroed by the caller); this pass sums them, normalises, and
 // publishes mean/invstd/scale/shift (+ moving statistics) for the backward pass
 int fv_ew_bn_stat_slots(int C);
+// the coefficients of the moving-statistics update under the context's zero-debias step (fv_set_bn_zero_debias_step)
+void fv_ew_bn_ema_coeff(const fv_ctx* ctx, float momentum, float* c_old, float* c_new);
 int fv_ew_bn_act_stats(fv_ctx* ctx, const float* z, const double* slots, int nslot, double count, const float* gamma,
                        const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                        float* moving_mean, float* moving_var, const float* skip, float* out, long long rows, int C, float leaky);

@@ -96,47 +96,6 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float4* __restrict__ 
     }
 }
 
-// Accumulator slots of the conv epilogue (conv.h stat_slots) -> scale/shift of all C channels in LDS: fixed summation order
-// over the slots, fp64, 16 loads per thread.  `publish` (one workgroup per launch): also mean / invstd / scale / shift for the
-// backward pass and the update of the moving statistics.  The caller's barrier makes s_sc / s_sh visible.
-__device__ __forceinline__ void bn_slots_to_affine(const double* __restrict__ slots, int nslot, double count,
-                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                   float ema_old, float ema_new, float* __restrict__ mean_out,
-                                                   float* __restrict__ invstd_out, float* __restrict__ scale_out,
-                                                   float* __restrict__ shift_out, float* __restrict__ moving_mean,
-                                                   float* __restrict__ moving_var, int C, bool publish, float* s_sc, float* s_sh,
-                                                   double (*s_part)[256]) {
-    const int tid = threadIdx.x;
-    auto finish = [&](int c, double s, double q) {
-        const double mean = s / count;
-        double var = q / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = gamma[c] * invstd, sh = beta[c] - (float)mean * sc;
-        s_sc[c] = sc; s_sh[c] = sh;
-        if (publish) {
-            mean_out[c] = (float)mean; invstd_out[c] = invstd; scale_out[c] = sc; shift_out[c] = sh;
-            if (moving_mean) {   // Keras 2.2.4 BatchNormalization: EMA of batch mean and of var * n/(n-(1+eps))
-                const double corr = count / (count - (1.0 + (double)eps));
-                moving_mean[c] = ema_old * moving_mean[c] + ema_new * (float)mean;
-                moving_var[c] = ema_old * moving_var[c] + ema_new * (float)(var * corr);
-            }
-        }
-    };
-    if (C >= 256) {
-        for (int c = tid; c < C; c += 256) {
-            double s = 0.0, q = 0.0;
-            for (int k = 0; k < nslot; ++k) { s += slots[(size_t)(2 * k) * C + c]; q += slots[(size_t)(2 * k + 1) * C + c]; }
-            finish(c, s, q);
-        }
-    } else {
-        // C < 256 (a power of two >= 32 here): 256 / C thread groups share the slots of a channel
-        double s, q;
-        fv_bn_slot_totals(slots, nslot, C, tid, s_part, s, q);
-        if (tid < C) finish(tid, s, q);
-    }
-}
-
 // The normalise pass fed by the slots: every workgroup first turns them into scale/shift and keeps those in LDS; workgroup 0
 // also publishes -- no finalize launch in between.
 __global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restrict__ z, const double* __restrict__ slots, int nslot,
@@ -149,7 +108,7 @@ __global__ __launch_bounds__(256) void bn_act_stats_kernel(const float4* __restr
     __shared__ __attribute__((aligned(16))) float s_sc[1024], s_sh[1024];
     __shared__ double s_part[2][256];
     const int tid = threadIdx.x;
-    bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
+    fv_bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
                        moving_var, C, blockIdx.x == 0, s_sc, s_sh, s_part);
     __syncthreads();
     const int c4n = C >> 2;
@@ -176,7 +135,7 @@ __global__ __launch_bounds__(256) void bn_stats_publish_kernel(const double* __r
                                                                float* __restrict__ moving_var, int C) {
     __shared__ __attribute__((aligned(16))) float s_sc[1024], s_sh[1024];
     __shared__ double s_part[2][256];
-    bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
+    fv_bn_slots_to_affine(slots, nslot, count, gamma, beta, eps, ema_old, ema_new, mean_out, invstd_out, scale_out, shift_out, moving_mean,
                        moving_var, C, true, s_sc, s_sh, s_part);
 }
 
@@ -611,6 +570,8 @@ static inline void bn_ema_coeff(const fv_ctx* ctx, float momentum, float* c_old,
     *c_new = (float)((1.0 - m) / den);
 }
 
+void fv_ew_bn_ema_coeff(const fv_ctx* ctx, float momentum, float* c_old, float* c_new) { bn_ema_coeff(ctx, momentum, c_old, c_new); }
+
 int fv_ew_bn_finalize(fv_ctx* ctx, const float* psum, const float* psq, int mtiles, int C, double count, const float* gamma,
                       const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                       float* moving_mean, float* moving_var) {
@@ -650,10 +611,11 @@ int fv_ew_bn_stat_slots(int C) {
 int fv_ew_bn_act_stats(fv_ctx* ctx, const float* z, const double* slots, int nslot, double count, const float* gamma,
                        const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                        float* moving_mean, float* moving_var, const float* skip, float* out, long long rows, int C, float leaky) {
-    FV_REQUIRE(ctx, C % 4 == 0 && C <= 1024 && (C >= 256 || 256 % C == 0), "bn_act_stats: C must be a multiple of 4, <= 1024, and divide 256 when below it");
+    FV_REQUIRE(ctx, C % 4 == 0 && C >= 4 && C <= 1024, "bn_act_stats: C must be a multiple of 4, <= 1024");
     FV_REQUIRE(ctx, nslot >= 1 && slots, "bn_act_stats: no accumulator slots");
     long long n4 = rows * C / 4;
-    FvProfScope ps(ctx, "bn_act_stats_kernel", 0.0, 4.0 * rows * C * (skip ? 3 : 2));
+    FvProfScope ps(ctx, "bn_act_stats_kernel", "M" + std::to_string(rows) + " C" + std::to_string(C) + (skip ? " +skip" : ""), 0.0,
+                   4.0 * rows * C * (skip ? 3 : 2));
     // 4 workgroups per CU: the slot reduction in front of the stream is paid once per workgroup (measured:
     // 4096 / 2048 / 1024 / 512 workgroups -> 2.78 / 2.57 / 2.47 / 3.03 ms per step over the 52 layers)
     float ema_old, ema_new;

@@ -30,6 +30,13 @@ int fv_train_workspace_tensor(int batch, int image_size, int layer, int which, s
     return kept_tensor(p.k, base, N.L[layer], layer, which, batch, image_size, offset_bytes, count);
 }
 
+int fv_train_bn_in_1x1_plan(int option, int batch, int image_size, int32_t* folded, int n) {
+    const Net& N = net();
+    if (!folded || n != (int)N.L.size() || batch < 1 || image_size < 32 || image_size % 32) return FV_ERR_INVALID;
+    bn_in_plan(N.L, option, batch, image_size, folded);
+    return FV_OK;
+}
+
 // inference forward: the 52 base layers (the last one into `feat` when given), then the head into `y` when given
 static int forward_impl(fv_ctx* ctx, const char* who, const float* params, const float* bn_state, const float* x, int batch,
                         int image_size, void* workspace, size_t workspace_bytes, float* feat, float* y) {
@@ -93,6 +100,7 @@ int fv_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float
         if (int rc = train_bn_forward(t, l, cur, l == 0 ? p.w0p : params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
         cur = p.k.a[l];
     }
+    if (int rc = train_bn_forward_end(t)) return rc;
     // the head conv has 6 output channels: K-split like the batch-1 inference path (conv_small and conv_bm64 never take it)
     const auto& h = N.L[nb];
     if (int rc = infer_conv(Infer{ctx, params, batch, image_size, nullptr, nullptr, nullptr, p.head_slab}, h, cur, nullptr, p.yhat)) return rc;

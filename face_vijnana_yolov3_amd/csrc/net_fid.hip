@@ -158,6 +158,7 @@ int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, cons
             if (int rc = train_bn_forward(t, l, cur, l == 0 ? pa.w0p : params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
             cur = w.t[i].k.a[l];
         }
+        if (int rc = train_bn_forward_end(t)) return rc;
     }
     // ---------------- dense + l2_normalize over the 3B rows (read in place from the towers' top activations), loss, dense gradients
     const FidRows X{{w.t[0].k.a[NB - 1], w.t[1].k.a[NB - 1], w.t[2].k.a[NB - 1]}, batch};
@@ -227,6 +228,7 @@ int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, c
         if (int rc = train_bn_forward(t, l, cur, l == 0 ? p.w0p : params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
         cur = p.k.a[l];
     }
+    if (int rc = train_bn_forward_end(t)) return rc;
     const FidRows X{{p.k.a[NB - 1], nullptr, nullptr}, M};
     if (int rc = fv_fid_dense_fwd(ctx, X, M, F, params + dense_off, w.part)) return rc;
     if (int rc = fv_fid_dense_finish(ctx, w.part, fv_fid_chunks(F), M, params + dense_off + F * FID_DIM, w.pre, w.u)) return rc;

@@ -216,6 +216,14 @@ size_t fv_yolov3_train_workspace_bytes(int batch, int image_size, int out_channe
     return ytrain_plan(nullptr, ynet(out_channels), batch, image_size, out_channels).bytes;
 }
 
+int fv_yolov3_train_bn_in_1x1_plan(int option, int batch, int image_size, int out_channels, int32_t* folded, int n) {
+    if (!folded || batch < 1 || image_size < 32 || image_size % 32 || out_channels < 18 || out_channels % 3) return FV_ERR_INVALID;
+    const YNet& N = ynet(out_channels);
+    if (n != (int)N.L.size()) return FV_ERR_INVALID;
+    bn_in_plan(N.L, option, batch, image_size, folded);
+    return FV_OK;
+}
+
 int fv_yolov3_train_workspace_tensor(int batch, int image_size, int out_channels, int layer, int which, size_t* offset_bytes,
                                      int64_t* count) {
     if (!offset_bytes || !count || batch < 1 || image_size < 32 || image_size % 32 || out_channels < 18 || out_channels % 3) return FV_ERR_INVALID;
@@ -283,6 +291,7 @@ int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, cons
                                             0.f, nullptr, p.y[sidx], nullptr, nullptr)) return rc;
         }
     }
+    if (int rc = train_bn_forward_end(t)) return rc;
     // ------------------------------------------------------------------ loss of the three scales, its gradient, bias gradients
     const float* yt[3] = {yt13, yt26, yt52};
     const int det[3] = {D13, D26, D52};

@@ -41,9 +41,22 @@ bool fv_op_conv_forward_takes_bn_in(fv_ctx* ctx, int B, int H, int W, int cin, i
     return (long long)B * H * W * cin < (1ll << 29) && ctx->conv_halo && fv_conv9_fwd_ok(a);
 }
 
+bool fv_op_conv_forward_takes_bn_stats_in(int option, bool persist_on, int B, int H, int W, int cin, int cout, int ksize, int stride,
+                                          bool with_skip) {
+    if (option <= 0 || !persist_on || ksize != 1 || stride != 1 || B < 1 || H < 1 || W < 1 || cin < 1 || cout < 1) return false;
+    if ((long long)B * H * W * cin >= (1ll << 29)) return false;
+    static double any_slot;
+    FvConvArgs a{};
+    fwd_args(a, B, H, W, cin, cout, ksize, stride, FV_EPI_STATS, 1, &any_slot, 1);
+    if (!fv_conv1x1_bn_in_ok(a)) return false;
+    if (option >= 2) return true;
+    return fv_conv1x1_bn_in_wins(a, with_skip);
+}
+
 int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H, int W, int cin, int cout, int ksize,
                        int stride, int epi, const float* scale, const float* shift, float leaky, const float* addend,
-                       float* out, float* psum, float* psq, int ksplit, double* stat_slots, int stat_nslot, const FvBnIn* bn_in) {
+                       float* out, float* psum, float* psq, int ksplit, double* stat_slots, int stat_nslot, const FvBnIn* bn_in,
+                       const FvBnStatsIn* bn_stats_in) {
     FV_REQUIRE(ctx, (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)), "conv: unsupported k=%d s=%d", ksize, stride);
     FV_REQUIRE(ctx, H % stride == 0 && W % stride == 0, "conv: H,W must be divisible by the stride");
     FvConvArgs a{};
@@ -52,6 +65,15 @@ int fv_op_conv_forward(fv_ctx* ctx, const float* x, const float* w, int B, int H
     if (bn_in) {
         FV_REQUIRE(ctx, bn_in->scale && bn_in->shift, "conv: BN-on-load needs scale and shift");
         a.in_scale = bn_in->scale; a.in_shift = bn_in->shift; a.in_leaky = bn_in->leaky;
+    }
+    if (const FvBnStatsIn* bi = bn_stats_in) {
+        FV_REQUIRE(ctx, !bn_in, "conv: one BN-on-load form per launch");
+        a.bi_slots = bi->slots; a.bi_nslot = bi->nslot; a.bi_count = bi->count; a.bi_gamma = bi->gamma; a.bi_beta = bi->beta;
+        a.bi_eps = bi->eps; a.bi_leaky = bi->leaky;
+        fv_ew_bn_ema_coeff(ctx, bi->momentum, &a.bi_ema_old, &a.bi_ema_new);
+        a.bi_mean = bi->mean; a.bi_invstd = bi->invstd; a.bi_scale = bi->scale; a.bi_shift = bi->shift;
+        a.bi_mmean = bi->moving_mean; a.bi_mvar = bi->moving_var; a.bi_skip = bi->skip; a.bi_a = bi->a_out;
+        FV_REQUIRE(ctx, a.bi_slots, "conv: the BN-input mode needs the producing layer's statistics slots");
     }
     fwd_args(a, B, H, W, cin, cout, ksize, stride, epi, ksplit, stat_slots, stat_nslot);
     // inference epilogues only: the training forward keeps one tiling whatever the batch (its statistics are per-tile sums)
@@ -254,7 +276,7 @@ int fv_bn_act_slots(fv_ctx* ctx, const float* z, const double* slots, int nslot,
                     const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale, float* shift,
                     float* moving_mean, float* moving_var, const float* skip, float* out, float leaky) {
     if (!ctx) return FV_ERR_INVALID;
-    if (int rc = slots_ok(ctx, slots, nslot, C, "bn_act_slots")) return rc;
+    FV_REQUIRE(ctx, slots && nslot >= 1 && C % 4 == 0 && C >= 4 && C <= 1024, "bn_act_slots: needs accumulator slots, C %% 4 == 0 and C <= 1024 (C=%d)", C);
     FV_REQUIRE(ctx, z && gamma && beta && mean && invstd && scale && shift && out && rows > 0, "bn_act_slots: NULL buffer");
     return fv_ew_bn_act_stats(ctx, z, slots, nslot, (double)rows, gamma, beta, eps, momentum, mean, invstd, scale, shift,
                               moving_mean, moving_var, skip, out, rows, C, leaky);
@@ -291,6 +313,24 @@ int fv_conv2d_forward_slots_bn_in(fv_ctx* ctx, const float* z_in, const float* i
     const FvBnIn bi{in_scale, in_shift, leaky};
     return fv_op_conv_forward(ctx, z_in, w, B, H, W, cin, cout, ksize, stride, FV_EPI_STATS, nullptr, nullptr, 0.f, nullptr, z, nullptr,
                               nullptr, 1, slots, nslot, &bi);
+}
+
+int fv_conv2d_forward_slots_bn_stats_in(fv_ctx* ctx, const float* z_in, const double* in_slots, int in_nslot, const float* gamma,
+                                        const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale,
+                                        float* shift, float* moving_mean, float* moving_var, const float* skip, float* a_out,
+                                        float leaky, const float* w, int B, int H, int W, int cin, int cout, float* z,
+                                        double* slots, int nslot) {
+    if (!ctx) return FV_ERR_INVALID;
+    if (int rc = slots_ok(ctx, slots, nslot, cout, "conv2d_forward_slots_bn_stats_in")) return rc;
+    FV_REQUIRE(ctx, z_in && in_slots && in_nslot >= 1 && gamma && beta && mean && invstd && scale && shift && a_out && w && z,
+               "conv2d_forward_slots_bn_stats_in: NULL buffer");
+    FV_REQUIRE(ctx, fv_op_conv_forward_takes_bn_stats_in(2, ctx->conv1x1_persist, B, H, W, cin, cout, 1, 1, skip != nullptr),
+               "conv2d_forward_slots_bn_stats_in: only the persistent 1x1 kernel has the BN-input mode (cin %% 32 == 0, cin <= 512, "
+               "cout %% 4 == 0, cout > 32, option conv1x1_persist); it does not take B=%d H=%d W=%d cin=%d cout=%d", B, H, W, cin, cout);
+    const FvBnStatsIn bi{in_slots, in_nslot, (double)B * H * W, gamma, beta, eps, momentum, mean, invstd, scale, shift, moving_mean,
+                         moving_var, skip, a_out, leaky};
+    return fv_op_conv_forward(ctx, z_in, w, B, H, W, cin, cout, 1, 1, FV_EPI_STATS, nullptr, nullptr, 0.f, nullptr, z, nullptr,
+                              nullptr, 1, slots, nslot, nullptr, &bi);
 }
 
 int fv_conv2d_wgrad_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky, const float* dy,

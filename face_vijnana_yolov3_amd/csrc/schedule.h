@@ -214,6 +214,9 @@ struct Train {
     fv_ctx* ctx; const Layers& L; const Kept& k; int B, S;
     const float* params; float* bn_state; float* grads;
     bool accumulate_bn = false;   // d-beta / d-gamma are added to `grads` (towers sharing one BN layer), not stored
+    // forward pass: the layer whose normalise pass waits for the next layer's forward (bn_in_next), and that pass's skip
+    mutable int deferred = -1;
+    mutable const float* deferred_skip = nullptr;
 };
 
 // Option "early_bn_fused" (DESIGN.md 4.3): where the readers of a(l - 1) are halo kernels, which stage every input element once,
@@ -237,25 +240,74 @@ EarlyIn early_in(const Train& t, int l, const float* in) {
     return e;
 }
 
+// Option "bn_in_1x1" (DESIGN.md 4.3): the first 1x1 conv of a residual block (role 1, C -> C/2, stride 1) reads every element of
+// its input once, and that input a(l) is what layer l's normalise pass has just written.  Where the persistent 1x1 kernel takes
+// the launch (and its shape class measured faster) the pass of layer l runs inside the forward of layer l + 1: the kernel sums
+// layer l's slots, publishes its vectors, forms a(l) while staging z(l) and writes it once (a(l) is the block's skip and the input of
+// the weight-gradient; nothing in the backward pass changes).  Decided from the layer table and the launcher's predicate alone:
+// a consumer that is 3x3, strided, fed by a route / concatenation or a head (none of them has role 1) keeps the pass in front.
+bool bn_in_next(const Layers& L, int l, int option, bool persist_on, int B, int S, bool with_skip) {
+    if (option <= 0 || l < 0 || l + 1 >= (int)L.size()) return false;
+    const auto &d = L[l], &dn = L[l + 1];
+    if (!d.has_bn || !dn.has_bn || dn.role != 1 || dn.cin != d.cout || dn.in_div != d.out_div) return false;
+    const int H = S / dn.in_div;
+    return fv_op_conv_forward_takes_bn_stats_in(option, persist_on, B, H, H, dn.cin, dn.cout, dn.ksize, dn.stride, with_skip);
+}
+// the listing behind fv_train_bn_in_1x1_plan / fv_yolov3_train_bn_in_1x1_plan
+void bn_in_plan(const Layers& L, int option, int B, int S, int32_t* folded) {
+    for (int l = 0; l < (int)L.size(); ++l) folded[l] = bn_in_next(L, l, option, true, B, S, L[l].role == 2) ? 1 : 0;
+}
+
 // Training forward of BN layer l: the conv adds its column sums to the fp64 accumulator slots and the normalise pass reduces
 // them itself -- two launches per layer (the per-operator API keeps the partial-row form + fv_bn_finalize).  `in` is a(l - 1) as
 // the caller's graph names it; a(l) stays unwritten when layer l + 1 reads z(l) in both passes (the caller hands a(l) on as ever).
+// (The pass of layer l: train_bn_pass; where bn_in_next says so it waits and runs inside the forward of layer l + 1.)
+int train_bn_pass(const Train& t, int l, const float* skip) {
+    const auto& d = t.L[l];
+    const int Ho = t.S / d.out_div;
+    const long long rows = (long long)t.B * Ho * Ho;
+    return fv_ew_bn_act_stats(t.ctx, t.k.z[l], t.k.slots[l], fv_ew_bn_stat_slots(d.cout), (double)rows, t.params + d.gamma_off,
+                              t.params + d.beta_off, BN_EPS, BN_MOMENTUM, t.k.mean[l], t.k.invstd[l], t.k.scale[l], t.k.shift[l],
+                              t.bn_state + d.mean_off, t.bn_state + d.var_off, skip, t.k.a[l], rows, d.cout, LEAKY);
+}
 int train_bn_forward(const Train& t, int l, const float* in, const float* w, const float* skip) {
     const auto& d = t.L[l];
     const int H = t.S / d.in_div, Ho = t.S / d.out_div;
     const long long rows = (long long)t.B * Ho * Ho;
     const int ns = fv_ew_bn_stat_slots(d.cout);
-    const bool from_z = early_in(t, l, in).fwd;
-    const FvBnIn bi{from_z ? t.k.scale[l - 1] : nullptr, from_z ? t.k.shift[l - 1] : nullptr, LEAKY};
-    if (int rc = fv_op_conv_forward(t.ctx, from_z ? t.k.z[l - 1] : in, w, t.B, H, H, d.cin, d.cout, d.ksize, d.stride, FV_EPI_STATS, nullptr,
-                                    nullptr, 0.f, nullptr, t.k.z[l], nullptr, nullptr, 1, t.k.slots[l], ns, from_z ? &bi : nullptr)) return rc;
+    if (t.deferred >= 0) {   // the pass of layer l - 1 runs inside this conv: x is z(l - 1), and the kernel writes a(l - 1)
+        const int lp = t.deferred;
+        const auto& dp = t.L[lp];
+        FV_REQUIRE(t.ctx, lp == l - 1 && in == t.k.a[lp], "train_bn_forward: layer %d does not read the layer whose normalise pass waits for it", l);
+        const FvBnStatsIn bi{t.k.slots[lp], fv_ew_bn_stat_slots(dp.cout), (double)t.B * H * H, t.params + dp.gamma_off, t.params + dp.beta_off,
+                             BN_EPS, BN_MOMENTUM, t.k.mean[lp], t.k.invstd[lp], t.k.scale[lp], t.k.shift[lp], t.bn_state + dp.mean_off,
+                             t.bn_state + dp.var_off, t.deferred_skip, t.k.a[lp], LEAKY};
+        t.deferred = -1; t.deferred_skip = nullptr;
+        if (int rc = fv_op_conv_forward(t.ctx, t.k.z[lp], w, t.B, H, H, d.cin, d.cout, d.ksize, d.stride, FV_EPI_STATS, nullptr, nullptr, 0.f,
+                                        nullptr, t.k.z[l], nullptr, nullptr, 1, t.k.slots[l], ns, nullptr, &bi)) return rc;
+    } else {
+        const bool from_z = early_in(t, l, in).fwd;
+        const FvBnIn bi{from_z ? t.k.scale[l - 1] : nullptr, from_z ? t.k.shift[l - 1] : nullptr, LEAKY};
+        if (int rc = fv_op_conv_forward(t.ctx, from_z ? t.k.z[l - 1] : in, w, t.B, H, H, d.cin, d.cout, d.ksize, d.stride, FV_EPI_STATS, nullptr,
+                                        nullptr, 0.f, nullptr, t.k.z[l], nullptr, nullptr, 1, t.k.slots[l], ns, from_z ? &bi : nullptr)) return rc;
+    }
     if (!skip && early_in(t, l + 1, t.k.a[l]).virt())
         return fv_ew_bn_stats_publish(t.ctx, t.k.slots[l], ns, (double)rows, t.params + d.gamma_off, t.params + d.beta_off, BN_EPS,
                                       BN_MOMENTUM, t.k.mean[l], t.k.invstd[l], t.k.scale[l], t.k.shift[l], t.bn_state + d.mean_off,
                                       t.bn_state + d.var_off, d.cout);
-    return fv_ew_bn_act_stats(t.ctx, t.k.z[l], t.k.slots[l], ns, (double)rows, t.params + d.gamma_off, t.params + d.beta_off, BN_EPS,
-                              BN_MOMENTUM, t.k.mean[l], t.k.invstd[l], t.k.scale[l], t.k.shift[l], t.bn_state + d.mean_off,
-                              t.bn_state + d.var_off, skip, t.k.a[l], rows, d.cout, LEAKY);
+    if (bn_in_next(t.L, l, t.ctx->bn_in_1x1, t.ctx->conv1x1_persist, t.B, t.S, skip != nullptr)) {
+        t.deferred = l; t.deferred_skip = skip;
+        return FV_OK;
+    }
+    return train_bn_pass(t, l, skip);
+}
+// After the last train_bn_forward of a pass: a pass still waiting (the caller stopped in front of its reader) runs on its own.
+int train_bn_forward_end(const Train& t) {
+    if (t.deferred < 0) return FV_OK;
+    const int l = t.deferred;
+    const float* skip = t.deferred_skip;
+    t.deferred = -1; t.deferred_skip = nullptr;
+    return train_bn_pass(t, l, skip);
 }
 
 // Every data-gradient also reduces d-beta / d-gamma of the BN layer whose output gradient it produces (conv.h FV_EPI_BNRED):

@@ -164,6 +164,23 @@ def conv2d_forward_slots_bn_in(ctx, z_in, in_scale, in_shift, w, stride, slots, 
     return z
 
 
+def conv2d_forward_slots_bn_stats_in(ctx, z_in, in_slots, gamma, beta, w, slots, eps=1e-3, momentum=0.99, moving_mean=None, moving_var=None,
+                                     skip=None, leaky=0.1, a_out=None):
+    """bn_act_slots of the producing layer + conv2d_forward_slots of a 1x1 conv in one kernel (option bn_in_1x1).
+    Returns z, a, mean, invstd, scale, shift; a_out: the buffer the activation is written to (default: a new one)."""
+    B, H, W, cin = z_in.shape
+    cout = w.shape[0]
+    mk = lambda: torch.empty(cin, dtype=torch.float32, device=z_in.device)
+    mean, invstd, scale, shift = mk(), mk(), mk(), mk()
+    a = torch.empty_like(z_in) if a_out is None else a_out
+    z = torch.empty((B, H, W, cout), dtype=torch.float32, device=z_in.device)
+    rc = lib().fv_conv2d_forward_slots_bn_stats_in(ctx.handle, ptr(z_in), ptr(in_slots), in_slots.shape[0], ptr(gamma), ptr(beta), eps, momentum,
+                                                   ptr(mean), ptr(invstd), ptr(scale), ptr(shift), _p(moving_mean), _p(moving_var), _p(skip),
+                                                   ptr(a), leaky, ptr(w.contiguous()), B, H, W, cin, cout, ptr(z), ptr(slots), slots.shape[0])
+    ctx.check(rc, 'fv_conv2d_forward_slots_bn_stats_in')
+    return z, a, mean, invstd, scale, shift
+
+
 def conv2d_wgrad_bn_in(ctx, z_in, in_scale, in_shift, dy, cout, ksize, stride=1, leaky=0.1):
     """conv2d_wgrad with x = leaky(z_in*in_scale+in_shift) formed on load (3x3, 32 -> 64 channels)."""
     B, H, W, cin = z_in.shape

@@ -98,6 +98,11 @@ int fv_set_bn_zero_debias_step(fv_ctx* ctx, long long step);
  *                       written either.  Needs "conv_halo" / "wgrad_fused_taps" (otherwise the passes run as before).  Same bits
  *                       per element; d-beta / d-gamma of layer 0 are made on the side stream.  0 off, 1 on; for A/B runs of one
  *                       part an even value selects parts: 2 forward on load, 4 weight-gradient on load, 8 dz(0), or their sums.
+ *   "bn_in_1x1"         the normalise pass (BN + LeakyReLU + residual add) of the layer in front of a residual block's first 1x1
+ *                       conv runs inside that conv (conv1x1_mfma.hip): the kernel sums the statistics slots, publishes the
+ *                       layer's vectors, forms the activation while staging z as its operand and writes it once.  Same bits
+ *                       per element as the separate pass.  Needs "conv1x1_persist".  0 off, 1 on for the shape classes that
+ *                       measured faster than the two launches, 2 on for every launch the kernel takes.
  *   "wgrad_fused_taps"  weight-gradients of conv_0 / conv_1 / conv_2 / conv_3 from halo tiles / streaming units (wgrad0, wgrad1,
  *                       wgrad9) instead of the generic kernel.  Same products, other float-atomic summation order.
  * Unknown keys return FV_ERR_INVALID.  The environment variable FV_OPTIONS="key=0,key=1" sets initial values at fv_create. */
@@ -305,6 +310,21 @@ int fv_bn_bwd_slots(fv_ctx* ctx, const float* g, const float* z, const float* sc
 int fv_conv2d_forward_slots_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky,
                                   const float* w, int B, int H, int W, int cin, int cout, int ksize, int stride, float* z,
                                   double* slots, int nslot);
+/* fv_bn_act_slots of the producing layer + fv_conv2d_forward_slots of a 1x1 stride-1 conv in one kernel (option "bn_in_1x1"):
+ * z_in [B][H][W][cin] is the producing layer's raw conv output with its statistics in in_slots [in_nslot][2][cin]; the kernel
+ * publishes mean / invstd / scale / shift [cin] (+ the moving statistics when given), writes a_out = LeakyReLU(z_in*scale+shift)
+ * (+ skip when given) and z = conv(a_out, w) with its column sums added to slots.  cin % 32 == 0, cin <= 512, cout % 4 == 0,
+ * cout > 32.  a_out, z and the vectors are bit-identical to the two calls. */
+int fv_conv2d_forward_slots_bn_stats_in(fv_ctx* ctx, const float* z_in, const double* in_slots, int in_nslot, const float* gamma,
+                                        const float* beta, float eps, float momentum, float* mean, float* invstd, float* scale,
+                                        float* shift, float* moving_mean, float* moving_var, const float* skip, float* a_out,
+                                        float leaky, const float* w, int B, int H, int W, int cin, int cout, float* z,
+                                        double* slots, int nslot);
+/* Which normalise passes of a training step run inside the next layer's 1x1 conv under option value `option` (and
+ * "conv1x1_persist" on): folded[l] = 1 when layer l's pass is folded into layer l + 1's forward, else 0, for the n =
+ * fv_num_layers() / fv_yolov3_num_layers() layers.  Needs no device. */
+int fv_train_bn_in_1x1_plan(int option, int batch, int image_size, int32_t* folded, int n);
+int fv_yolov3_train_bn_in_1x1_plan(int option, int batch, int image_size, int out_channels, int32_t* folded, int n);
 /* fv_conv2d_wgrad with the same input transform (same shapes). */
 int fv_conv2d_wgrad_bn_in(fv_ctx* ctx, const float* z_in, const float* in_scale, const float* in_shift, float leaky,
                           const float* dy, int B, int H, int W, int cin, int cout, int dy_stride, int ksize, int stride,
