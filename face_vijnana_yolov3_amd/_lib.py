@@ -163,6 +163,10 @@ def _declare(L):
         'fv_fid_batch_workspace_bytes': (sz, [i32, i32]),
         'fv_fid_batch_train_step': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         'fv_fid_towers_dense_dgrad': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i32]),
+        'fv_fid_margin_workspace_bytes': (sz, [i32, i32]),
+        'fv_fid_margin_softmax_loss_grad': (i32, [vp, vp, vp, vp, i32, vp, i32, i32, f64, f64, f64, vp, sz, vp, vp, vp, vp, vp, vp]),
+        'fv_fid_cls_workspace_bytes': (sz, [i32, i32, i32]),
+        'fv_fid_cls_train_step': (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, f64, f64, vp, sz, vp, vp, vp, vp, vp]),
         'fv_fid_towers_dense_wgrad': (i32, [vp, vp, vp, vp, i32, vp, i32, i64, vp]),
         'fv_fid_match': (i32, [vp, vp, i32, vp, i32, vp, vp]),
         'fv_fid_pair_dists': (i32, [vp, vp, i64, ctypes.POINTER(PairBlock), i32, ctypes.POINTER(f32), i32, vp, i64, vp]),

@@ -49,6 +49,16 @@ constexpr int FID_BATCH_MAX = 1024;
 int fv_fid_batch_triplet(fv_ctx* ctx, const float* pre, const float* u, const int32_t* subjects, int M, double margin, int mode,
                          double loss_weight, float* loss, float* dE, float* dbias, int32_t* pos_index, int32_t* neg_index, int32_t* kind,
                          double* d_ap, double* d_an);
+// additive-margin softmax over the subjects (fid_margin.hip) on M labelled rows and the class kernel W [C][64];
+// include/fv_hotpath.h, fv_fid_margin_softmax_loss_grad, has the contract.  1 <= M <= FID_BATCH_MAX, 1 <= C <= FID_CLASSES_MAX; u, W
+// and the workspace (fv_fid_margin_ws_bytes; 0 for a shape that is not served) 16-byte aligned.  fv_fid_margin_check: the
+// refusals of the scalar arguments alone, for a caller that enqueues other work first.
+constexpr int FID_CLASSES_MAX = 32768;
+size_t fv_fid_margin_ws_bytes(int M, int C);
+int fv_fid_margin_check(fv_ctx* ctx, const char* who, int M, int C, int kind, double scale, double margin, double loss_weight);
+int fv_fid_margin_softmax(fv_ctx* ctx, const float* pre, const float* u, const int32_t* labels, int M, const float* W, int C, int kind,
+                          double scale, double margin, double loss_weight, void* workspace, size_t workspace_bytes, float* loss,
+                          float* dE, float* dbias, float* dW, int32_t* pred, double* cos_t);
 // dX = dE . W^T, written (not added) into the rows of dX
 int fv_fid_dense_dgrad(fv_ctx* ctx, const float* dE, int M, long long F, const float* W, FidRows dX);
 // The reconstruction model's head: u [M][64] = relu(l2_normalize(ids)), x [M][F] = u . W^T + bias (W the dense kernel [F][64])

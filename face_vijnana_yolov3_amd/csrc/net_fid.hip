@@ -193,22 +193,19 @@ int fv_fid_train_step_dp(fv_ctx* ctx, const float* params, float* bn_state, cons
     return FV_OK;
 }
 
-int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* subjects, int M,
-                            int image_size, int mode, double margin, void* workspace, size_t workspace_bytes, float* grads, float* loss,
-                            int32_t* pos_index, int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an) {
-    if (!ctx) return FV_ERR_INVALID;
-    FV_REQUIRE(ctx, params && bn_state && x && subjects && workspace && grads && loss && pos_index && neg_index && kind && d_ap && d_an,
-               "fid_batch_train_step: NULL buffer");
-    FV_REQUIRE(ctx, M <= FID_BATCH_MAX, "fid_batch_train_step: M %d beyond the loss's %d rows", M, FID_BATCH_MAX);
-    FV_REQUIRE(ctx, mode == 0 || mode == 1, "fid_batch_train_step: mode %d (0 batch hard, 1 batch semi-hard)", mode);
-    FV_REQUIRE(ctx, std::isfinite(margin) && margin > 0.0, "fid_batch_train_step: margin %g is not finite and > 0", margin);
-    if (int rc = check_batch(ctx, "fid_batch_train_step", M, image_size)) return rc;
-    BatchWs w = make_batch(workspace, M, image_size);
-    if (w.bytes > workspace_bytes)
-        return fv_fail(ctx, FV_ERR_WORKSPACE, "fid_batch_train_step: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+}  // extern "C"
+
+namespace {
+
+// One tower over the M images of a labelled batch: forward in training-mode BN (one update of the moving statistics: update
+// ctx->bn_ema_step, as the caller set it), the dense layer and l2_normalize over the M rows, `loss_call(w, dbias)` -- which
+// enqueues the loss on w.pre / w.u and writes w.dE and the dense bias gradient --, the dense gradients and one backward of the base.
+template <class LossCall>
+int labelled_batch_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, int M, int image_size, BatchWs& w,
+                        float* grads, LossCall&& loss_call) {
     Plan& p = w.t;
     TailLend lend(ctx, p.tail, p.tail_floats);
-    EmaReset ema_reset{ctx};   // the one update of the moving statistics is update ctx->bn_ema_step, as the caller set it
+    EmaReset ema_reset{ctx};
     const Net& N = net();
     const long long F = feat_floats(image_size);
     const int64_t dense_off = base_param_count();
@@ -232,13 +229,61 @@ int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, c
     const FidRows X{{p.k.a[NB - 1], nullptr, nullptr}, M};
     if (int rc = fv_fid_dense_fwd(ctx, X, M, F, params + dense_off, w.part)) return rc;
     if (int rc = fv_fid_dense_finish(ctx, w.part, fv_fid_chunks(F), M, params + dense_off + F * FID_DIM, w.pre, w.u)) return rc;
-    if (int rc = fv_fid_batch_triplet(ctx, w.pre, w.u, subjects, M, margin, mode, 1.0, loss, w.dE, grads + dense_off + F * FID_DIM,
-                                      pos_index, neg_index, kind, d_ap, d_an)) return rc;
+    if (int rc = loss_call(w, grads + dense_off + F * FID_DIM)) return rc;
     if (int rc = fv_fid_dense_wgrad(ctx, X, w.dE, M, F, grads + dense_off)) return rc;
     if (int rc = fv_fid_dense_dgrad(ctx, w.dE, M, F, params + dense_off, FidRows{{p.G[0], nullptr, nullptr}, M})) return rc;
     WgradPipe pipe(t, nullptr, nullptr, p.G[2], p.G[3]);
     if (int rc = base_backward(pipe, NB, x, p.G, {}, false)) return rc;
     return pipe.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* subjects, int M,
+                            int image_size, int mode, double margin, void* workspace, size_t workspace_bytes, float* grads, float* loss,
+                            int32_t* pos_index, int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, params && bn_state && x && subjects && workspace && grads && loss && pos_index && neg_index && kind && d_ap && d_an,
+               "fid_batch_train_step: NULL buffer");
+    FV_REQUIRE(ctx, M <= FID_BATCH_MAX, "fid_batch_train_step: M %d beyond the loss's %d rows", M, FID_BATCH_MAX);
+    FV_REQUIRE(ctx, mode == 0 || mode == 1, "fid_batch_train_step: mode %d (0 batch hard, 1 batch semi-hard)", mode);
+    FV_REQUIRE(ctx, std::isfinite(margin) && margin > 0.0, "fid_batch_train_step: margin %g is not finite and > 0", margin);
+    if (int rc = check_batch(ctx, "fid_batch_train_step", M, image_size)) return rc;
+    BatchWs w = make_batch(workspace, M, image_size);
+    if (w.bytes > workspace_bytes)
+        return fv_fail(ctx, FV_ERR_WORKSPACE, "fid_batch_train_step: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    return labelled_batch_step(ctx, params, bn_state, x, M, image_size, w, grads, [&](BatchWs& b, float* dbias) {
+        return fv_fid_batch_triplet(ctx, b.pre, b.u, subjects, M, margin, mode, 1.0, loss, b.dE, dbias, pos_index, neg_index, kind, d_ap,
+                                    d_an);
+    });
+}
+
+size_t fv_fid_cls_workspace_bytes(int M, int C, int image_size) {
+    const size_t loss_bytes = fv_fid_margin_ws_bytes(M, C);
+    if (!loss_bytes || image_size < 32 || image_size % 32) return 0;
+    return carver_at(nullptr, make_batch(nullptr, M, image_size).bytes).off + loss_bytes;
+}
+
+int fv_fid_cls_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* labels, int M,
+                          int image_size, const float* class_kernel, int C, int kind, double scale, double margin, void* workspace,
+                          size_t workspace_bytes, float* grads, float* class_grads, float* loss, int32_t* pred, double* cos_t) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, params && bn_state && x && labels && class_kernel && workspace && grads && class_grads && loss && pred && cos_t,
+               "fid_cls_train_step: NULL buffer");
+    if (int rc = fv_fid_margin_check(ctx, "fid_cls_train_step", M, C, kind, scale, margin, 1.0)) return rc;
+    FV_REQUIRE(ctx, (((uintptr_t)class_kernel | (uintptr_t)workspace) & 15) == 0,
+               "fid_cls_train_step: the class kernel and the workspace must be 16-byte aligned");
+    if (int rc = check_batch(ctx, "fid_cls_train_step", M, image_size)) return rc;
+    BatchWs w = make_batch(workspace, M, image_size);
+    const size_t loss_off = carver_at(nullptr, w.bytes).off, loss_bytes = fv_fid_margin_ws_bytes(M, C);
+    if (loss_off + loss_bytes > workspace_bytes)
+        return fv_fail(ctx, FV_ERR_WORKSPACE, "fid_cls_train_step: workspace %zu < %zu bytes", workspace_bytes, loss_off + loss_bytes);
+    return labelled_batch_step(ctx, params, bn_state, x, M, image_size, w, grads, [&](BatchWs& b, float* dbias) {
+        return fv_fid_margin_softmax(ctx, b.pre, b.u, labels, M, class_kernel, C, kind, scale, margin, 1.0, (char*)workspace + loss_off,
+                                     loss_bytes, loss, b.dE, dbias, class_grads, pred, cos_t);
+    });
 }
 
 }  // extern "C"

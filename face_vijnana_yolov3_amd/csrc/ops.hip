@@ -468,6 +468,16 @@ int fv_fid_batch_triplet_loss_grad(fv_ctx* ctx, const float* pre, const float* u
                                 d_an);
 }
 
+size_t fv_fid_margin_workspace_bytes(int M, int C) { return fv_fid_margin_ws_bytes(M, C); }
+
+int fv_fid_margin_softmax_loss_grad(fv_ctx* ctx, const float* pre, const float* u, const int32_t* labels, int M, const float* W, int C,
+                                    int kind, double scale, double margin, double loss_weight, void* workspace, size_t workspace_bytes,
+                                    float* loss, float* dE, float* dbias, float* dW, int32_t* pred, double* cos_t) {
+    if (!ctx) return FV_ERR_INVALID;
+    return fv_fid_margin_softmax(ctx, pre, u, labels, M, W, C, kind, scale, margin, loss_weight, workspace, workspace_bytes, loss, dE,
+                                 dbias, dW, pred, cos_t);
+}
+
 int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
                               int per) {
     if (!ctx) return FV_ERR_INVALID;

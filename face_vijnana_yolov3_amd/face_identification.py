@@ -6,11 +6,14 @@ variant), the facial-ID database (`make_facial_ids_db`, `register_facial_ids`, f
 (fi.py:994-1153) and `main` (fi.py:1715-1760) for the modes it dispatches, and the data mode (`create_db_fi` /
 `save_extracted_face`, fi.py:78-280) that cuts the face crops and writes the subject db everything else reads.  The hot path is
 the C ABI (fv_fid_extract, fv_fid_train_step(_dp), fv_adam_step, fv_letterbox_crops, fv_crop_nearest_u8, fv_gather_u8_f32,
-fv_fid_match, fv_fid_pair_dists, fv_fid_mine_negatives, fv_fid_batch_train_step, fv_draw_prims_u8); this module holds the
-weights and drives it.  fi_conf.hps['triplet_mining'] ('semi_hard' / 'hardest'; not in the reference, off unless asked for) has
+fv_fid_match, fv_fid_pair_dists, fv_fid_mine_negatives, fv_fid_batch_train_step, fv_fid_cls_train_step, fv_draw_prims_u8); this
+module holds the weights and drives it.
+fi_conf.hps['triplet_mining'] ('semi_hard' / 'hardest'; not in the reference, off unless asked for) has
 train() choose every triplet's negative from the model's current facial IDs (DESIGN.md section 21);
 fi_conf.hps['batch_mining'] ('batch_hard' / 'batch_semi_hard'; likewise opt-in) trains on batches of P subjects x K crops through
 one tower and forms the triplets inside each batch.
+fi_conf.hps['margin_softmax'] ('cosface' / 'arcface'; likewise opt-in) trains the same batches as a classification over the db's
+subjects, a softmax with an additive margin over a class kernel of its own (fv_fid_cls_train_step).
 fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
@@ -47,6 +50,10 @@ ALPHA = 0.2                     # fi.py:66
 TRIPLET_MARGIN = ALPHA          # the loss's margin is the mining band's width: one number
 BATCH_MINING_MODES = {'batch_hard': 0, 'batch_semi_hard': 1}   # fv_fid_batch_triplet_loss_grad's mode
 BATCH_MAX_ROWS = 1024           # rows one fv_fid_batch_triplet_loss_grad call takes
+MARGIN_SOFTMAX_KINDS = {'cosface': 0, 'arcface': 1}            # fv_fid_margin_softmax_loss_grad's kind
+MARGIN_SOFTMAX_MARGINS = {'cosface': 0.35, 'arcface': 0.5}     # the papers' values (Wang et al. 2018; Deng et al. 2019)
+MARGIN_SOFTMAX_SCALE = 30.0
+CLASSES_MAX = 32768             # class rows one fv_fid_margin_softmax_loss_grad call takes
 DENSE1_DIM = 64                 # the loss slices 0:64 / 64:128 / 128:192 (fi.py:72-76)
 RESOURCE_TYPE_UCCS = 'uccs'
 RESOURCE_TYPE_VGGFACE2 = 'vggface2'
@@ -198,6 +205,81 @@ class FidModel(Model):
 
     def train_on_labelled_batch(self, x, subjects, mode, lr, beta_1, beta_2, decay=0.0, margin=None):
         loss = self.forward_backward_batch(x, subjects, mode, margin)
+        self.adam_step(lr, beta_1, beta_2, decay)
+        return loss
+
+    # ------------------------------------------------------------------ training with a margin softmax
+    def init_classes(self, C, seed=0):
+        """The class kernel [C][64] of the margin softmax: rows drawn from np.random.RandomState(seed).standard_normal, each
+        normalised to length 1, float32; its gradient and Adam vectors start at zero."""
+        C = int(C)
+        if not 1 <= C <= CLASSES_MAX:
+            raise ValueError('init_classes takes 1 .. %d classes, got %d' % (CLASSES_MAX, C))
+        w = np.random.RandomState(int(seed)).standard_normal((C, DENSE1_DIM))
+        w = (w / np.sqrt((w * w).sum(-1, keepdims=True))).astype(np.float32)
+        self.set_classes(w)
+
+    def set_classes(self, kernel):
+        self.class_kernel = torch.as_tensor(np.asarray(kernel, np.float32)).to(self.dev).contiguous()
+        self.class_grads = torch.zeros_like(self.class_kernel)
+        self.class_m = torch.zeros_like(self.class_kernel)
+        self.class_v = torch.zeros_like(self.class_kernel)
+
+    def _cls_workspace(self, M):
+        """The workspace of fv_fid_cls_train_step, under a key of its own (nothing else is evicted), grown to the largest call."""
+        n = int(lib().fv_fid_cls_workspace_bytes(M, int(self.class_kernel.shape[0]), self.image_size))
+        if n == 0:
+            raise FvError('unsupported batch/classes/image_size %r' % ((M, int(self.class_kernel.shape[0]), self.image_size),))
+        key = (0, self.image_size, 'classified_batch')
+        if key not in self._ws or self._ws[key].numel() < n:
+            self._ws.pop(key, None)
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
+        return self._ws[key]
+
+    def forward_backward_classes(self, x, labels, kind='cosface', scale=MARGIN_SOFTMAX_SCALE, margin=None):
+        """One tower over the labelled batch x (M,S,S,3), labels (M,) int32 class indices (< 0: an unknown identity), the margin
+        softmax over self.class_kernel (fv_fid_cls_train_step; kind 'cosface' / 'arcface' or 0 / 1; margin: the paper's):
+        gradients in self.grads and self.class_grads, ONE update of the BN moving statistics; returns the loss as a 1-element
+        CUDA tensor (no host sync).  self.class_selection keeps pred (int32) and cos_t (float64), CUDA tensors of M.  Labels
+        handed over as a host array are checked against the class count."""
+        if getattr(self, 'class_kernel', None) is None:
+            raise ValueError('forward_backward_classes needs a class kernel: call init_classes first')
+        self.ensure_optimizer()
+        x = self._as_input(x)
+        M, C = x.shape[0], int(self.class_kernel.shape[0])
+        if not torch.is_tensor(labels):
+            labels = np.asarray(labels)
+            if labels.size and int(labels.max()) >= C:
+                raise ValueError('forward_backward_classes: label %d is not below the %d classes' % (int(labels.max()), C))
+            labels = torch.as_tensor(labels)
+        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        if lab.dim() != 1 or lab.shape[0] != M:
+            raise ValueError('forward_backward_classes expects one label per image (%d images, labels of shape %r)' % (M, tuple(lab.shape)))
+        if M > BATCH_MAX_ROWS:
+            raise ValueError('forward_backward_classes takes at most %d images, got %d' % (BATCH_MAX_ROWS, M))
+        name = kind if isinstance(kind, str) else {v: k for k, v in MARGIN_SOFTMAX_KINDS.items()}.get(kind)
+        if isinstance(kind, bool) or name not in MARGIN_SOFTMAX_KINDS:
+            raise ValueError('forward_backward_classes: kind %r (available: %s)' % (kind, ', '.join(sorted(MARGIN_SOFTMAX_KINDS))))
+        margin = MARGIN_SOFTMAX_MARGINS[name] if margin is None else margin
+        ws = self._cls_workspace(M)
+        sel = dict(pred=torch.empty(M, dtype=torch.int32, device=self.dev), cos_t=torch.empty(M, dtype=torch.float64, device=self.dev))
+        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
+        rc = lib().fv_fid_cls_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), ptr(lab), M, self.image_size,
+                                         ptr(self.class_kernel), C, MARGIN_SOFTMAX_KINDS[name], float(scale), float(margin), ptr(ws),
+                                         ws.numel(), ptr(self.grads), ptr(self.class_grads), ptr(self._loss), ptr(sel['pred']),
+                                         ptr(sel['cos_t']))
+        self.ctx.check(rc, 'fv_fid_cls_train_step')
+        self.bn_updates += 1
+        self.class_selection = sel
+        return self._loss
+
+    def train_on_classified_batch(self, x, labels, kind, scale, margin, lr, beta_1, beta_2, decay=0.0):
+        """forward_backward_classes, then Adam over the class kernel (its own m / v; the same iteration, lr, betas and decay)
+        and over the model."""
+        from . import ops
+        loss = self.forward_backward_classes(x, labels, kind, scale, margin)
+        ops.adam_step(self.ctx, self.class_kernel, self.class_grads, self.class_m, self.class_v, self.iterations, lr, beta_1, beta_2,
+                      1e-7, decay)
         self.adam_step(lr, beta_1, beta_2, decay)
         return loss
 
@@ -726,6 +808,10 @@ def refuse_mining_on_ranks(hps, ranks):
     if int(ranks) > 1 and batch_mining_mode(hps) is not None:
         raise NotImplementedError('fi_conf.hps.batch_mining with multi_gpu and %d ranks is not implemented: train on one GPU, '
                                   'or without in-batch mining' % int(ranks))
+    # the margin softmax across ranks needs the class gradients and the softmax sums all-reduced, and two GPUs to prove
+    if int(ranks) > 1 and margin_softmax_kind(hps) is not None:
+        raise NotImplementedError('fi_conf.hps.margin_softmax with multi_gpu and %d ranks is not implemented: train on one GPU, '
+                                  'or without the margin softmax' % int(ranks))
 
 
 def batch_mining_mode(hps):
@@ -763,6 +849,58 @@ def batch_mining_conf(hps, image_size):
         raise ValueError('fi_conf.hps: pk_subjects * pk_crops = %d images, one step at image_size %d takes at most %d'
                          % (P * K, int(image_size), most))
     return dict(mode=mode, P=P, K=K, seed=seed)
+
+
+def margin_softmax_kind(hps):
+    """hps['margin_softmax'] -> None (absent, None or 'none') or 'cosface' / 'arcface'; ValueError for anything else."""
+    kind = hps.get('margin_softmax')
+    if kind is None or kind == 'none':
+        return None
+    if not isinstance(kind, str) or kind not in MARGIN_SOFTMAX_KINDS:
+        raise ValueError('fi_conf.hps.margin_softmax %r is not valid (available: none, %s)' % (kind, ', '.join(sorted(MARGIN_SOFTMAX_KINDS))))
+    return kind
+
+
+def _hps_float(hps, key, default, below):
+    """A finite number in (0, below); bool and strings are refused."""
+    v = hps.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not 0 < v < below:
+        raise ValueError('fi_conf.hps.%s must be a number in (0, %g), got %r' % (key, below, v))
+    return float(v)
+
+
+def margin_softmax_conf(hps, image_size):
+    """hps -> None (no margin softmax) or dict(kind, scale, margin, seed, P, K, pk_seed): hps['margin_softmax'], ms_scale (> 0,
+    default 30), ms_margin (cosface: in (0, 1), default 0.35; arcface: in (0, pi / 2), default 0.5), ms_seed (the class kernel's,
+    default 0) and the PK sampler's pk_crops / pk_subjects / pk_seed with batch_mining_conf's defaults and limits.  ValueError for
+    a value that is not served and for margin_softmax together with batch_mining or triplet_mining.  Needs no device."""
+    kind = margin_softmax_kind(hps)
+    if kind is None:
+        return None
+    if mining_mode(hps) is not None or batch_mining_mode(hps) is not None:
+        raise ValueError('fi_conf.hps.margin_softmax trains without triplets: set it without batch_mining and triplet_mining')
+    scale = _hps_float(hps, 'ms_scale', MARGIN_SOFTMAX_SCALE, float('inf'))
+    margin = _hps_float(hps, 'ms_margin', MARGIN_SOFTMAX_MARGINS[kind], 1.0 if kind == 'cosface' else float(np.pi / 2))
+    seed = _hps_int(hps, 'ms_seed', 0, 0)
+    pk = batch_mining_conf(dict(hps, batch_mining='batch_hard', triplet_mining=None), image_size)
+    return dict(kind=kind, scale=scale, margin=margin, seed=seed, P=pk['P'], K=pk['K'], pk_seed=pk['seed'])
+
+
+def check_class_count(C):
+    if int(C) > CLASSES_MAX:
+        raise ValueError('fi_conf.hps.margin_softmax: the db holds %d subjects, the class kernel takes at most %d' % (int(C), CLASSES_MAX))
+
+
+def subject_list(subject_ids, codes):
+    """The subject id of every class: ids[c] is the id subject_codes gave code c (int64 for UCCS, bytes for VGGFace2)."""
+    C = int(codes.max()) + 1 if len(codes) else 0
+    ids = [None] * C
+    for sid, c in zip(subject_ids, codes.tolist()):
+        if c >= 0:
+            ids[c] = sid
+    if all(isinstance(v, str) for v in ids):
+        return np.char.encode(np.asarray(ids, dtype=str), 'utf8') if ids else np.zeros(0, 'S1')
+    return np.asarray(ids, np.int64)
 
 
 def pk_batches(codes, P, K, rng):
@@ -1220,6 +1358,7 @@ class FaceIdentifier(object):
     """Face identifier on the Darknet-53 base of YOLOv3."""
 
     MODEL_PATH = 'face_identifier.h5'
+    CLASSES_PATH = 'face_identifier_classes.h5'    # the margin softmax's class kernel and the subject id of every class
     BASE_MODEL_PATH = 'yolov3_base.h5'
     DARKNET_WEIGHTS_PATH = 'yolov3.weights'
 
@@ -1246,6 +1385,10 @@ class FaceIdentifier(object):
         self.last_mining = None
         self.batch_mining = batch_mining_conf(self.hps, self.image_size)       # likewise
         self.last_batch_mining = None
+        self.margin_softmax = margin_softmax_conf(self.hps, self.image_size)   # likewise
+        self.last_margin_softmax = None
+        if self.margin_softmax is not None:
+            self._check_db_classes()
         if device is None:           # FV_DEVICE: several ranks on ONE device, to rehearse N > 1 on a one-GPU box (gloo transport)
             device = int(os.environ.get('FV_DEVICE', os.environ.get('LOCAL_RANK', 0)))
         self.model = FidModel(self.image_size, device)
@@ -1265,6 +1408,15 @@ class FaceIdentifier(object):
             from .face_detection import FaceDetector
             self._fd = FaceDetector(self._full_conf['fd_conf'])
         return self._fd
+
+    def _check_db_classes(self):
+        """ValueError when the subject db (read when it is there; train() checks the sequence's in any case) holds more subjects
+        than the class kernel takes."""
+        import pandas as pd
+        db_file = db_files(self.conf.get('resource_type'))
+        if db_file is not None and os.path.exists(db_file[0]):
+            sids = pd.read_csv(db_file[0]).iloc[:, 1:]['subject_id']
+            check_class_count(int(sids[sids != -1].nunique()))
 
     def _load_base(self):
         """YOLOV3Base (fi.py:398-614), as FaceDetector._load_base: yolov3_base.h5 when yolov3_base_model_load is set, else the
@@ -1343,6 +1495,13 @@ class FaceIdentifier(object):
         pk = batch_mining_conf(h, self.image_size) if batch_mining_mode(h) is not None else None
         if pk is not None:                 # one rank (refused above otherwise): no collective below
             self._train_pk(tr_gen, pk, steps, epochs)
+            print('Save the model.')
+            self.model.save(self.MODEL_PATH)
+            trainer.shutdown()
+            return
+        ms = margin_softmax_conf(h, self.image_size) if margin_softmax_kind(h) is not None else None
+        if ms is not None:                 # one rank (refused above otherwise): no collective below
+            self._train_classes(tr_gen, ms, steps, epochs)
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
             trainer.shutdown()
@@ -1430,6 +1589,80 @@ class FaceIdentifier(object):
                       % (e + 1, epochs, mean, pk['mode'], c[0], c[1], c[2], c[3], self.last_batch_mining['active']))
         finally:
             inputs.close()
+
+    def _train_classes(self, tr_gen, ms, steps, epochs):
+        """train() with hps['margin_softmax']: the batches of _train_pk (pk_batches, one generator seeded
+        with pk_seed), every one through FidModel.train_on_classified_batch with the rows' subject codes as class labels,
+        C = max code + 1.  The class kernel is read from face_identifier_classes.h5 when model_loading is set and the file holds
+        this db's subject list, and initialised (ms_seed) otherwise; it is written back, with the subject list, after the last
+        epoch.  Per epoch one line: the mean loss, the training accuracy (pred == label over the labelled rows) and the mean
+        target cosine, summed on the device and read back once.  self.last_margin_softmax: the batches of every epoch, the class
+        count, the last epoch's accuracy and mean cosine."""
+        from .crop_store import HOST, TripletInputs, store_budget
+        from .hdf5_lite import write_hdf5
+        m, h, S = self.model, self.hps, self.image_size
+        labels = list(tr_gen.db.index)
+        sids = list(tr_gen.db['subject_id'])
+        codes = subject_codes(sids)
+        C = int(codes.max()) + 1 if len(codes) else 0
+        if C < 1:
+            raise ValueError('fi_conf.hps.margin_softmax: the db holds no subject with a known identity')
+        check_class_count(C)
+        subjects = subject_list(sids, codes)
+        kernel = self._saved_classes(subjects) if self.model_loading else None
+        if kernel is None:
+            m.init_classes(C, ms['seed'])
+        else:
+            m.set_classes(kernel)
+        rng = np.random.default_rng(ms['pk_seed'])
+        rows_most = ms['P'] * ms['K']
+        m.ensure_optimizer()
+        m._cls_workspace(rows_most)        # before the store's budget is taken from what is free
+        if h.get('crop_store', CROP_STORE_DEFAULT):
+            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, store_budget(h, m.dev),
+                                   self._loader_threads(), slots=max(3 * tr_gen.batch_size, rows_most))
+        else:
+            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, 0, self._loader_threads(), tier=HOST)
+        self.last_margin_softmax = dict(batches=[], classes=C, accuracy=None, cos_t=None)
+        try:
+            for e in range(epochs):
+                batches = pk_batches(codes, ms['P'], ms['K'], rng)[:steps]
+                self.last_margin_softmax['batches'].append(batches)
+                losses = []
+                sums = torch.zeros(3, dtype=torch.float64, device=m.dev)      # labelled rows, hits, sum of cos_t
+                feed = inputs.crop_batches([[labels[r] for r in b] for b in batches])
+                for b, x in zip(batches, feed):
+                    lab = torch.from_numpy(codes[b]).to(m.dev)
+                    loss = m.train_on_classified_batch(x, lab, ms['kind'], ms['scale'], ms['margin'], h['lr'], h['beta_1'], h['beta_2'],
+                                                       h.get('decay', 0.0))
+                    losses.append(loss.clone())
+                    sel = m.class_selection
+                    known = lab >= 0
+                    sums += torch.stack([known.sum().double(), ((sel['pred'] == lab) & known).sum().double(),
+                                         torch.where(known, sel['cos_t'], torch.zeros_like(sel['cos_t'])).sum()])
+                n, hits, cs = (float(v) for v in sums.cpu())
+                mean = float(torch.cat(losses).double().mean().cpu()) if losses else float('nan')
+                acc, ct = (hits / n, cs / n) if n else (float('nan'), float('nan'))
+                self.last_margin_softmax.update(accuracy=acc, cos_t=ct)
+                print('Epoch %d/%d - loss: %.4f - margin softmax (%s) accuracy: %.4f, target cosine: %.4f'
+                      % (e + 1, epochs, mean, ms['kind'], acc, ct))
+        finally:
+            inputs.close()
+        write_hdf5(self.CLASSES_PATH, {'/class_kernel': m.class_kernel.cpu().numpy(), '/subject_ids': subjects})
+
+    def _saved_classes(self, subjects):
+        """The class kernel of face_identifier_classes.h5 when the file is there and holds this subject list, else None."""
+        from .hdf5_lite import is_hdf5, read_hdf5
+        if not os.path.exists(self.CLASSES_PATH) or not is_hdf5(self.CLASSES_PATH):
+            return None
+        data, _ = read_hdf5(self.CLASSES_PATH)
+        kernel, ids = data.get('/class_kernel'), data.get('/subject_ids')
+        if kernel is None or ids is None or np.asarray(kernel).shape != (len(subjects), DENSE1_DIM):
+            return None
+        ids = np.asarray(ids)
+        if ids.shape != subjects.shape or ids.dtype.kind != subjects.dtype.kind or not np.array_equal(ids, subjects):
+            return None
+        return np.asarray(kernel, np.float32)
 
     # ------------------------------------------------------------------ triplet mining (DESIGN.md section 21)
     def _sequence(self):

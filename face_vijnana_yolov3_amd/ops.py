@@ -2,6 +2,7 @@
 
 Used by the parity tests and by anyone composing the kernels differently from engine.py.
 All tensors are contiguous float32 CUDA (ROCm) tensors in NHWC / OHWI layout."""
+import numpy as np
 import torch
 
 from ._lib import lib, ptr, c_void_p
@@ -331,6 +332,30 @@ def fid_batch_triplet_loss_grad(ctx, pre, u, subjects, margin=0.2, mode=0, grad_
                                               ptr(o['loss']), ptr(o['dE']), ptr(o['dbias']), ptr(o['pos_index']), ptr(o['neg_index']),
                                               ptr(o['kind']), ptr(o['d_ap']), ptr(o['d_an']))
     ctx.check(rc, 'fv_fid_batch_triplet_loss_grad')
+    return o
+
+
+def fid_margin_softmax_loss_grad(ctx, pre, u, labels, W, kind=0, scale=30.0, margin=0.35, grad_weight=1.0, out=None, workspace=None):
+    """pre, u (M, 64) float32, labels (M,) int32 (< 0: an unknown identity), W (C, 64) float32, the class kernel; kind 0 CosFace,
+    1 ArcFace -> dict(loss (1,), dE (M, 64), dbias (64,), dW (C, 64), pred (M,) int32, cos_t (M,) float64).  out: buffers to write
+    into, by those names.  Labels handed over as a host array are checked against C here; on the device a label >= C makes the
+    row one of an unknown identity with pred -2."""
+    M, C = int(pre.shape[0]), int(W.shape[0])
+    if not torch.is_tensor(labels):
+        host = np.asarray(labels)
+        if host.shape != (M,) or (host.size and int(host.max()) >= C):
+            raise ValueError('fid_margin_softmax_loss_grad expects %d labels below %d' % (M, C))
+        labels = torch.from_numpy(host.astype(np.int32)).to(pre.device)
+    out = dict(out or {})
+    new = lambda name, shape, dtype: out[name] if name in out else torch.empty(shape, dtype=dtype, device=pre.device)
+    o = dict(loss=new('loss', (1,), torch.float32), dE=new('dE', (M, 64), torch.float32), dbias=new('dbias', (64,), torch.float32),
+             dW=new('dW', (C, 64), torch.float32), pred=new('pred', (M,), torch.int32), cos_t=new('cos_t', (M,), torch.float64))
+    if workspace is None:
+        workspace = torch.empty(max(16, int(lib().fv_fid_margin_workspace_bytes(M, C))), dtype=torch.uint8, device=pre.device)
+    rc = lib().fv_fid_margin_softmax_loss_grad(ctx.handle, ptr(pre), ptr(u), ptr(labels), M, ptr(W), C, int(kind), float(scale),
+                                               float(margin), float(grad_weight), ptr(workspace), workspace.numel(), ptr(o['loss']),
+                                               ptr(o['dE']), ptr(o['dbias']), ptr(o['dW']), ptr(o['pred']), ptr(o['cos_t']))
+    ctx.check(rc, 'fv_fid_margin_softmax_loss_grad')
     return o
 
 

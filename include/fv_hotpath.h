@@ -609,6 +609,42 @@ size_t fv_fid_batch_workspace_bytes(int M, int image_size);
 int fv_fid_batch_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* subjects, int M,
                             int image_size, int mode, double margin, void* workspace, size_t workspace_bytes, float* grads,
                             float* loss, int32_t* pos_index, int32_t* neg_index, int32_t* kind, double* d_ap, double* d_an);
+/* Softmax over the subjects with an additive margin (CosFace: Wang et al. 2018; ArcFace: Deng et al. 2019) and its gradients.
+ * Device inputs: pre / u [M][64] float as the dense call returns them, labels [M] int32 (a class in [0, C), < 0: an unknown
+ * identity), W [C][64] float, the class kernel; u, W and the workspace 16-byte aligned.  1 <= M <= 1024, 1 <= C <= 32768; kind 0
+ * CosFace, 1 ArcFace; scale s finite and > 0; margin m finite, 0 < m < 1 (kind 0) or 0 < m < pi / 2 (kind 1); loss_weight finite
+ * and > 0.  Device outputs: loss [1], dE [M][64], dbias [64], dW [C][64] float, pred [M] int32, cos_t [M] double.
+ * Everything is computed in fp64 and every stored float is rounded once.
+ *   w^_c = w_c * 1 / sqrt(max(sum_k w_ck^2, 1e-12)) (the l2_normalize rule; the factor is the constant 1e6 where the sum is <=
+ *   1e-12); cos_ic = sum_k u_ik w^_ck; pred[i] = argmax_c cos_ic, the lowest c among equals, for every row.
+ *   A row with y = labels[i] >= 0: cos_t[i] = cos_iy; t = clamp(cos_iy, -1, 1), whose derivative is 1 where -1 <= cos_iy <= 1, else 0.
+ *   kind 0: psi = t - m, psi' = 1.  kind 1: q = 1 - t^2, sin = sqrt(max(q, 1e-12)); if t > cos(pi - m): psi = t cos m - sin sin m,
+ *   psi' = cos m + (q > 1e-12 ? t sin m / sin : 0); otherwise psi = t - m sin(pi - m), psi' = 1 (keeps psi monotone).
+ *   logits z_ic = s cos_ic for c != y, z_iy = s psi; row loss = logsumexp_c(z_i) - z_iy (the row maximum subtracted);
+ *   loss = (1 / V) sum over the V rows with a label >= 0.  A row with a label < 0: cos_t one quiet NaN, nothing added anywhere.
+ *   A label >= C cannot be refused without a sync: the row is treated as label < 0 and pred[i] = -2.
+ *   V == 0: loss 0, all gradients exactly 0, FV_OK.
+ *   gradients, p the softmax of z_i: g_ic = (p_ic - [c = y]) s / V, times psi' clamp' for c = y; dU_i = sum_c g_ic w^_c;
+ *   dE_i = dU_i taken back through l2_normalize and ReLU as in fv_fid_triplet_loss_grad, loss_weight multiplying once where the
+ *   value is rounded; dbias = the column sums of the STORED dE rows (fp64); dW^_c = sum_i g_ic u_i; dW_c = inv_c (dW^_c - w^_c
+ *   (w^_c . dW^_c)) where sum w^2 > 1e-12, else dW^_c 1e6, times loss_weight.  dW is stored, not accumulated.
+ * No atomics: the same inputs give the same bits on every call.  The summation orders over k, c and i are the build's.
+ * workspace: fv_fid_margin_workspace_bytes(M, C) bytes (0 for an M or C out of range); it keeps the [M][C] coefficients g.
+ * Checked before anything is enqueued: a NULL buffer, M / C / kind / scale / margin / loss_weight out of range or a misaligned
+ * buffer is FV_ERR_INVALID, a workspace that is too small FV_ERR_WORKSPACE; the outputs are left untouched. */
+size_t fv_fid_margin_workspace_bytes(int M, int C);
+int fv_fid_margin_softmax_loss_grad(fv_ctx* ctx, const float* pre, const float* u, const int32_t* labels, int M, const float* W, int C,
+                                    int kind, double scale, double margin, double loss_weight, void* workspace,
+                                    size_t workspace_bytes, float* loss, float* dE, float* dbias, float* dW, int32_t* pred,
+                                    double* cos_t);
+/* One training step on a labelled batch with the margin softmax: fv_fid_batch_train_step with the loss exchanged for
+ * fv_fid_margin_softmax_loss_grad (loss_weight 1) over class_kernel [C][64] (device, 16-byte aligned).  One tower, one update of
+ * the moving statistics.  `grads` (the fv_fid_param_count layout) and class_grads [C][64] are overwritten; loss, pred and cos_t
+ * are device buffers as above.  Refusals as both operators', before anything is enqueued. */
+size_t fv_fid_cls_workspace_bytes(int M, int C, int image_size);
+int fv_fid_cls_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const int32_t* labels, int M,
+                          int image_size, const float* class_kernel, int C, int kind, double scale, double margin, void* workspace,
+                          size_t workspace_bytes, float* grads, float* class_grads, float* loss, int32_t* pred, double* cos_t);
 /* dX = dE . w^T ([M][64] x [F][64]^T) stored into the towers' rows; each element one fp32 chain over the 64 columns in order. */
 int fv_fid_towers_dense_dgrad(fv_ctx* ctx, const float* dE, int M, int64_t F, const float* w, float* dx0, float* dx1, float* dx2,
                               int per);

@@ -11,6 +11,13 @@ batch_step: alternating in this process, three blocks eac
 one-tower M = 39 labelled-batch step (fv_fid_batch_train_step + fv_adam_step; 13 subjects of 3 crops), the host clock around
 blocks that end in a synchronise, all blocks reported; then the per-launch device time of the batch loss's three kernels at
 M = 39, 96 and 1024 next to fid_triplet_kernel at B = 13, and the loss's share of the M = 39 step.
+
+    python tools/fid_bench.py --only margin_step [--iters N] [--classes C]
+
+margin_step: alternating in this process, three blocks each of the one-tower M = 39 labelled-batch step
+(fv_fid_batch_train_step + fv_adam_step) and of the margin-softmax step on the same images (fv_fid_cls_train_step + two
+fv_adam_step; C classes, default 1000), all blocks reported; then the per-launch device time of the loss's six kernels inside that
+step and alone at (M, C) = (39, 1000), (96, 8631) and (1024, 8631) for both kinds, and of the class kernel's Adam launch.
 """
 import argparse
 import json
@@ -118,10 +125,51 @@ def batch_step(m, g, iters, rounds=3):
     return out
 
 
+MARGIN_KERNELS = ('fid_margin_cos_kernel', 'fid_margin_row_kernel', 'fid_margin_du_kernel', 'fid_margin_dw_kernel',
+                  'fid_margin_rows_kernel', 'fid_margin_finish_kernel')
+
+
+def margin_step(m, g, iters, C, rounds=3):
+    from face_vijnana_yolov3_amd import ops
+    state0, params0 = m.state.clone(), m.params.clone()
+    P, K = 13, 3
+    x = torch.rand((P * K, S, S, 3), generator=g, device='cuda')
+    subjects = torch.arange(P, dtype=torch.int32, device='cuda').repeat_interleave(K)
+    m.init_classes(C, 0)
+    ms = dict(batch_mining_m39=[], margin_softmax_m39=[])
+    for r in range(rounds):
+        for name, step in (('batch_mining_m39', lambda: m.train_on_labelled_batch(x, subjects, 'batch_semi_hard', 1e-6, 0.99, 0.99)),
+                           ('margin_softmax_m39', lambda: m.train_on_classified_batch(x, subjects, 'cosface', 30.0, None, 1e-6, 0.99, 0.99))):
+            ms[name].append(round(1e3 * timed(step, iters, 1 if r == 0 else 0), 2))
+            m.params.copy_(params0); m.state.copy_(state0)
+    out = dict(image_size=S, classes=C, iters_per_block=iters, step_ms_blocks=ms)
+    out['margin_loss_us_in_step_m39'] = profiled_us(m, lambda: m.forward_backward_classes(x, subjects, 'cosface'), MARGIN_KERNELS)
+    out['margin_loss_us_in_step_m39']['total'] = round(sum(out['margin_loss_us_in_step_m39'].values()), 2)
+    m.params.copy_(params0); m.state.copy_(state0)
+    adam = lambda: ops.adam_step(m.ctx, m.class_kernel, m.class_grads, m.class_m, m.class_v, 0, 1e-6, 0.99, 0.99)
+    out['class_adam_us'] = profiled_us(m, adam, ('adam_kernel',))
+    alone = {}
+    for M, Cc in ((39, 1000), (96, 8631), (1024, 8631)):
+        pre = torch.randn((M, 64), generator=g, device='cuda')
+        r = torch.relu(pre)
+        u = r / r.norm(dim=1, keepdim=True).clamp_min(1e-6)
+        W = 0.1 * torch.randn((Cc, 64), generator=g, device='cuda')
+        labels = (torch.arange(M, device='cuda') % Cc).to(torch.int32)
+        ws = torch.empty(int(ops.lib().fv_fid_margin_workspace_bytes(M, Cc)), dtype=torch.uint8, device='cuda')
+        for kind in (0, 1):
+            us = profiled_us(m, lambda: ops.fid_margin_softmax_loss_grad(m.ctx, pre, u, labels, W, kind, 30.0, 0.35 if kind == 0 else 0.5,
+                                                                         workspace=ws), MARGIN_KERNELS)
+            us['total'] = round(sum(us.values()), 2)
+            alone['m%d_c%d_kind%d' % (M, Cc, kind)] = us
+    out['margin_loss_us_alone'] = alone
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=5)
-    ap.add_argument('--only', choices=['batch_step'], default=None)
+    ap.add_argument('--only', choices=['batch_step', 'margin_step'], default=None)
+    ap.add_argument('--classes', type=int, default=1000)
     args = ap.parse_args()
     m = FidModel(S, 0)
     m.init_synthetic(seed=7)
@@ -129,6 +177,9 @@ def main():
     g = torch.Generator(device='cuda').manual_seed(0)
     if args.only == 'batch_step':
         print(json.dumps(batch_step(m, g, args.iters)))
+        return
+    if args.only == 'margin_step':
+        print(json.dumps(margin_step(m, g, args.iters, args.classes)))
         return
     out = dict(image_size=S)
     for B in (1, 48):
