@@ -68,6 +68,12 @@ class DrawPrim(ctypes.Structure):
                 ('g', ctypes.c_uint8), ('b', ctypes.c_uint8), ('reserved', ctypes.c_uint8), ('mask_off', ctypes.c_int64)]
 
 
+class YoloDetConf(ctypes.Structure):
+    """fv_yolo_det_conf of include/fv_hotpath.h."""
+    _fields_ = [('box_loss', ctypes.c_int32), ('ignore_thresh', ctypes.c_float), ('box_weight', ctypes.c_float),
+                ('noobj_weight', ctypes.c_float), ('max_boxes', ctypes.c_int32), ('anchors', ctypes.c_float * 18)]
+
+
 BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64)
 
 
@@ -146,6 +152,12 @@ def _declare(L):
         'fv_yolov3_train_workspace_bytes': (sz, [i32, i32, i32]),
         'fv_yolov3_train_step': (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, f64, BUCKET_FN, vp]),
         'fv_yolov3_train_workspace_tensor': (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]),
+        'fv_yolov3_train_workspace_head': (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i64)]),
+        'fv_yolo_det_scratch_bytes': (sz, [i32, i32, i32]),
+        'fv_yolo_det_loss_grad': (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), i32, i32, i32, i32, ctypes.POINTER(YoloDetConf), f64,
+                                        vp, sz, vp, ctypes.POINTER(vp), vp]),
+        'fv_yolov3_train_step_det': (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, f64, BUCKET_FN, vp,
+                                           ctypes.POINTER(YoloDetConf), vp, sz, vp]),
         'fv_yolo_decode_nms_batch': (i32, [vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(f32), f32, f64, i32, i32, i32, i32, i32,
                                            vp, vp, vp, vp]),
         'fv_yolo_decode_nms': (i32, [vp, vp, vp, vp, i32, i32, ctypes.POINTER(f32), f32, f64, i32, i32, i32, i32, i32,

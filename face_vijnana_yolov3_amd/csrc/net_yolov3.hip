@@ -4,6 +4,7 @@
 // flat layout); layers 75..105 add the 13/26/52 heads with two UpSampling2D(2)+concatenate routes.
 // Inference only (the reference defines no training loss for it).
 #include "schedule.h"
+#include "yolo_det_loss.h"
 
 namespace {
 
@@ -234,14 +235,33 @@ int fv_yolov3_train_workspace_tensor(int batch, int image_size, int out_channels
     return kept_tensor(p.k, base, N.L[layer], layer, which, batch, image_size, offset_bytes, count);
 }
 
-int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const float* yt13, const float* yt26,
-                         const float* yt52, int batch, int image_size, int out_channels, void* workspace, size_t workspace_bytes,
-                         float* grads, float* loss, double loss_weight, fv_bucket_fn on_bucket, void* user) {
+int fv_yolov3_train_workspace_head(int batch, int image_size, int out_channels, int scale, int which, size_t* offset_bytes,
+                                   int64_t* count) {
+    if (!offset_bytes || !count || batch < 1 || image_size < 32 || image_size % 32 || out_channels < 18 || out_channels % 3) return FV_ERR_INVALID;
+    if (scale < 0 || scale > 2 || which < 0 || which > 1) return FV_ERR_INVALID;
+    char* const base = (char*)(uintptr_t)65536;
+    const YTrain p = ytrain_plan(base, ynet(out_channels), batch, image_size, out_channels);
+    const int64_t rows = (int64_t)batch * (image_size / (32 >> scale)) * (image_size / (32 >> scale));
+    *offset_bytes = (size_t)((char*)(which ? p.dy[scale] : p.y[scale]) - base);
+    *count = rows * (which ? p.cpad : out_channels);
+    return FV_OK;
+}
+
+// One body for fv_yolov3_train_step (det == nullptr: the fd_loss generalisation) and fv_yolov3_train_step_det (the YOLOv3 detection
+// loss of yolo_det_loss.hip): the same forward and backward, only the loss stage differs.
+static int yolov3_train_step_body(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const float* yt13, const float* yt26,
+                                  const float* yt52, int batch, int image_size, int out_channels, void* workspace, size_t workspace_bytes,
+                                  float* grads, float* loss, double loss_weight, fv_bucket_fn on_bucket, void* user,
+                                  const fv_yolo_det_conf* det, void* det_scratch, size_t det_scratch_bytes, double* det_stats) {
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, loss_weight > 0.0 && loss_weight <= 1.0, "yolov3_train_step: loss_weight must be in (0, 1]");
     FV_REQUIRE(ctx, params && bn_state && x && yt13 && yt26 && yt52 && workspace && grads && loss, "yolov3_train_step: NULL buffer");
     if (int rc = check_batch(ctx, "yolov3_train_step", batch, image_size)) return rc;
     FV_REQUIRE(ctx, out_channels >= 18 && out_channels % 3 == 0, "yolov3_train_step: bad shape (out_channels = 3*(5+classes))");
+    if (det) {
+        if (int rc = fv_det_check(ctx, "yolov3_train_step_det", det, batch, image_size, out_channels / 3 - 5, (out_channels + 31) / 32 * 32,
+                                  det_scratch, det_scratch_bytes, det_stats)) return rc;
+    }
     const YNet& N = ynet(out_channels);
     const int S = image_size, B = batch, nl = (int)N.L.size(), nb = N.nbase;
     const int ncls = out_channels / 3 - 5;
@@ -294,16 +314,20 @@ int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, cons
     if (int rc = train_bn_forward_end(t)) return rc;
     // ------------------------------------------------------------------ loss of the three scales, its gradient, bias gradients
     const float* yt[3] = {yt13, yt26, yt52};
-    const int det[3] = {D13, D26, D52};
+    const int dconv[3] = {D13, D26, D52};
     long long cells[3];
     double* lpart = (double*)p.loss_part;
-    {
+    for (int s = 0; s < 3; ++s) cells[s] = (long long)B * (S / (32 >> s)) * (S / (32 >> s));
+    if (det) {
+        if (int rc = fv_det_loss_launch(ctx, p.y, yt, B, S, ncls, p.cpad, det, loss_weight, det_scratch, loss, p.dy, det_stats)) return rc;
+        for (int s = 0; s < 3; ++s)
+            if (int rc = fv_ew_colsum(ctx, p.dy[s], cells[s], out_channels, p.cpad, (double*)p.colsum_part, grads + N.L[dconv[s]].beta_off)) return rc;
+    } else {
         int off = 0;
         for (int s = 0; s < 3; ++s) {
-            cells[s] = (long long)B * (S / (32 >> s)) * (S / (32 >> s));
             if (int rc = fv_ew_yolo_loss_part(ctx, p.y[s], yt[s], cells[s], ncls, 3, p.cpad, p.dy[s], lpart + off, loss_weight)) return rc;
             off += fv_ew_yolo_loss_blocks(cells[s] * 3);
-            if (int rc = fv_ew_colsum(ctx, p.dy[s], cells[s], out_channels, p.cpad, (double*)p.colsum_part, grads + N.L[det[s]].beta_off)) return rc;
+            if (int rc = fv_ew_colsum(ctx, p.dy[s], cells[s], out_channels, p.cpad, (double*)p.colsum_part, grads + N.L[dconv[s]].beta_off)) return rc;
         }
         if (int rc = fv_ew_yolo_loss_finish(ctx, lpart, cells, 3, loss)) return rc;
     }
@@ -347,6 +371,23 @@ int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, cons
     float* const g[2] = {ga, gb};
     if (int rc = base_backward(pipe, nb, x, g, addend_at)) return rc;
     return pipe.finish();
+}
+
+int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const float* yt13, const float* yt26,
+                         const float* yt52, int batch, int image_size, int out_channels, void* workspace, size_t workspace_bytes,
+                         float* grads, float* loss, double loss_weight, fv_bucket_fn on_bucket, void* user) {
+    return yolov3_train_step_body(ctx, params, bn_state, x, yt13, yt26, yt52, batch, image_size, out_channels, workspace, workspace_bytes,
+                                  grads, loss, loss_weight, on_bucket, user, nullptr, nullptr, 0, nullptr);
+}
+
+int fv_yolov3_train_step_det(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const float* yt13, const float* yt26,
+                             const float* yt52, int batch, int image_size, int out_channels, void* workspace, size_t workspace_bytes,
+                             float* grads, float* loss, double loss_weight, fv_bucket_fn on_bucket, void* user,
+                             const fv_yolo_det_conf* conf, void* scratch, size_t scratch_bytes, double* stats) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, conf && scratch && stats, "yolov3_train_step_det: NULL conf, scratch or stats");
+    return yolov3_train_step_body(ctx, params, bn_state, x, yt13, yt26, yt52, batch, image_size, out_channels, workspace, workspace_bytes,
+                                  grads, loss, loss_weight, on_bucket, user, conf, scratch, scratch_bytes, stats);
 }
 
 }  // extern "C"

@@ -131,6 +131,71 @@ def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_AN
     return out
 
 
+# ----------------------------------------------------------------------------- detection loss of the three-scale head (hps['loss'])
+DET_LOSS_DEFAULTS = {'box_loss': 'giou', 'ignore_thresh': 0.5, 'box_weight': 1.0, 'noobj_weight': 1.0, 'max_boxes': 256}
+DET_BOX_LOSSES = ('l2', 'giou')        # FV_DET_BOX_L2, FV_DET_BOX_GIOU of include/fv_hotpath.h, in this order
+
+
+def det_loss_conf(value, head='three_scale'):
+    """fd_conf.hps['loss'] -> None (absent, None or "fd": the fd_loss generalisation every head trains with today) or the complete
+    parameter dict of the YOLOv3 detection loss (fv_yolo_det_loss_grad) -- "yolo": DET_LOSS_DEFAULTS; an
+    object {"yolo": {...}}: its keys over the defaults; either way plus 'anchors' = YOLO_ANCHORS.  ValueError for an
+    unknown name or key, a value outside its range (box_loss 'l2' / 'giou', ignore_thresh in (0, 1], box_weight and noobj_weight
+    finite and > 0, max_boxes an int in [1, 1024]) and for "yolo" with the single-scale head.  Not in the reference; pure host
+    code."""
+    if value is None or value == 'fd':
+        return None
+    opts = {}
+    if isinstance(value, dict) and set(value) == {'yolo'} and isinstance(value['yolo'], dict):
+        opts = dict(value['yolo'])
+    elif not (isinstance(value, str) and value == 'yolo'):
+        raise ValueError('fd_conf.hps.loss %r is not valid ("fd", "yolo" or {"yolo": {%s}})' % (value, ', '.join(sorted(DET_LOSS_DEFAULTS))))
+    if head != 'three_scale':
+        raise ValueError("fd_conf.hps.loss 'yolo' needs nn_arch.head = 'three_scale' (the single-scale head trains with 'fd')")
+    unknown = sorted(set(opts) - set(DET_LOSS_DEFAULTS))
+    if unknown:
+        raise ValueError('fd_conf.hps.loss has unknown key(s) %s (available: %s)' % (', '.join(map(repr, unknown)),
+                                                                                  ', '.join(sorted(DET_LOSS_DEFAULTS))))
+    c = dict(DET_LOSS_DEFAULTS)
+    c.update(opts)
+    if c['box_loss'] not in DET_BOX_LOSSES:
+        raise ValueError('fd_conf.hps.loss.box_loss %r is not valid (%s)' % (c['box_loss'], ' or '.join(map(repr, DET_BOX_LOSSES))))
+    if not (_is_number(c['ignore_thresh']) and 0 < c['ignore_thresh'] <= 1):
+        raise ValueError('fd_conf.hps.loss.ignore_thresh %r is not valid (an IoU in (0, 1])' % (c['ignore_thresh'],))
+    for k in ('box_weight', 'noobj_weight'):
+        if not (_is_number(c[k]) and c[k] > 0):
+            raise ValueError('fd_conf.hps.loss.%s %r is not valid (a finite number > 0)' % (k, c[k]))
+    if not (isinstance(c['max_boxes'], int) and not isinstance(c['max_boxes'], bool) and 1 <= c['max_boxes'] <= 1024):
+        raise ValueError('fd_conf.hps.loss.max_boxes %r is not valid (an int in [1, 1024])' % (c['max_boxes'],))
+    for k in ('ignore_thresh', 'box_weight', 'noobj_weight'):
+        c[k] = float(c[k])
+    c['anchors'] = [list(map(float, row)) for row in YOLO_ANCHORS]
+    return c
+
+
+DET_STATS = ('box', 'obj', 'noobj', 'cls', 'positives', 'ignored', 'iou_sum', 'iou_gt_50', 'iou_gt_75', 'max_count', 'dropped', 'spare')
+
+
+def det_stats_line(sums, steps, slots):
+    """The epoch line of hps['loss'] = 'yolo': `sums` = the 12 stats of fv_yolo_det_loss_grad added up over the `steps` steps of
+    the epoch (entry 9: their maximum), `slots` = (cell, anchor) slots the steps held in all.  Loss parts are means per step;
+    mean IoU and recall over the assigned slots; the ignored share over the unassigned ones."""
+    s = dict(zip(DET_STATS, (float(v) for v in sums)))
+    pos = max(s['positives'], 1.0)
+    neg = max(float(slots) - s['positives'], 1.0)
+    n = max(int(steps), 1)
+    return ('yolo loss - box: %.4f - obj: %.4f - noobj: %.4f - cls: %.4f - mean IoU: %.4f - recall@0.5: %.4f - recall@0.75: %.4f - '
+            'ignored: %.4f' % (s['box'] / n, s['obj'] / n, s['noobj'] / n, s['cls'] / n, s['iou_sum'] / pos, s['iou_gt_50'] / pos,
+                               s['iou_gt_75'] / pos, s['ignored'] / neg))
+
+
+def check_det_dropped(dropped, max_count, max_boxes):
+    """A box beyond the cap is missing from the ignore mask of its image: an error, never a quietly weaker loss."""
+    if dropped > 0:
+        raise ValueError('fd_conf.hps.loss.max_boxes = %d is too small: an image holds %d assigned boxes (%d dropped this epoch); '
+                         'raise max_boxes (at most 1024)' % (max_boxes, int(max_count), int(dropped)))
+
+
 # ----------------------------------------------------------------------------- training augmentation (hps['augment'])
 AUGMENT_DEFAULTS = {'zoom': [0.75, 1.25], 'flip': 0.5, 'hue': 0.1, 'saturation': 1.5, 'exposure': 1.5, 'seed': 0}
 

@@ -26,6 +26,9 @@ ratios.csv, the model files).  Differences, all documented in DESIGN.md:
   * hps['augment'] (not in the reference, off unless asked for; data.augment_conf) gives every training sample a random zoom and
     translation, a horizontal flip and a hue / saturation / exposure distortion per epoch (Darknet's detector recipe), inside the
     batch's one letterbox launch (fv_letterbox_augment_batch); train() only
+  * hps['loss'] = 'yolo' (not in the reference, off unless asked for; data.det_loss_conf) trains the three-scale head with YOLOv3's
+    detection loss -- ignore mask, box terms on assigned slots only, GIoU or keras-yolo3's box term (fv_yolov3_train_step_det) --
+    and prints its statistics once per epoch; train() only
 """
 import glob
 import json
@@ -109,6 +112,7 @@ class FaceDetector(object):
         self.model_loading = conf['model_loading']
         self.image_size = int(self.nn_arch['image_size'])
         self.augment = data.augment_conf(self.hps.get('augment'))      # ValueError before a device is touched
+        self.det_loss = data.det_loss_conf(self.hps.get('loss'), self.nn_arch.get('head', 'single'))    # likewise
         if self.image_size % 32:
             raise ValueError('image_size must be a multiple of 32 (network stride)')
         if int(self.nn_arch.get('bb_info_c_size', 6)) != 6:
@@ -126,6 +130,7 @@ class FaceDetector(object):
             from .yolov3 import Yolov3
             self.nclass = int(self.nn_arch.get('num_classes', 1))
             self.model = Yolov3(device, out_channels=3 * (5 + self.nclass))
+            self.model.det_loss = self.det_loss
         else:
             self.model = Engine(device)
         # BN moving statistics as the reference's stack updates them (Keras 2.2.4: zero-debiased); "bn_zero_debias": false in the
@@ -211,11 +216,23 @@ class FaceDetector(object):
                         print('%d/%d - loss: %.4f' % (k + 1, steps, lv))
             feeder.set_epoch(epoch)          # hps['augment']: the epoch enters every sample's draw; nothing is prefetched across this line
             run_pipelined(self.model, trainer, feeder, [int(i) for i in order], self.image_size, hp, after_step)
+            if self.det_loss is not None:
+                self._report_det_epoch(trainer)
         feeder.close()
         if self.rank == 0:
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
         trainer.shutdown()
+
+    def _report_det_epoch(self, trainer):
+        """hps['loss'] = 'yolo': one line per epoch from the statistics the steps left on the device (this rank's share of the
+        batches), read here -- after the epoch's last step, where its loss is read too -- so that no step waits for the host.  A box
+        dropped by the cap on ANY rank is an error on every rank (a collective when a group exists: every rank calls this)."""
+        got = self.model.take_det_epoch()
+        dropped = trainer.max_over_ranks(float(got[0][10]) if got else 0.0)
+        data.check_det_dropped(dropped, trainer.max_over_ranks(float(got[0][9]) if got else 0.0), self.det_loss['max_boxes'])
+        if self.rank == 0 and got:
+            print(data.det_stats_line(*got))
 
     # ------------------------------------------------------------------ detect (fd.py:885-949)
     def detect(self, image):

@@ -2,6 +2,8 @@
 
 Used by the parity tests and by anyone composing the kernels differently from engine.py.
 All tensors are contiguous float32 CUDA (ROCm) tensors in NHWC / OHWI layout."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -288,6 +290,45 @@ def yolo_loss_grad(ctx, yp3, yt3, ncls, c_pad, grad_weight=1.0, A=3, dy3=None):
     rc = lib().fv_yolo_loss_grad(ctx.handle, arr(yp3), arr(yt3), c3, ncls, A, c_pad, float(grad_weight), ptr(part), ptr(loss), arr(dy3))
     ctx.check(rc, 'fv_yolo_loss_grad')
     return loss, dy3
+
+
+def yolo_det_conf(conf):
+    """data.det_loss_conf's dict -> the fv_yolo_det_conf struct (floats are rounded to float32 there)."""
+    from ._lib import YoloDetConf
+    from .data import DET_BOX_LOSSES
+    anchors = [float(v) for row in conf['anchors'] for v in row]
+    assert len(anchors) == 18
+    box_loss = conf['box_loss']
+    return YoloDetConf(DET_BOX_LOSSES.index(box_loss) if box_loss in DET_BOX_LOSSES else int(box_loss), conf['ignore_thresh'],
+                       conf['box_weight'], conf['noobj_weight'], int(conf['max_boxes']), (ctypes.c_float * 18)(*anchors))
+
+
+def yolo_det_scratch(batch, image_size, max_boxes, device):
+    """The caller-owned scratch of fv_yolo_det_loss_grad / fv_yolov3_train_step_det as a float64 tensor."""
+    n = lib().fv_yolo_det_scratch_bytes(batch, image_size, max_boxes)
+    if n == 0:
+        raise ValueError('fv_yolo_det_scratch_bytes: bad batch %r, image_size %r or max_boxes %r' % (batch, image_size, max_boxes))
+    return torch.empty(((n + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def yolo_det_loss_grad(ctx, yp3, yt3, batch, image_size, ncls, c_pad, conf, loss_weight=1.0, dy3=None, scratch=None):
+    """The YOLOv3 detection loss on its own: three scales' logits / targets (batch*g_s^2, 3*(5+ncls)), conf = data.det_loss_conf's
+    dict -> loss (1,), [dy_s (batch*g_s^2, c_pad)], stats (12,) float64."""
+    dev = yp3[0].device
+    cells = [batch * ((image_size // 32) << s) ** 2 for s in range(3)]
+    for t in list(yp3) + list(yt3):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    loss = torch.full((1,), float('nan'), dtype=torch.float32, device=dev)
+    stats = torch.full((12,), float('nan'), dtype=torch.float64, device=dev)
+    dy3 = [_new((c, c_pad), yp3[0], None if dy3 is None else dy3[s]) for s, c in enumerate(cells)]
+    if scratch is None:
+        scratch = yolo_det_scratch(batch, image_size, int(conf['max_boxes']), dev)
+    arr = lambda ts: (c_void_p * 3)(*[t.data_ptr() for t in ts])
+    c = yolo_det_conf(conf)
+    rc = lib().fv_yolo_det_loss_grad(ctx.handle, arr(yp3), arr(yt3), batch, image_size, ncls, c_pad, ctypes.byref(c), float(loss_weight),
+                                     ptr(scratch), scratch.numel() * 8, ptr(loss), arr(dy3), ptr(stats))
+    ctx.check(rc, 'fv_yolo_det_loss_grad')
+    return loss, dy3, stats
 
 
 def _towers(ts):

@@ -22,6 +22,11 @@ class Yolov3(model.Model):
     def __init__(self, device=0, out_channels=255, ctx=None):
         self.out_channels = int(out_channels)
         self.nclass = self.out_channels // 3 - 5
+        # data.det_loss_conf's dict: forward_backward then runs fv_yolov3_train_step_det (the YOLOv3 detection loss) and
+        # keeps its statistics in det_stats (12 float64 on the device, the last step's); None: fv_yolov3_train_step
+        self.det_loss = None
+        self.det_stats = None
+        self._det_key = None
         super(Yolov3, self).__init__(ctx or Context(device), yolov3_layer_table(self.out_channels),
                                      lib().fv_yolov3_param_count(self.out_channels), lib().fv_yolov3_state_count(self.out_channels))
 
@@ -83,8 +88,60 @@ class Yolov3(model.Model):
             assert y.numel() == B * (S // dv) ** 2 * self.out_channels, tuple(y.shape)
         ws = self._workspace(B, S, True)
         cb, errors = self._bucket_fn(on_bucket)
-        return self._train_call('fv_yolov3_train_step', ptr(x), ptr(t[0]), ptr(t[1]), ptr(t[2]), B, S, self.out_channels, ptr(ws),
-                                ws.numel(), ptr(self.grads), ptr(self._loss), float(loss_weight), cb, None, errors=errors)
+        if self.det_loss is None:
+            return self._train_call('fv_yolov3_train_step', ptr(x), ptr(t[0]), ptr(t[1]), ptr(t[2]), B, S, self.out_channels, ptr(ws),
+                                    ws.numel(), ptr(self.grads), ptr(self._loss), float(loss_weight), cb, None, errors=errors)
+        conf, scratch = self._det_buffers(B, S)
+        loss = self._train_call('fv_yolov3_train_step_det', ptr(x), ptr(t[0]), ptr(t[1]), ptr(t[2]), B, S, self.out_channels, ptr(ws),
+                                ws.numel(), ptr(self.grads), ptr(self._loss), float(loss_weight), cb, None, ctypes.byref(conf),
+                                ptr(scratch), scratch.numel() * 8, ptr(self.det_stats), errors=errors)
+        # the epoch's running totals stay on the device (no host sync in the step): sums, and the maximum for entry 9
+        self._det_sum.add_(self.det_stats)
+        torch.maximum(self._det_max, self.det_stats, out=self._det_max)
+        self._det_steps += 1
+        self._det_slots += B * 63 * (S // 32) ** 2
+        return loss
+
+    def head_tensor(self, batch, image_size, scale, grad=False):
+        """The raw output (batch*g^2, out_channels) of scale `scale` the last training call left in its workspace, or with grad
+        its gradient (batch*g^2, c_pad); a view."""
+        off, cnt = ctypes.c_size_t(0), ctypes.c_int64(0)
+        rc = lib().fv_yolov3_train_workspace_head(batch, image_size, self.out_channels, scale, 1 if grad else 0, ctypes.byref(off),
+                                                  ctypes.byref(cnt))
+        if rc != 0:
+            raise FvError('no head tensor of scale %d at batch %d, image size %d' % (scale, batch, image_size))
+        rows = batch * ((image_size // 32) << scale) ** 2
+        ws = self._workspace(batch, image_size, True)
+        return ws[off.value:off.value + 4 * cnt.value].view(torch.float32).view(rows, -1)
+
+    def _det_buffers(self, B, S):
+        """-> (fv_yolo_det_conf, scratch) of self.det_loss at this batch / image size; det_stats and the epoch totals on first use."""
+        from . import ops
+        key = (B, S, tuple(sorted((k, str(v)) for k, v in self.det_loss.items())))
+        if self._det_key != key:
+            self._det_conf = ops.yolo_det_conf(self.det_loss)
+            self._det_scratch = ops.yolo_det_scratch(B, S, int(self.det_loss['max_boxes']), self.dev)
+            self._det_key = key
+        if self.det_stats is None:
+            self.det_stats = torch.zeros(12, dtype=torch.float64, device=self.dev)
+            self.reset_det_epoch()
+        return self._det_conf, self._det_scratch
+
+    def reset_det_epoch(self):
+        self._det_sum = torch.zeros(12, dtype=torch.float64, device=self.dev)
+        self._det_max = torch.zeros(12, dtype=torch.float64, device=self.dev)
+        self._det_steps = self._det_slots = 0
+
+    def take_det_epoch(self):
+        """-> (the 12 stats of the steps since the last call: sums, entry 9 their maximum; steps; slots) or None when no step ran
+        with det_loss; host sync.  Resets the totals."""
+        if self.det_stats is None or self._det_steps == 0:
+            return None
+        sums = self._det_sum.cpu().numpy()
+        sums[9] = float(self._det_max[9].item())
+        out = (sums, self._det_steps, self._det_slots)
+        self.reset_det_epoch()
+        return out
 
     def train_on_batch(self, x, targets, lr, beta_1, beta_2, decay=0.0):
         loss = self.forward_backward(x, targets)

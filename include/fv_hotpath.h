@@ -775,6 +775,62 @@ int fv_yolov3_train_step(fv_ctx* ctx, const float* params, float* bn_state, cons
 /* as fv_train_workspace_tensor, for the workspace of fv_yolov3_train_step (BN layers of fv_yolov3_layer) */
 int fv_yolov3_train_workspace_tensor(int batch, int image_size, int out_channels, int layer, int which,
                                      size_t* offset_bytes, int64_t* count);
+/* the head tensors either training step leaves in its workspace: which = 0 the raw output y of scale `scale` (0 = the coarsest
+ * grid), [batch g^2][out_channels]; which = 1 its gradient dy, [batch g^2][c_pad] with c_pad = out_channels rounded up to 32 */
+int fv_yolov3_train_workspace_head(int batch, int image_size, int out_channels, int scale, int which,
+                                   size_t* offset_bytes, int64_t* count);
+/* ---- YOLOv3 detection loss for the three-scale head (not in the reference, which never trains this graph; an
+ * additive part of ABI version 4).  Replaces the loss STAGE of fv_yolov3_train_step: ignore mask, box regression on assigned
+ * slots only, box term in keras-yolo3's form or as 1 - GIoU.
+ * Tensors: y_s (raw head outputs) and t_s (targets of data.encode_gt_three_scale) are dense [batch][g_s][g_s][3][5+ncls] with
+ * g_s = image_size/32 << s, entries [tx, ty, tw, th, obj, cls...]; dy_s is [batch g_s^2][c_pad], c_pad >= 3*(5+ncls), its
+ * padding columns written as exactly 0.  cell_s = 32 >> s network pixels; (aw, ah) = anchors[6 s + 2 a], anchors[6 s + 2 a + 1].
+ * (a) Gather: per image, the slots with t4 == 1 of all three scales in slot order (scale, row, column, anchor) form a list of
+ *     boxes (cx, cy, w, h) = ((col + sigma(t0)) cell, (row + sigma(t1)) cell, aw e^t2, ah e^t3); the first max_boxes are kept,
+ *     the true count is recorded.
+ * (b) Per slot: the predicted box ((col + sigma(y0)) cell, (row + sigma(y1)) cell, aw e^c2, ah e^c3), c = clamp(y, -20, 20);
+ *     best = max IoU with the listed boxes of the same image (0 for an empty list).  With bce(x, z) = max(x,0) - x z +
+ *     log1p(e^-|x|) on the logit x:
+ *       assigned slot (t4 == 1):  bce(y4, 1) + sum_c bce(y_{5+c}, t_{5+c}) + box_weight * box term against the slot's OWN
+ *                                 target box (so a box cut from the list still trains its slot);
+ *       unassigned slot:          0 when best > ignore_thresh, else noobj_weight * bce(y4, 0)   (the mask carries no gradient).
+ *     box term, box_loss = FV_DET_BOX_L2 (keras-yolo3), s = 2 - w h / image_size^2 of the target box:
+ *           s (bce(y0, sigma(t0)) + bce(y1, sigma(t1))) + 0.5 s ((y2 - t2)^2 + (y3 - t3)^2);
+ *     box_loss = FV_DET_BOX_GIOU: 1 - GIoU(predicted, target), differentiated through the decode; an entry with |y| >= 20
+ *     (at the clamp) gets gradient 0.
+ * loss (device float) = the sum over every slot of every scale / batch, unweighted; dy = loss_weight * d loss / d y.
+ * stats (12 device doubles): [0..3] the loss parts box (with box_weight), objectness of the assigned slots, no-object (with
+ * noobj_weight), class -- each / batch, their sum is the loss; [4] assigned slots; [5] ignored unassigned slots; [6] sum of
+ * IoU(predicted, target) over the assigned slots; [7], [8] assigned slots with that IoU > 0.5, > 0.75; [9] the largest
+ * per-image box count; [10] boxes dropped by the cap, summed over the images; [11] 0 (spare).
+ * fp64 inside; per-workgroup partial sums added in a fixed order: deterministic, two runs are bit-identical.
+ * scratch: fv_yolo_det_scratch_bytes(batch, image_size, max_boxes) bytes of device memory, 8-byte aligned, owned by the caller
+ * (0 for a bad argument).  FV_ERR_INVALID before any launch for: NULL buffers, ignore_thresh outside (0, 1], box_weight /
+ * noobj_weight / loss_weight not finite or <= 0, max_boxes outside [1, 1024], unknown box_loss, anchors not finite or <= 0,
+ * c_pad < 3*(5+ncls), image_size not a multiple of 32, a scratch buffer that is too small. */
+#define FV_DET_BOX_L2 0
+#define FV_DET_BOX_GIOU 1
+typedef struct {
+    int32_t box_loss;      /* FV_DET_BOX_L2 / FV_DET_BOX_GIOU */
+    float ignore_thresh;   /* (0, 1] */
+    float box_weight;      /* > 0 */
+    float noobj_weight;    /* > 0 */
+    int32_t max_boxes;     /* 1 .. 1024 listed boxes per image */
+    float anchors[18];     /* network pixels, scale 0 (the coarsest grid) first, (w, h) per anchor */
+} fv_yolo_det_conf;
+size_t fv_yolo_det_scratch_bytes(int batch, int image_size, int max_boxes);
+/* yp3 / yt3 / dy3: HOST arrays of three DEVICE pointers, scale 0 first (as fv_yolo_loss_grad) */
+int fv_yolo_det_loss_grad(fv_ctx* ctx, const float* const* yp3, const float* const* yt3, int batch, int image_size, int ncls,
+                          int c_pad, const fv_yolo_det_conf* conf, double loss_weight, void* scratch, size_t scratch_bytes,
+                          float* loss, float* const* dy3, double* stats);
+/* fv_yolov3_train_step with this loss in place of its loss stage: the same forward, backward, workspace
+ * (fv_yolov3_train_workspace_bytes) and arguments, plus conf, the scratch buffer above and stats.  The activations and the BN
+ * state it leaves are those of fv_yolov3_train_step bit for bit. */
+int fv_yolov3_train_step_det(fv_ctx* ctx, const float* params, float* bn_state, const float* x, const float* yt13,
+                             const float* yt26, const float* yt52, int batch, int image_size, int out_channels,
+                             void* workspace, size_t workspace_bytes, float* grads, float* loss, double loss_weight,
+                             fv_bucket_fn on_bucket, void* user, const fv_yolo_det_conf* conf, void* scratch,
+                             size_t scratch_bytes, double* stats);
 /* replaces decode_netout x3 (yd.py:335-387, with its anchor skip list), correct_yolo_boxes
  * (yd.py:389-404) and do_nms (yd.py:426-444) for ONE image: outputs in the reference's list order;
  * boxes [capacity][4] int32 xmin,ymin,xmax,ymax in image pixels, objness [capacity],
