@@ -138,6 +138,8 @@ def _declare(L):
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_letterbox_augment_batch': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32, i32,
                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), vp]),
+        'fv_letterbox_mosaic_batch': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32, i32, i32,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), i32, vp]),
         'fv_crop_nearest_u8': (i32, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), i32,
                                     ctypes.POINTER(ctypes.c_int32), i32, i32, vp]),
         'fv_gather_u8_f32': (i32, [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_int32), i32, vp]),

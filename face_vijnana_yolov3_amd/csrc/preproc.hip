@@ -320,6 +320,127 @@ __global__ __launch_bounds__(256) void letterbox_augment_kernel(const unsigned c
     }
 }
 
+// Mosaic (hps['mosaic']): a canvas is made of up to four TILES.  A tile is letterbox_augment_kernel's placed crop -- the
+// ch x cw crop letterboxed into a T x T box at (oy, ox), which may reach beyond the canvas -- seen through a WINDOW [wy0, wy1) x
+// [wx0, wx1) of the canvas; a tile's flip mirrors its box in place (local column c -> T - 1 - c).  The windows of a canvas are
+// disjoint; a pixel outside every window, or inside a window but outside the tile's content, is +0.  A workgroup makes the same
+// 64 x 16 output pixels as letterbox_augment_kernel: it zero-fills its LDS stage, then for every tile of its canvas whose window
+// meets its rectangle (a workgroup-uniform test: most workgroups meet one tile, those on a seam two, the one on the centre four)
+// builds the column / row tables and evaluates the taps -- letterbox_augment_kernel's expressions in the same order, so a tile
+// holds letterbox_crops_kernel's bits at image size T -- writing the lanes inside window and content; one barrier, then the same
+// 16-byte row-segment stores.  The tile table travels in the kernel arguments, MOS_TILES tiles (whole canvases) per launch.
+constexpr int MOS_TILES = 48;       // tiles per launch (48 x 68 B of kernel arguments); MOS_PER = tiles per canvas at most
+constexpr int MOS_PER = 4;
+struct MosTable { long long off[MOS_TILES]; int pitch[MOS_TILES], h[MOS_TILES], w[MOS_TILES], w_p[MOS_TILES], h_p[MOS_TILES],
+                  top[MOS_TILES],          // canvas row of the content's first row
+                  xa[MOS_TILES],           // content column xi of canvas column x: x - xa, under a flip xa - x
+                  mode[MOS_TILES],         // bit 0 = flip, bit 1 = the colour stage runs
+                  wy0[MOS_TILES], wx0[MOS_TILES], wy1[MOS_TILES], wx1[MOS_TILES];
+                  float dh[MOS_TILES], sat[MOS_TILES], ex[MOS_TILES];
+                  unsigned char first[MOS_TILES + 1]; };    // canvas z of the launch owns the tiles [first[z], first[z + 1])
+
+__global__ __launch_bounds__(256) void letterbox_mosaic_kernel(const unsigned char* __restrict__ packed, MosTable t, int S,
+                                                               float* __restrict__ dst) {
+    __shared__ int col_s[LBA_TW], row_s[LBA_TH];                                  // floor of the source coordinate, or LBA_OUT
+    __shared__ __attribute__((aligned(16))) float col_w[LBA_TW][4], row_w[LBA_TH][4];
+    __shared__ __attribute__((aligned(16))) float out_s[LBA_TH][LBA_TW * 3];
+    const int b = blockIdx.z, x0 = blockIdx.x * LBA_TW, y0 = blockIdx.y * LBA_TH, tid = threadIdx.x;
+    constexpr int ROW_Q = LBA_TW * 3 / 4;
+#pragma unroll
+    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) reinterpret_cast<float4*>(&out_s[0][0])[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int lx = tid & (LBA_TW - 1), ly = tid >> 6;
+    const int k1 = t.first[b + 1];
+    for (int k = t.first[b]; k < k1; ++k) {
+        const int wy0 = t.wy0[k], wx0 = t.wx0[k], wy1 = t.wy1[k], wx1 = t.wx1[k];
+        if (wx1 <= x0 || wx0 >= x0 + LBA_TW || wy1 <= y0 || wy0 >= y0 + LBA_TH) continue;    // the same in every lane of the workgroup
+        const int h = t.h[k], w = t.w[k], w_p = t.w_p[k], h_p = t.h_p[k], pitch = t.pitch[k], mode = t.mode[k];
+        __syncthreads();                                                          // the tables of the tile before are read; the stage is zeroed
+        if (tid < LBA_TW) {
+            const int x = x0 + tid;
+            const int xi = (mode & 1) ? t.xa[k] - x : x - t.xa[k];                // undo the window's placement and the in-box flip
+            int s = LBA_OUT;
+            float wx[4] = {0.f, 0.f, 0.f, 0.f};
+            if (x >= wx0 && x < wx1 && xi >= 0 && xi < w_p) {
+                const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
+                s = (int)floor(fx);
+                cubic_w((float)(fx - s), wx);
+            }
+            col_s[tid] = s;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col_w[tid][i] = wx[i];
+        } else if (tid < LBA_TW + LBA_TH) {
+            const int j = tid - LBA_TW, y = y0 + j;
+            const int yi = y - t.top[k];
+            int s = LBA_OUT;
+            float wy[4] = {0.f, 0.f, 0.f, 0.f};
+            if (y >= wy0 && y < wy1 && yi >= 0 && yi < h_p) {
+                const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
+                s = (int)floor(fy);
+                cubic_w((float)(fy - s), wy);
+            }
+            row_s[j] = s;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) row_w[j][i] = wy[i];
+        }
+        __syncthreads();
+        const unsigned char* __restrict__ src = packed + t.off[k];
+        const int sx = col_s[lx];
+        const float4 wxv = *reinterpret_cast<const float4*>(col_w[lx]);
+        const float wx[4] = {wxv.x, wxv.y, wxv.z, wxv.w};
+        int xo[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xo[i] = sx == LBA_OUT ? 0 : min(max(sx - 1 + i, 0), w - 1) * 3;
+        const bool inner = sx != LBA_OUT && sx >= 1 && sx + 2 <= w - 1;           // the four taps are 12 contiguous bytes of a source row
+        const float dh = t.dh[k], sat = t.sat[k], ex = t.ex[k];
+#pragma unroll
+        for (int pass = 0; pass < LBA_TH / LBA_ROWS; ++pass) {
+            const int j0 = pass * LBA_ROWS + ly;
+            const int sy = row_s[j0];
+            if (sx != LBA_OUT && sy != LBA_OUT) {
+                float r = 0.f, g = 0.f, bl = 0.f;
+                const float4 wyv = *reinterpret_cast<const float4*>(row_w[j0]);
+                const float wy[4] = {wyv.x, wyv.y, wyv.z, wyv.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int yy = min(max(sy - 1 + j, 0), h - 1);
+                    const unsigned char* __restrict__ row = src + (size_t)yy * pitch;
+                    float rr = 0.f, gg = 0.f, bb = 0.f;
+                    if (inner) {
+                        unsigned v[3];
+                        __builtin_memcpy(v, row + xo[0], 12);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float p0 = (float)((v[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u);
+                            const float p1 = (float)((v[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u);
+                            const float p2 = (float)((v[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u);
+                            rr += wx[i] * p0; gg += wx[i] * p1; bb += wx[i] * p2;
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const unsigned char* p = row + xo[i];
+                            rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
+                        }
+                    }
+                    r += wy[j] * rr; g += wy[j] * gg; bl += wy[j] * bb;
+                }
+                r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); bl *= (1.0f / 255.0f);
+                if (mode & 2) lba_colour(r, g, bl, dh, sat, ex);
+                out_s[j0][3 * lx] = r; out_s[j0][3 * lx + 1] = g; out_s[j0][3 * lx + 2] = bl;   // a thread's own pixel in every tile
+            }
+        }
+    }
+    __syncthreads();
+    const int row_q = 3 * min(LBA_TW, S - x0) / 4;                                 // chunks of this tile's row segment (S % 4 == 0)
+#pragma unroll
+    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) {
+        const int rr = q / ROW_Q, kq = q - rr * ROW_Q;
+        const int y = y0 + rr;
+        if (y < S && kq < row_q)
+            reinterpret_cast<float4*>(dst + (((size_t)b * S + y) * S + x0) * 3)[kq] = reinterpret_cast<const float4*>(out_s[rr])[kq];
+    }
+}
+
 bool lb_geometry(int h, int w, int S, int* g) {
     int w_p, h_p, pad_t = 0, pad_b = 0, pad_l = 0, pad_r = 0;
     if (w >= h) {   // face_detection.py:120-133
@@ -456,6 +577,86 @@ extern "C" int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, co
         hipLaunchKernelGGL(letterbox_augment_kernel, dim3((S + LBA_TW - 1) / LBA_TW, (S + LBA_TH - 1) / LBA_TH, nb), dim3(256), 0,
                            ctx->stream, packed, t, S, dst + (size_t)b0 * S * S * 3);
         FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+extern "C" int fv_letterbox_mosaic_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                                         int image_size, int n_out, const int32_t* tiles, const float* colour, int n_tiles, float* dst) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, packed && offsets && hw && tiles && dst && n_img >= 1 && n_out >= 1 && n_tiles >= n_out && n_tiles <= MOS_PER * (long long)n_out &&
+                        image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
+               "letterbox_mosaic_batch: bad arguments (1 to 4 tiles per canvas, image_size a multiple of 4 and dst 16-byte aligned: rows are "
+               "stored 16 bytes at a time)");
+    const int S = image_size;
+    // every record before anything is enqueued: a bad one leaves dst untouched
+    int canvas = 0, first = 0;                                       // the canvas being read and its first tile
+    for (int k = 0; k < n_tiles; ++k) {
+        const int* r = tiles + 14 * k;
+        const int cv = r[0], im = r[1], cy0 = r[2], cx0 = r[3], ch = r[4], cw = r[5], T = r[6], oy = r[7], ox = r[8], flip = r[9];
+        const int wy0 = r[10], wx0 = r[11], wy1 = r[12], wx1 = r[13];
+        FV_REQUIRE(ctx, cv >= 0 && cv < n_out && (cv == canvas || (cv == canvas + 1 && k > first)),
+                   "letterbox_mosaic_batch: tile %d names canvas %d after canvas %d (of %d): the tiles are sorted by canvas and every canvas "
+                   "has at least one", k, cv, canvas, n_out);
+        if (cv != canvas) { canvas = cv; first = k; }
+        FV_REQUIRE(ctx, k - first < MOS_PER, "letterbox_mosaic_batch: canvas %d has more than %d tiles", cv, MOS_PER);
+        FV_REQUIRE(ctx, im >= 0 && im < n_img, "letterbox_mosaic_batch: tile %d names image %d of %d", k, im, n_img);
+        const int H = hw[2 * im], W = hw[2 * im + 1];
+        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "letterbox_mosaic_batch: bad image %d", im);
+        FV_REQUIRE(ctx, ch >= 1 && cw >= 1 && cy0 >= 0 && cx0 >= 0 && cy0 <= H - ch && cx0 <= W - cw,
+                   "letterbox_mosaic_batch: tile %d: crop (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", k, cy0, cx0, ch, cw, im, H, W);
+        FV_REQUIRE(ctx, T >= 1 && T <= 4LL * S && oy >= -T && ox >= -T && oy <= S && ox <= S,
+                   "letterbox_mosaic_batch: tile %d: box of side %d at (y %d, x %d): 1 <= side <= 4 x %d and -side <= y, x <= %d", k, T, oy, ox, S, S);
+        int g[6];
+        FV_REQUIRE(ctx, lb_geometry(ch, cw, T, g), "letterbox_mosaic_batch: tile %d: crop %d x %d too elongated for a box of side %d", k, ch, cw, T);
+        FV_REQUIRE(ctx, flip == 0 || flip == 1, "letterbox_mosaic_batch: tile %d: flip %d is neither 0 nor 1", k, flip);
+        FV_REQUIRE(ctx, wy0 >= 0 && wx0 >= 0 && wy0 < wy1 && wx0 < wx1 && wy1 <= S && wx1 <= S,
+                   "letterbox_mosaic_batch: tile %d: window rows [%d, %d) columns [%d, %d) is empty or outside the %d x %d canvas", k, wy0, wy1,
+                   wx0, wx1, S, S);
+        for (int j = first; j < k; ++j) {
+            const int* q = tiles + 14 * j;
+            FV_REQUIRE(ctx, wy1 <= q[10] || q[12] <= wy0 || wx1 <= q[11] || q[13] <= wx0,
+                       "letterbox_mosaic_batch: the windows of tiles %d and %d of canvas %d overlap", j, k, cv);
+        }
+        if (colour)
+            FV_REQUIRE(ctx, std::isfinite(colour[3 * k]) && std::isfinite(colour[3 * k + 1]) && std::isfinite(colour[3 * k + 2]),
+                       "letterbox_mosaic_batch: tile %d: colour parameters are not finite", k);
+    }
+    FV_REQUIRE(ctx, canvas == n_out - 1, "letterbox_mosaic_batch: canvas %d of %d has no tile", canvas + 1, n_out);
+    // whole canvases per launch, as many as MOS_TILES tiles hold
+    for (int k0 = 0, c0 = 0; k0 < n_tiles;) {
+        MosTable t{};
+        double bytes = 0.0;
+        int nt = 0, nc = 0;
+        while (k0 + nt < n_tiles) {
+            int m = 1;
+            while (k0 + nt + m < n_tiles && tiles[14 * (k0 + nt + m)] == tiles[14 * (k0 + nt)]) ++m;    // the tiles of the next canvas
+            if (nt + m > MOS_TILES) break;
+            t.first[nc] = (unsigned char)nt;
+            for (int i = nt; i < nt + m; ++i) {
+                const int* r = tiles + 14 * (k0 + i);
+                const float* c = colour ? colour + 3 * (k0 + i) : nullptr;
+                const int W = hw[2 * r[1] + 1];
+                int g[6];
+                lb_geometry(r[4], r[5], r[6], g);
+                t.off[i] = offsets[r[1]] + ((long long)r[2] * W + r[3]) * 3; t.pitch[i] = W * 3;
+                t.h[i] = r[4]; t.w[i] = r[5]; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.top[i] = r[7] + g[2];
+                t.xa[i] = r[9] ? r[8] + r[6] - 1 - g[4] : r[8] + g[4];
+                const bool col = c && !(c[0] == 0.f && c[1] == 1.f && c[2] == 1.f);       // exactly (0, 1, 1): the stage is skipped
+                t.mode[i] = r[9] | (col ? 2 : 0);
+                t.wy0[i] = r[10]; t.wx0[i] = r[11]; t.wy1[i] = r[12]; t.wx1[i] = r[13];
+                t.dh[i] = col ? c[0] : 0.f; t.sat[i] = col ? c[1] : 1.f; t.ex[i] = col ? c[2] : 1.f;
+                bytes += (double)r[4] * r[5] * 3;
+            }
+            nt += m; ++nc;
+            t.first[nc] = (unsigned char)nt;
+        }
+        bytes += 12.0 * S * S * nc;
+        FvProfScope ps(ctx, "letterbox_mosaic_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_mosaic_kernel, dim3((S + LBA_TW - 1) / LBA_TW, (S + LBA_TH - 1) / LBA_TH, nc), dim3(256), 0,
+                           ctx->stream, packed, t, S, dst + (size_t)c0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+        k0 += nt; c0 += nc;
     }
     return FV_OK;
 }

@@ -67,16 +67,50 @@ def _placed_centres(faces, h, w, image_size, placement):
         yield x1, y1, x2, y2, xc, yc, m, T
 
 
-def encode_gt(faces, h, w, image_size=416, grid=13, channels=6, placement=None):
+def _tile_centres(tiles, image_size):
+    """_placed_centres for a canvas made of tiles (hps['mosaic'], draw_mosaic).  tiles: [(faces of the tile's source image, the
+    tile's record (canvas, image, cy0, cx0, ch, cw, T, oy, ox, flip, wy0, wx0, wy1, wx1))], in the table's order; the faces of
+    tile 0 come first, then tile 1's, ...  Per tile _placed_centres' expressions with the tile's numbers,
+        x1p = int((x1 - cx0) / m * T) + ox + pad_l,  ...,  xc = (x1p + x2p) // 2,  yc = (y1p + y2p) // 2,
+    ox and oy possibly negative; a tile's flip mirrors its box in place, xc = 2 * ox + T - 1 - xc.  A face is kept only when its
+    centre, after the flip, lies inside both the tile's placed content rectangle and its window rows [wy0, wy1) x columns
+    [wx0, wx1); its box is NOT clipped, neither to the crop nor to the window.  One tile whose window is the whole canvas yields
+    what the equivalent placement yields (the canvas flip of a placement with box column ox is the in-box flip with S - T - ox)."""
+    for faces, rec in tiles:
+        _canvas, _image, cy0, cx0, ch, cw, T, oy, ox, flip, wy0, wx0, wy1, wx1 = (int(v) for v in rec)
+        w_p, h_p, pad_t, _, pad_l, _ = letterbox_geometry(ch, cw, T)
+        m = cw if cw >= ch else ch
+        left, top = ox + pad_l, oy + pad_t
+        for fx, fy, fw, fh in np.asarray(faces, dtype=np.float64).reshape(-1, 4):
+            if not (fx > 0 and fy > 0 and fw > 0 and fh > 0):
+                continue
+            x1, y1 = int(fx), int(fy)
+            x2, y2 = x1 + int(fw) - 1, y1 + int(fh) - 1
+            x1p, x2p = int((x1 - cx0) / m * T) + left, int((x2 - cx0) / m * T) + left
+            y1p, y2p = int((y1 - cy0) / m * T) + top, int((y2 - cy0) / m * T) + top
+            xc, yc = (x1p + x2p) // 2, (y1p + y2p) // 2
+            if not (left <= xc < left + w_p and top <= yc < top + h_p):
+                continue
+            if flip:
+                xc = 2 * ox + T - 1 - xc
+            if not (wx0 <= xc < wx1 and wy0 <= yc < wy1):
+                continue
+            yield x1, y1, x2, y2, xc, yc, m, T
+
+
+def encode_gt(faces, h, w, image_size=416, grid=13, channels=6, placement=None, tiles=None):
     """Ground-truth tensor of one image (face_detection.py:150-202).
 
     faces: array-like (n,4) of FACE_X, FACE_Y, FACE_WIDTH, FACE_HEIGHT in csv order; rows with
     any value <= 0 are skipped; later rows overwrite earlier ones in the same cell.
     placement: None (the reference's letterbox) or (cy0, cx0, ch, cw, T, oy, ox, flip) as draw_augment returns it
-    (_placed_centres states the arithmetic); the box sizes are then fractions of the canvas, (x2 - x1 + 1) / m * (T / S)."""
+    (_placed_centres states the arithmetic); the box sizes are then fractions of the canvas, (x2 - x1 + 1) / m * (T / S).
+    tiles: a mosaic canvas, [(faces, tile record)] as _tile_centres takes it (faces, h, w and placement are then not read):
+    the tiles are written in their order, sizes with each tile's own m and T."""
     cell = image_size // grid
     gt = np.zeros((grid, grid, channels), np.float64)
-    for x1, y1, x2, y2, xc, yc, m, T in _placed_centres(faces, h, w, image_size, placement):
+    centres = _tile_centres(tiles, image_size) if tiles is not None else _placed_centres(faces, h, w, image_size, placement)
+    for x1, y1, x2, y2, xc, yc, m, T in centres:
         cx, cy = xc // cell, yc // cell
         k = T / image_size
         gt[cy, cx, :6] = [1.0, (xc - cx * cell) / cell, (yc - cy * cell) / cell,
@@ -92,7 +126,7 @@ YOLO_ANCHORS_DECODED = ((0, 1), (1, 0), (1, 2), (2, 1))
 
 
 def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_ANCHORS, anchor_keep=YOLO_ANCHORS_DECODED,
-                          placement=None):
+                          placement=None, tiles=None):
     """Ground truth of one image for the three-scale head: [t13, t26, t52], t_s of shape (g_s, g_s, 3*(5+nclass)) float64 with
     g_s = image_size/32 * 2^s, laid out [cell][anchor][tx, ty, tw, th, objectness, classes...] like the network output.
 
@@ -104,11 +138,13 @@ def encode_gt_three_scale(faces, h, w, image_size=416, nclass=1, anchors=YOLO_AN
     decode_netout (yolov3_detect.py:335-387) inverts: sigma(tx) = offset, anchor_w * exp(tw) = box width in network pixels.
     Offsets are clamped to [0.5/cell, 1 - 0.5/cell] (logit of 0 is -inf; half a pixel is below the decode's int() grain).
     Objectness 1 and class 0 = 1 at the assigned slot; later rows overwrite earlier ones in the same slot.
-    placement: as for encode_gt; the box in network pixels is then (x2 - x1 + 1) / m * T."""
+    placement: as for encode_gt; the box in network pixels is then (x2 - x1 + 1) / m * T.
+    tiles: as for encode_gt (a mosaic canvas; every tile's faces with that tile's m and T)."""
     S = int(image_size)
     C = 5 + nclass
     out = [np.zeros((S // 32 << s, S // 32 << s, 3 * C), np.float64) for s in range(3)]
-    for x1, y1, x2, y2, xc, yc, m, T in _placed_centres(faces, h, w, S, placement):
+    centres = _tile_centres(tiles, S) if tiles is not None else _placed_centres(faces, h, w, S, placement)
+    for x1, y1, x2, y2, xc, yc, m, T in centres:
         bw, bh = (x2 - x1 + 1) / m * T, (y2 - y1 + 1) / m * T          # the single-scale targets bw, bh times the network size
         best, best_iou = None, -1.0
         for (s, b) in anchor_keep:
@@ -283,6 +319,125 @@ def draw_augment(aug_conf, epoch, file_index, h, w, S):
     return placement, (dh + 0.0, scale[0], scale[1])
 
 
+# ----------------------------------------------------------------------------- mosaic (hps['mosaic'])
+MOSAIC_DEFAULTS = {'prob': 0.5, 'scale': [0.4, 1.0], 'centre': [0.25, 0.75], 'seed': 0}
+
+
+def mosaic_conf(value):
+    """fd_conf.hps['mosaic'] -> None (absent, None or false: every canvas holds one image, as without the key) or the complete
+    parameter dict (true: MOSAIC_DEFAULTS; an object: its keys over the defaults).  ValueError for another type, an unknown key
+    or a value outside its range: prob in [0, 1] (the share of canvases that are mosaics), scale [lo, hi] with
+    0 < lo <= hi <= 2 (a tile's box side as a fraction of the network size), centre [lo, hi] with 0 < lo <= hi < 1 (the mosaic
+    centre as a fraction of the network size, per axis), seed an int >= 0.  Not in the reference; pure host code."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError('fd_conf.hps.mosaic %r is not valid (false, true or an object with the keys %s)'
+                         % (value, ', '.join(sorted(MOSAIC_DEFAULTS))))
+    unknown = sorted(set(value) - set(MOSAIC_DEFAULTS))
+    if unknown:
+        raise ValueError('fd_conf.hps.mosaic has unknown key(s) %s (available: %s)' % (', '.join(map(repr, unknown)),
+                                                                                    ', '.join(sorted(MOSAIC_DEFAULTS))))
+    c = dict(MOSAIC_DEFAULTS)
+    c.update(value)
+    if not (_is_number(c['prob']) and 0 <= c['prob'] <= 1):
+        raise ValueError('fd_conf.hps.mosaic.prob %r is not valid (a share in [0, 1])' % (c['prob'],))
+    for k, ok, rule in (('scale', lambda lo, hi: 0 < lo <= hi <= 2, '0 < lo <= hi <= 2'),
+                        ('centre', lambda lo, hi: 0 < lo <= hi < 1, '0 < lo <= hi < 1')):
+        v = c[k]
+        if not (isinstance(v, (list, tuple)) and len(v) == 2 and all(_is_number(x) for x in v) and ok(v[0], v[1])):
+            raise ValueError('fd_conf.hps.mosaic.%s %r is not valid ([lo, hi] with %s)' % (k, v, rule))
+        c[k] = [float(v[0]), float(v[1])]
+    if not (isinstance(c['seed'], int) and not isinstance(c['seed'], bool) and c['seed'] >= 0):
+        raise ValueError('fd_conf.hps.mosaic.seed %r is not valid (an int >= 0)' % (c['seed'],))
+    c['prob'] = float(c['prob'])
+    return c
+
+
+def draw_mosaic(mos_conf, aug_conf, epoch, file_indices, shapes, S):
+    """The canvases of one rank's slice of a batch in epoch `epoch` at network size S -> (tiles, colour): what
+    fv_letterbox_mosaic_batch and the encoders' `tiles=` take.  file_indices[i] / shapes[i]: the index in
+    TrainingSequence.file_names and the (h, w) of the slice's image i, in order; canvas i is built around image i.  tiles: int32
+    [n_tiles][14] records (canvas, image, cy0, cx0, ch, cw, T, oy, ox, flip, wy0, wx0, wy1, wx1), `image` a position in the
+    slice, sorted by canvas; colour: float32 [n_tiles][3] records (dh, sat, exp), or None when aug_conf is None.  Pure host
+    code.  mos_conf: mosaic_conf()'s dict; aug_conf: augment_conf()'s dict or None.
+
+    Canvas i draws from rng = np.random.default_rng([seed, epoch, file_indices[i], 1]) (the trailing 1 keeps the stream apart
+    from draw_augment's) in this fixed order (round = Python's round):
+      1. mosaic = rng.random() < prob
+      2. a mosaic: px = rng.integers(round(lo * S), round(hi * S) + 1), then py likewise, (lo, hi) = centre, each then clamped
+         to [1, S - 1] (no window is empty)
+      3. a mosaic: three partner positions rng.integers(0, n) in the slice of n images, for tiles 1, 2, 3; repeats and i itself
+         are allowed; tile 0 is image i
+      4. a mosaic: four u = rng.uniform(lo, hi), (lo, hi) = scale: tile q's box side is T = max(1, round(S * u))
+    Tile q = 0, 1, 2, 3 is the top-left, top-right, bottom-left, bottom-right quadrant around the centre (py, px): its window is
+    rows [0, py) or [py, S) x columns [0, px) or [px, S); the four windows partition the canvas.  The tile's WHOLE image is
+    letterboxed by letterbox_geometry(h, w, T) into a T x T box, and the box is placed so that the corner of its CONTENT
+    rectangle that faces the centre lies at (py, px): for q = 0, ox = px - (pad_l + w_p) and oy = py - (pad_t + h_p); for q = 1,
+    ox = px - pad_l; for q = 2 and 3, oy = py - pad_t.  ox and oy may be negative and the box may reach beyond the canvas: the
+    window cuts.  Where that geometry is not feasible (w_p < 1 or h_p < 1) the tile falls back to T = S, as draw_augment falls
+    back to the identity.
+    With aug_conf, tile q takes the flip and the colour record of ITS source image from
+    draw_augment(aug_conf, epoch, that image's file index, ...); the zoom of that draw is not used for a tile.  A tile's flip
+    mirrors the T x T box in place (local column c -> T - 1 - c, padding included) and the content corner is aligned AFTER the
+    flip (pad_l above is then the mirrored box's, T - pad_l - w_p).  Without aug_conf a tile has no flip and no colour.
+    A canvas that is not a mosaic is ONE tile whose window is the whole canvas, with the parameters it has without mosaic:
+    draw_augment's placement and colour -- a canvas flip restated as the in-box flip, ox' = S - T - ox -- or, without
+    aug_conf, identity_placement.
+
+    The partners are positions in the slice, so the result is determined by (seed, epoch, the slice's composition): the batch
+    size, the world size and the rank all enter.  Unlike draw_augment, two ranks do NOT see the one-GPU run's dataset."""
+    S, epoch, n = int(S), int(epoch), len(shapes)
+    lo_c, hi_c = mos_conf['centre']
+    lo_s, hi_s = mos_conf['scale']
+    aug = {}
+
+    def augmented(i):                      # draw_augment of the slice's image i, once
+        if i not in aug:
+            aug[i] = draw_augment(aug_conf, epoch, file_indices[i], shapes[i][0], shapes[i][1], S)
+        return aug[i]
+
+    tiles, colour = [], []
+    for i in range(n):
+        rng = np.random.default_rng([int(mos_conf['seed']), epoch, int(file_indices[i]), 1])
+        if not rng.random() < mos_conf['prob']:
+            h, w = int(shapes[i][0]), int(shapes[i][1])
+            if aug_conf is None:
+                pl = identity_placement(h, w, S)
+            else:
+                pl, col = augmented(i)
+                colour.append(col)
+            cy0, cx0, ch, cw, T, oy, ox, flip = pl
+            tiles.append((i, i, cy0, cx0, ch, cw, T, oy, S - T - ox if flip else ox, flip, 0, 0, S, S))
+            continue
+        px = min(max(int(rng.integers(round(lo_c * S), round(hi_c * S) + 1)), 1), S - 1)
+        py = min(max(int(rng.integers(round(lo_c * S), round(hi_c * S) + 1)), 1), S - 1)
+        members = [i] + [int(rng.integers(0, n)) for _ in range(3)]
+        sides = [max(1, round(S * float(rng.uniform(lo_s, hi_s)))) for _ in range(4)]
+        for q, (j, T) in enumerate(zip(members, sides)):
+            h, w = int(shapes[j][0]), int(shapes[j][1])
+            flip = 0
+            if aug_conf is not None:
+                pl, col = augmented(j)
+                flip = pl[7]
+                colour.append(col)
+            w_p, h_p, pad_t, _, pad_l, _ = letterbox_geometry(h, w, T)
+            if w_p < 1 or h_p < 1:
+                T = S
+                w_p, h_p, pad_t, _, pad_l, _ = letterbox_geometry(h, w, T)
+            if flip:
+                pad_l = T - pad_l - w_p
+            ox = px - pad_l if q & 1 else px - (pad_l + w_p)
+            oy = py - pad_t if q & 2 else py - (pad_t + h_p)
+            wy0, wy1 = (py, S) if q & 2 else (0, py)
+            wx0, wx1 = (px, S) if q & 1 else (0, px)
+            tiles.append((i, j, 0, 0, h, w, T, oy, ox, flip, wy0, wx0, wy1, wx1))
+    tiles = np.asarray(tiles, np.int32).reshape(-1, 14)
+    return tiles, (None if aug_conf is None else np.asarray(colour, np.float32).reshape(-1, 3))
+
+
 # ----------------------------------------------------------------------------- bicubic letterbox
 def _cubic_weights(t, a=-0.75):
     t = np.asarray(t, np.float64)
@@ -342,12 +497,13 @@ class TrainingSequence(object):
         self.three_scale = nn_arch.get('head', 'single') == 'three_scale'
         self.nclass = int(nn_arch.get('num_classes', 1))
 
-    def encode(self, rows, h, w, placement=None):
+    def encode(self, rows, h, w, placement=None, tiles=None):
         """GT of one image: (G,G,6) for the reference's single-scale head, [t13, t26, t52] for the three-scale head; placement:
-        an augmented sample's placement (draw_augment), None = the reference's letterbox."""
+        an augmented sample's placement (draw_augment), None = the reference's letterbox; tiles: a mosaic canvas as
+        [(rows of the tile's image, tile record)] (draw_mosaic; rows, h, w are then not read)."""
         if self.three_scale:
-            return encode_gt_three_scale(rows, h, w, self.image_size, self.nclass, placement=placement)
-        return encode_gt(rows, h, w, self.image_size, self.grid, self.nn_arch['bb_info_c_size'], placement=placement)
+            return encode_gt_three_scale(rows, h, w, self.image_size, self.nclass, placement=placement, tiles=tiles)
+        return encode_gt(rows, h, w, self.image_size, self.grid, self.nn_arch['bb_info_c_size'], placement=placement, tiles=tiles)
 
     def __len__(self):
         return self.hps['step']

@@ -26,6 +26,9 @@ ratios.csv, the model files).  Differences, all documented in DESIGN.md:
   * hps['augment'] (not in the reference, off unless asked for; data.augment_conf) gives every training sample a random zoom and
     translation, a horizontal flip and a hue / saturation / exposure distortion per epoch (Darknet's detector recipe), inside the
     batch's one letterbox launch (fv_letterbox_augment_batch); train() only
+  * hps['mosaic'] (not in the reference, off unless asked for; data.mosaic_conf) makes a share of the training canvases out of four
+    images of the batch around a random centre, each with its own size, flip and colour, in the same one launch
+    (fv_letterbox_mosaic_batch); train() only
   * hps['loss'] = 'yolo' (not in the reference, off unless asked for; data.det_loss_conf) trains the three-scale head with YOLOv3's
     detection loss -- ignore mask, box terms on assigned slots only, GIoU or keras-yolo3's box term (fv_yolov3_train_step_det) --
     and prints its statistics once per epoch; train() only
@@ -112,6 +115,7 @@ class FaceDetector(object):
         self.model_loading = conf['model_loading']
         self.image_size = int(self.nn_arch['image_size'])
         self.augment = data.augment_conf(self.hps.get('augment'))      # ValueError before a device is touched
+        self.mosaic = data.mosaic_conf(self.hps.get('mosaic'))         # likewise
         self.det_loss = data.det_loss_conf(self.hps.get('loss'), self.nn_arch.get('head', 'single'))    # likewise
         if self.image_size % 32:
             raise ValueError('image_size must be a multiple of 32 (network stride)')
@@ -520,11 +524,18 @@ class BatchFeeder(object):
     seq.hps['augment'] (data.augment_conf): every image's placement and colour parameters are drawn here (data.draw_augment, from
     the seed, the epoch of set_epoch() and the image's index in seq.file_names), its GT is encoded under that placement, and the two
     small tables travel with the packed images as ('augment', packed, (place, colour)) for the same one launch
-    (fv_letterbox_augment_batch)."""
+    (fv_letterbox_augment_batch).
+
+    seq.hps['mosaic'] (data.mosaic_conf): the canvases of this rank's slice are drawn here, once per load (data.draw_mosaic: up to
+    four of the slice's images per canvas, each tile with its source image's flip and colour when 'augment' is on too), each
+    canvas's GT is encoded from its tiles, and the tables travel as ('mosaic', packed, (tiles, colour, n_out)) for the same one
+    launch (fv_letterbox_mosaic_batch).  The partners are positions in the slice: the result depends on the batch composition, the
+    world size and the rank."""
 
     def __init__(self, seq, world, rank, threads=8):
         self.seq, self.world, self.rank = seq, world, rank
         self.augment = data.augment_conf(seq.hps.get('augment'))
+        self.mosaic = data.mosaic_conf(seq.hps.get('mosaic'))
         self.epoch = 0
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.one = ThreadPoolExecutor(max_workers=1)
@@ -613,7 +624,13 @@ class BatchFeeder(object):
             raws = list(self.pool.map(lambda nm: seq.loader(os.path.join(seq.raw_data_path, nm)), mine))
             packed = pack_images(raws, pin=pin)
             shapes = [(r.shape[0], r.shape[1]) for r in raws]
-        if self.augment is not None:
+        if self.mosaic is not None:
+            first = index * seq.batch_size + lo                       # mine[i] is seq.file_names[first + i]
+            tiles, colour = data.draw_mosaic(self.mosaic, self.augment, self.epoch, range(first, first + len(mine)), shapes, seq.image_size)
+            rows = [seq.groups[nm].iloc[:, 3:7].values for nm in mine]
+            enc = [seq.encode(None, 0, 0, tiles=[(rows[t[1]], t) for t in tiles if t[0] == i]) for i in range(len(mine))]
+            packed = ('mosaic', packed, (tiles, colour, len(mine)))
+        elif self.augment is not None:
             first = index * seq.batch_size + lo                       # mine[i] is seq.file_names[first + i]
             drawn = [data.draw_augment(self.augment, self.epoch, first + i, h, w, seq.image_size) for i, (h, w) in enumerate(shapes)]
             enc = [seq.encode(seq.groups[nm].iloc[:, 3:7].values, h, w, placement=d[0]) for nm, (h, w), d in zip(mine, shapes, drawn)]
@@ -645,12 +662,20 @@ def split_augment(packed):
     return packed, None
 
 
+def split_mosaic(packed):
+    """BatchFeeder.load's `packed` -> (what is left for split_augment, the mosaic tables (tiles, colour, n_out) or None)."""
+    if isinstance(packed[0], str) and packed[0] == 'mosaic':
+        return packed[1], packed[2]
+    return packed, None
+
+
 def train_on_item(engine, trainer, item, image_size, hp):
     """One optimisation step on what BatchFeeder.load returned, everything on the compute stream: H2D copy, device JPEG
     reconstruction / letterbox, fv_train_step (+ gradient all-reduce when world > 1), Adam.  run_pipelined() is the overlapped form."""
     packed, y, weight, (feeder, slot) = item
+    packed, mos = split_mosaic(packed)
     packed, aug = split_augment(packed)
-    x, _ = letterbox_batch_device(engine.ctx, None, image_size, engine.dev, packed=packed, aug=aug)
+    x, _ = letterbox_batch_device(engine.ctx, None, image_size, engine.dev, packed=packed, aug=aug, mosaic=mos)
     if slot is not None:
         feeder.copied(slot)
     yd = [t.to(engine.dev, non_blocking=True) for t in y] if isinstance(y, (tuple, list)) else y.to(engine.dev, non_blocking=True)
@@ -672,12 +697,13 @@ class DeviceStager(object):
         if item is None:
             return None
         packed, y, weight, (feeder, slot) = item
+        packed, mos = split_mosaic(packed)
         packed, aug = split_augment(packed)
         main = torch.cuda.current_stream(self.eng.dev)
         with torch.cuda.stream(self.stream):
             self.eng.ctx.set_stream(self.stream.cuda_stream)      # the library's launches of this block go to the staging stream
             try:
-                x, _ = letterbox_batch_device(self.eng.ctx, None, self.S, self.eng.dev, packed=packed, aug=aug)
+                x, _ = letterbox_batch_device(self.eng.ctx, None, self.S, self.eng.dev, packed=packed, aug=aug, mosaic=mos)
             finally:
                 self.eng.ctx.set_stream(main.cuda_stream)
             if slot is not None:

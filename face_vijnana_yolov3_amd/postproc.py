@@ -148,13 +148,16 @@ def pack_images(raws, pin=True, ring=None):
     return buf, offs, hw
 
 
-def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None, keep=None, aug=None):
+def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None, keep=None, aug=None, mosaic=None):
     """list of uint8 HxWx3 arrays -> ((n,S,S,3) float32 CUDA tensor, [geometry tuples]) in ONE launch
     (fv_letterbox_batch); `packed` = the result of pack_images when a loader thread prepared it.  keep: a list that receives
     (device uint8 buffer, offsets, hw) -- the batch's decoded images on the device, for a later fv_letterbox_crops.
     aug: (place, colour) -- n x 8 int placements and n x 3 float colour parameters (or None) as data.draw_augment draws them: the
     launch is then fv_letterbox_augment_batch (crop, placement, flip and colour distortion in the same single pass) and the second
-    result is None (the placements ARE the geometry)."""
+    result is None (the placements ARE the geometry).
+    mosaic: (tiles, colour, n_out) -- n_tiles x 14 int tile records, n_tiles x 3 float colour parameters (or None) and the number
+    of canvases, as data.draw_mosaic draws them: the launch is then fv_letterbox_mosaic_batch, the result holds n_out canvases made
+    of the n images, and the second result is None.  Not together with aug (draw_mosaic carries the augmentation per tile)."""
     import ctypes
     import torch
     if packed is not None and isinstance(packed[0], str) and packed[0] == 'jpeg':
@@ -169,6 +172,28 @@ def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None,
         dbuf = buf.to(device, non_blocking=True)
     n = len(offs)
     S = int(image_size)
+    if mosaic is not None:
+        if aug is not None:
+            raise ValueError('letterbox_batch_device: aug and mosaic are given together (the mosaic tables carry the augmentation)')
+        tiles, colour, n_out = mosaic
+        tiles = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1))
+        n_tiles, n_out = tiles.size // 14, int(n_out)
+        if tiles.size != 14 * n_tiles or n_tiles < 1:
+            raise ValueError('letterbox_batch_device: %d tile values (14 each, at least one tile)' % tiles.size)
+        cp = None
+        if colour is not None:
+            colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(-1))
+            if colour.size != 3 * n_tiles:
+                raise ValueError('letterbox_batch_device: %d colour values for %d tiles (3 each)' % (colour.size, n_tiles))
+            cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        if out is None:
+            out = torch.empty((n_out, S, S, 3), dtype=torch.float32, device=device)
+        rc = lib().fv_letterbox_mosaic_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, n_out,
+                                             tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, n_tiles, ptr(out))
+        ctx.check(rc, 'fv_letterbox_mosaic_batch')
+        if keep is not None:
+            keep.append((dbuf, list(offs), list(hw)))
+        return out, None
     if out is None:
         out = torch.empty((n, S, S, 3), dtype=torch.float32, device=device)
     if aug is not None:

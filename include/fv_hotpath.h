@@ -396,6 +396,24 @@ int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offset
  * letterboxed side of at least 1, flip 0 or 1, finite colour values -- and a bad one is FV_ERR_INVALID with dst untouched. */
 int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int image_size,
                                const int32_t* place, const float* colour, float* dst);
+/* Mosaic: canvases made of up to four tiles, for FaceDetector.train with hps['mosaic'] (not in the reference; data.draw_mosaic
+ * draws the tables).  packed / offsets / hw: the n_img images as for fv_letterbox_batch.  tiles: HOST int32 [n_tiles][14] records
+ * (canvas, image, cy0, cx0, ch, cw, T, oy, ox, flip, wy0, wx0, wy1, wx1), sorted by canvas, 1 to 4 for every canvas 0 .. n_out - 1:
+ * the ch x cw crop at (cy0, cx0) of `image` is letterboxed as fv_letterbox_crops letterboxes it at image_size T into a T x T box
+ * whose corner lies at row oy, column ox of the S x S canvas -- oy, ox may be negative and the box may reach beyond the canvas --
+ * flip = 1 mirrors the BOX in place, padding included (local column c -> T - 1 - c), and only the WINDOW rows [wy0, wy1) x columns
+ * [wx0, wx1) of the canvas shows the tile.  colour: HOST float [n_tiles][3] records (dh, sat, exp) per tile, or NULL.  An output
+ * pixel inside a tile's window and inside its placed content rectangle holds fv_letterbox_crops's bits for that crop at image
+ * size T at the (mirrored) local position, then fv_letterbox_augment_batch's colour stage when the tile's record is not exactly
+ * (0, 1, 1); every other pixel is +0.  One tile whose window is the whole canvas is fv_letterbox_augment_batch's sample (its flip
+ * restated for the box: ox' = S - T - ox).  dst: DEVICE float32 [n_out][S][S][3], 16-byte aligned; image_size a multiple of 4.
+ * One kernel, one pass, whole canvases of up to 48 tiles together per launch, on the context's stream; no atomics: the same call
+ * gives the same bits.  Every record is checked before anything is enqueued -- canvas in range and non-decreasing, 1 to 4 tiles
+ * for every canvas, image in range, crop inside its image, 1 <= T <= 4 S, -T <= oy, ox <= S, a letterboxed side of at least 1,
+ * flip 0 or 1, a non-empty window inside the canvas, the windows of one canvas pairwise disjoint, finite colour values -- and a
+ * bad one is FV_ERR_INVALID with dst untouched.  Additive: fv_abi_version() is unchanged. */
+int fv_letterbox_mosaic_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img, int image_size,
+                              int n_out, const int32_t* tiles, const float* colour, int n_tiles, float* dst);
 /* Crop + nearest-neighbour letterbox of many face rectangles on uint8, in one call (create_db_fi / save_extracted_face,
  * fi.py:113-161 and 233-274: the slice, cv.resize(INTER_NEAREST), cv.copyMakeBorder(value 0)).  Images and crop records as for
  * fv_letterbox_crops; dst: device uint8 [n][S][S][3], 16-byte aligned; image_size a multiple of 16, at most 4096.  Geometry as
