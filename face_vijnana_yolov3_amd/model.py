@@ -81,7 +81,9 @@ class Model(object):
 
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, batch, image_size, training):
-        """Device workspace of one call (self._workspace_bytes); one is kept per mode (inference / training)."""
+        """Device workspace of one call (self._workspace_bytes); one is kept per mode (inference / training).  It is allocated
+        uninitialised and reused call after call: the library ignores its contents on entry, and writes nothing outside
+        [workspace, workspace + bytes)."""
         key = (batch, image_size, bool(training))
         if key not in self._ws:
             n = int(self._workspace_bytes(batch, image_size, 1 if training else 0))

@@ -174,7 +174,9 @@ int fv_layer(int i, fv_layer_desc* out);
 int64_t fv_param_count(void);                  /* 40 640 230 trainable floats */
 int64_t fv_state_count(void);                  /* 35 712 BN moving mean/var floats */
 /* bytes of caller-provided device workspace for a batch; training != 0 keeps every layer's
- * pre-BN and activated output for the backward pass. */
+ * pre-BN and activated output for the backward pass.  The contents of the workspace on entry are ignored, and nothing outside
+ * [workspace, workspace + bytes) is written: this holds for every entry point that takes a workspace or a scratch buffer
+ * (tests/test_workspace_contract_gpu.py runs each of them on a poisoned workspace between guards). */
 size_t fv_workspace_bytes(int batch, int image_size, int training);
 
 /* ------------------------------------------------------------------ hot path: network level */
