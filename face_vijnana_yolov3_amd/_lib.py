@@ -89,6 +89,10 @@ def _declare(L):
         'fv_profile_enable': (i32, [vp, i32]),
         'fv_profile_collect': (i32, [vp, ctypes.POINTER(ProfileRec), i32, ctypes.POINTER(i32)]),
         'fv_bbox_iou_pairs': (i32, [vp, vp, vp, i64, vp]),
+        'fv_det_rows_from_nms': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        'fv_det_match_rows': (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+        'fv_det_ap_sweep_workspace_bytes': (sz, [i32]),
+        'fv_det_ap_sweep': (i32, [vp, vp, vp, vp, vp, i32, ctypes.POINTER(f64), i32, i64, vp, sz, vp, vp, vp, vp]),
         'fv_num_layers': (i32, []),
         'fv_layer': (i32, [i32, ctypes.POINTER(LayerDesc)]),
         'fv_param_count': (i64, []),

@@ -232,8 +232,72 @@ def check_det_dropped(dropped, max_count, max_boxes):
                          'raise max_boxes (at most 1024)' % (max_boxes, int(max_count), int(dropped)))
 
 
+# ----------------------------------------------------------------------------- per-epoch validation (hps['validate'])
+VALIDATE_DEFAULTS = {'path': None, 'every': 1, 'iou_ths': None, 'save_best': False}
+VALIDATE_MAX_THS = 16                  # FV_DET_MAX_TH of include/fv_hotpath.h
+
+
+def validate_conf(value, test_path=None):
+    """fd_conf.hps['validate'] -> None (absent, None or false: train() looks at no held-out image, as without the key) or the complete
+    parameter dict (true: VALIDATE_DEFAULTS; an object: its keys over the defaults) with 'path' resolved (default: `test_path`, the
+    configuration's test_path) and 'iou_ths' a list of floats (default: np.arange(0.5, 1.0, 0.05), cal_mAP_sweep's).  ValueError for
+    another type, an unknown key or a value outside its range: path a string, every an int >= 1, iou_ths 1 to 16 numbers in (0, 1]
+    in ascending order, save_best a bool.  Not in the reference; pure host code."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError('fd_conf.hps.validate %r is not valid (false, true or an object with the keys %s)'
+                         % (value, ', '.join(sorted(VALIDATE_DEFAULTS))))
+    unknown = sorted(set(value) - set(VALIDATE_DEFAULTS))
+    if unknown:
+        raise ValueError('fd_conf.hps.validate has unknown key(s) %s (available: %s)' % (', '.join(map(repr, unknown)),
+                                                                                      ', '.join(sorted(VALIDATE_DEFAULTS))))
+    c = dict(VALIDATE_DEFAULTS)
+    c.update(value)
+    if c['path'] is None:
+        c['path'] = test_path
+    if not (isinstance(c['path'], str) and c['path']):
+        raise ValueError('fd_conf.hps.validate.path %r is not valid (a directory with validation.csv and the *.jpg files; default: '
+                         'fd_conf.test_path)' % (c['path'],))
+    if not (isinstance(c['every'], int) and not isinstance(c['every'], bool) and c['every'] >= 1):
+        raise ValueError('fd_conf.hps.validate.every %r is not valid (an int >= 1)' % (c['every'],))
+    ths = c['iou_ths']
+    if ths is None:
+        ths = [float(t) for t in np.arange(0.5, 1.0, 0.05)]
+    if not (isinstance(ths, (list, tuple)) and 1 <= len(ths) <= VALIDATE_MAX_THS and all(_is_number(t) and 0 < t <= 1 for t in ths)
+            and all(a < b for a, b in zip(ths, ths[1:]))):
+        raise ValueError('fd_conf.hps.validate.iou_ths %r is not valid (1 to %d numbers in (0, 1], ascending)' % (ths, VALIDATE_MAX_THS))
+    c['iou_ths'] = [float(t) for t in ths]
+    if not isinstance(c['save_best'], bool):
+        raise ValueError('fd_conf.hps.validate.save_best %r is not valid (true or false)' % (c['save_best'],))
+    return c
+
+
+def refuse_validate_on_ranks(hps, ranks):
+    """Validation on more than one rank is not served: the ranking needs every rank's detections in one list, which needs a gather
+    and a run on two GPUs to prove."""
+    if int(ranks) > 1 and hps.get('validate') not in (None, False):
+        raise NotImplementedError('fd_conf.hps.validate with multi_gpu and %d ranks is not implemented: train on one GPU, or '
+                                  'without validate' % int(ranks))
+
+
+def validate_line(res):
+    """The line train() prints after a validation: AP50, AP75 (where those thresholds are in the sweep), the mean over the sweep,
+    and what it was computed from."""
+    parts = ['val -']
+    for name, th in (('AP50', 0.5), ('AP75', 0.75)):
+        for t, ap in zip(res['iou_ths'], res['ap']):
+            if abs(t - th) < 1e-9:
+                parts.append('%s %.4f' % (name, ap))
+    parts.append('mAP %.4f' % res['mean_ap'])
+    parts.append('(%d detections on %d images, %d faces)' % (res['n_det'], res['n_images'], res['n_gt']))
+    return ' '.join(parts)
+
+
 # ----------------------------------------------------------------------------- training augmentation (hps['augment'])
-AUGMENT_DEFAULTS = {'zoom': [0.75, 1.25], 'flip': 0.5, 'hue': 0.1, 'saturation': 1.5, 'exposure': 1.5, 'seed': 0}
+AUGMENT_DEFAULTS ={'zoom': [0.75, 1.25], 'flip': 0.5, 'hue': 0.1, 'saturation': 1.5, 'exposure': 1.5, 'seed': 0}
 
 
 def _is_number(v):

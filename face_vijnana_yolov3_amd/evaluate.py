@@ -4,8 +4,9 @@ FaceIdentifier.test's output: `cal_acc_fi` (evaluate.py:225-329) and its sweep (
 `cal_face_pairs_dists` and `cal_VAL_FAR` (evaluate.py:129-223), whose pair distances run on the device (fv_fid_pair_dists,
 DESIGN.md section 15).
 
-The detection / identification metrics are host code, as in the reference (pandas/NumPy/SciPy on a few thousand boxes).
-What they restate, line by line:
+The detection / identification metrics are host code, as in the reference (pandas/NumPy/SciPy on a few thousand boxes);
+cal_mAP_sweep_device is the detection metric with everything after the csv parsing on the device (det_metric.py, DESIGN.md
+section 28), the form FaceDetector.validate runs per epoch.  What they restate, line by line:
 
 * solution csv (no header): FILE, x, y, w, h, confidence  -- what `FaceDetector.evaluate` writes
   (face_detection.py:733-737); ground truth csv (header): FACE_ID, FILE, SUBJECT_ID, FACE_X,
@@ -158,6 +159,55 @@ def cal_mAP_sweep(gt_path, sol_path, iou_ths=None):
         ps, rs = pr_curve(conf, ious, gt_df.shape[0], th)
         res.append((float(th), integrate_pr(ps, rs)))
     return res, float(np.mean([m for _, m in res])) if res else 0.0
+
+
+def sweep_device(gt_path, sol_path, iou_ths=None, ctx=None, want_curve=False):
+    """cal_mAP_sweep's metric with everything after the csv parsing on the device (det_metric.py: fv_det_match_rows, one
+    fv_det_ap_sweep) -> dict: iou_ths, ap, mean_ap, precision, recall (final), n_det and, with want_curve, ps / rs: one float64
+    array per threshold, rebuilt from the device's ranking and running counts with pr_curve's two divisions.  AP is the trapezoid sum
+    over the (recall, precision) points -- the exact integral of the interpolant integrate_pr hands to quad.  An image with more
+    than 60 solution rows (FaceDetector.evaluate never writes more) or more than 4096 ground-truth rows is a ValueError naming the
+    file."""
+    import pandas as pd
+    import torch
+    from . import det_metric
+    from ._lib import Context
+    iou_ths = np.arange(0.5, 1.0, 0.05) if iou_ths is None else np.asarray(iou_ths, np.float64)
+    sol_df = pd.read_csv(sol_path, header=None)
+    gt_df = pd.read_csv(gt_path)
+    names = sorted(gt_df['FILE'].unique())
+    boxes, offs, max_gt = det_metric.group_ground_truth(gt_df, names, gt_path)
+    sol_groups = {k: v for k, v in sol_df.groupby(0, sort=True)}
+    rows = np.zeros((len(names), det_metric.ROWS, 5), np.float64)
+    nrows = np.zeros(len(names), np.int32)
+    for i, name in enumerate(names):
+        rel = sol_groups.get(name)
+        if rel is None:
+            continue
+        if len(rel) > det_metric.ROWS:
+            raise ValueError('%s: %d rows for %s (the device metric takes at most %d per image)' % (sol_path, len(rel), name, det_metric.ROWS))
+        nrows[i] = len(rel)
+        rows[i, :len(rel)] = rel.iloc[:, 1:6].to_numpy(dtype=np.float64)
+    ctx = ctx if ctx is not None else Context(0)
+    dev = torch.device('cuda', ctx.device)
+    d_rows, d_nrows = torch.from_numpy(rows).to(dev), torch.from_numpy(nrows).to(dev)
+    iou, flag = det_metric.match_rows(ctx, d_rows, d_nrows, torch.from_numpy(boxes).to(dev), torch.from_numpy(offs).to(dev), max_gt)
+    out = det_metric.ap_sweep(ctx, d_rows, d_nrows, iou, flag, iou_ths, gt_df.shape[0], want_curve=want_curve)
+    n = int(out['n_det'].cpu()[0])
+    res = det_metric.summarise(iou_ths, out['result'].cpu().numpy(), n)
+    if want_curve:
+        counts = out['counts'][:, :n].cpu().numpy()
+        res['order'] = out['order'][:n].cpu().numpy()
+        res['ps'] = [c / np.arange(1, n + 1) for c in counts]
+        res['rs'] = [c / float(gt_df.shape[0]) for c in counts]
+    return res
+
+
+def cal_mAP_sweep_device(gt_path, sol_path, iou_ths=None, ctx=None):
+    """cal_mAP_sweep with the matching, the ranking and the precision / recall sweep on the device (sweep_device): -> list of
+    (iou_th, mAP) and their mean.  ctx: an fv Context (default: device 0)."""
+    r = sweep_device(gt_path, sol_path, iou_ths, ctx)
+    return [(t, m) for t, m in zip(r['iou_ths'], r['ap'])], r['mean_ap']
 
 
 def acc_fi_image(gt_sids, gt_boxes, det_sids, det_boxes):
@@ -376,6 +426,7 @@ def main(argv=None):
     ap.add_argument('--sol_path', help='solution csv (cal_map_fd, cal_acc_fi)')
     ap.add_argument('--seed', type=int, default=None, help='np.random.seed before the random subject draw (verification modes)')
     ap.add_argument('--resource_type', default='uccs', help='uccs or vggface2: which subject db / facial-ID h5 (verification modes)')
+    ap.add_argument('--device', action='store_true', help='cal_map_fd: matching, ranking and the sweep on the GPU (cal_mAP_sweep_device)')
     ap.add_argument('--counts_only', action='store_true', help='cal_VAL_FAR without the distance arrays (no face_pairs_dists.h5)')
     a = ap.parse_args(argv)
     if a.mode in ('cal_face_pairs_dists', 'cal_VAL_FAR'):
@@ -404,7 +455,7 @@ def main(argv=None):
                                  '/tn_ls': cols[:, 2].astype(np.int64), '/fn_ls': cols[:, 3].astype(np.int64),
                                  '/acc_ls': cols[:, 4]})          # evaluate.py:382-387
         return
-    res, mean = cal_mAP_sweep(a.gt_path, a.sol_path)
+    res, mean = (cal_mAP_sweep_device if a.device else cal_mAP_sweep)(a.gt_path, a.sol_path)
     for th, m in res:
         print('{0:1.2f}'.format(th), m)
     print('mean', mean)

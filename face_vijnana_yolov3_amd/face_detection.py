@@ -32,6 +32,10 @@ ratios.csv, the model files).  Differences, all documented in DESIGN.md:
   * hps['loss'] = 'yolo' (not in the reference, off unless asked for; data.det_loss_conf) trains the three-scale head with YOLOv3's
     detection loss -- ignore mask, box terms on assigned slots only, GIoU or keras-yolo3's box term (fv_yolov3_train_step_det) --
     and prints its statistics once per epoch; train() only
+  * hps['validate'] (not in the reference, off unless asked for; data.validate_conf) measures the model on a held-out folder after
+    every n-th epoch -- cal_mAP_fd's AP over cal_mAP_sweep's thresholds, for the rows evaluate() would write, computed on the device
+    (fv_det_rows_from_nms / fv_det_match_rows / fv_det_ap_sweep) -- keeps the results in validation_history and, with save_best,
+    the best epoch's model in face_detector_best.h5; validate() is public and works on a loaded model
 """
 import glob
 import json
@@ -98,6 +102,7 @@ class FaceDetector(object):
     """Face detector using the Darknet-53 base of YOLOv3."""
 
     MODEL_PATH = 'face_detector.h5'
+    BEST_MODEL_PATH = 'face_detector_best.h5'      # hps['validate'].save_best: the epoch with the largest mean AP so far
     BASE_MODEL_PATH = 'yolov3_base.h5'
     DARKNET_WEIGHTS_PATH = 'yolov3.weights'
     OUTPUT_FILE_NAME = 'solution.csv'
@@ -117,6 +122,9 @@ class FaceDetector(object):
         self.augment = data.augment_conf(self.hps.get('augment'))      # ValueError before a device is touched
         self.mosaic = data.mosaic_conf(self.hps.get('mosaic'))         # likewise
         self.det_loss = data.det_loss_conf(self.hps.get('loss'), self.nn_arch.get('head', 'single'))    # likewise
+        self.validation = data.validate_conf(self.hps.get('validate'), conf.get('test_path'))          # likewise
+        self.validation_history = []
+        self._validator = None
         if self.image_size % 32:
             raise ValueError('image_size must be a multiple of 32 (network stride)')
         if int(self.nn_arch.get('bb_info_c_size', 6)) != 6:
@@ -196,7 +204,13 @@ class FaceDetector(object):
     # ------------------------------------------------------------------ train (fd.py:602-630)
     def train(self):
         from .parallel import DataParallelTrainer
-        seq = self.TrainingSequence(self.raw_data_path, self.hps, self.nn_arch, self.grid, self.cell_image_size)
+        data.refuse_validate_on_ranks(self.hps, self.world)
+        validation = getattr(self, 'validation', None)    # hps['validate'] as __init__ checked it; None: no epoch is validated
+        if validation is not None:
+            self._validator = self._make_validator()      # the held-out set is read and its ground truth uploaded once
+            self.validation_history = []
+        best = None
+        seq =self.TrainingSequence(self.raw_data_path, self.hps, self.nn_arch, self.grid, self.cell_image_size)
         trainer = DataParallelTrainer(self.model, world_size=self.world, rank=self.rank)
         hp = self.hps
         steps = len(seq)
@@ -222,6 +236,15 @@ class FaceDetector(object):
             run_pipelined(self.model, trainer, feeder, [int(i) for i in order], self.image_size, hp, after_step)
             if self.det_loss is not None:
                 self._report_det_epoch(trainer)
+            if validation is not None and ((epoch + 1) % validation['every'] == 0 or epoch + 1 == hp['epochs']):
+                res = self.validate(epoch=epoch + 1)
+                self.validation_history.append(res)
+                if self.rank == 0:
+                    print(data.validate_line(res))
+                    if validation['save_best'] and (best is None or res['mean_ap'] > best):
+                        self.model.save(self.BEST_MODEL_PATH)
+                if best is None or res['mean_ap'] > best:
+                    best = res['mean_ap']
         feeder.close()
         if self.rank == 0:
             print('Save the model.')
@@ -332,14 +355,32 @@ class FaceDetector(object):
         return shard_files(names, self.world, self.rank) if self.world > 1 else names
 
     def _detect_files(self, files, need_raw=True, _with_images=False):
-        """Yield (file_name, raw image, boxes in image coordinates) in file order.  The reference's evaluate()/test() loops
+        """Yield (file_name, raw image, boxes in image coordinates) in file order: _launched_batches with the network + decode/NMS
+        launch of _detect_launch, each batch's result turned into BoundBoxes and projected back one batch behind the queue.
+        _with_images (FaceIdentifier.test): every item gains a fourth element ((device uint8 buffer, offsets, hw), index) -- the
+        batch's decoded images as fv_letterbox_batch read them, kept alive and usable on the current stream."""
+        def finish(done):
+            chunk_, raws_, geoms_, launched, imgs_ = done
+            for i, (name, boxes, geom) in enumerate(zip(chunk_, self._detect_collect(launched), geoms_)):
+                self._project_back(boxes, geom)
+                if _with_images:
+                    yield name, (raws_[i] if raws_ is not None else None), boxes, (imgs_, i)
+                else:
+                    yield name, (raws_[i] if raws_ is not None else None), boxes
+        for done in self._launched_batches(files, lambda x, geoms: self._detect_launch(x), need_raw, _with_images):
+            for item in finish(done):
+                yield item
+
+    def _launched_batches(self, files, launch, need_raw=True, _with_images=False):
+        """The batched input path of evaluate() / test() / validate(): yield (chunk of file names, raw images or None, letterbox
+        geometries, launch(x, geoms), device images or None) per batch of hps['eval_batch_size'] files, x the (n,S,S,3) letterboxed
+        batch on the device, one batch behind the queue: batch k-1 is yielded once launch(k) was called and batch
+        k+1 was staged, so the consumer's host work on a result never holds the device up.  The reference's evaluate()/test() loops
         (fd.py:632-883) decode, letterbox and predict one image at a time; here a thread pool decodes batch k+1 (PIL releases
         the GIL) while batch k is letterboxed in one launch (fv_letterbox_batch) and runs ONE forward + ONE decode/NMS launch
         -- batch 1 is the slowest operating point of the network (1.3 ms/img against 0.4 at batch 16+).  Two deep: the loader
-        thread fills a reused pinned buffer (PinnedRing) with batch k+1 while batch k is in the device queue and the host turns
-        batch k-1's result into BoundBoxes and rows.  _with_images (FaceIdentifier.test): every item gains a fourth element
-        ((device uint8 buffer, offsets, hw), index) -- the batch's decoded images as fv_letterbox_batch read them, kept alive and
-        usable on the current stream."""
+        thread fills a reused pinned buffer (PinnedRing) with batch k+1 while batch k is in the device queue and the consumer works on
+        batch k-1's result."""
         bs = max(1, int(self.hps.get('eval_batch_size', default_eval_batch(self.image_size))))
         chunks = [files[i:i + bs] for i in range(0, len(files), bs)]
         if not chunks:
@@ -372,14 +413,6 @@ class FaceDetector(object):
                             ring.untake()
                 raws = list(pool.map(data._pil_loader, chunk))
                 return raws, pack_images(raws, ring=ring)
-            def finish(done):
-                chunk_, raws_, geoms_, launched, imgs_ = done
-                for i, (name, boxes, geom) in enumerate(zip(chunk_, self._detect_collect(launched), geoms_)):
-                    self._project_back(boxes, geom)
-                    if _with_images:
-                        yield name, (raws_[i] if raws_ is not None else None), boxes, (imgs_, i)
-                    else:
-                        yield name, (raws_[i] if raws_ is not None else None), boxes
             # The device half of the input path (H2D copy of the batch -- 70 MB of JPEG coefficients at 32 images: ~3 ms of PCIe time --,
             # fv_jpeg_reconstruct_batch, fv_letterbox_batch) runs on its OWN stream: batch k+1 is staged while batch k's forward computes
             # (on one stream the copy sat in front of every forward: 16.7 ms per batch of 32 where the forward takes 12.8).
@@ -415,18 +448,16 @@ class FaceDetector(object):
                 x.record_stream(main)              # allocated on the staging stream, consumed on the compute stream
                 if imgs is not None:
                     imgs[0].record_stream(main)
-                cur = (chunk, raws, geoms, self._detect_launch(x), imgs)
+                cur = (chunk, raws, geoms, launch(x, geoms), imgs)
                 if k + 1 < len(chunks):            # the host waits for the decode of k+1 while the GPU runs batch k, then stages it beside it
                     loaded = pending.result()
                     if k + 2 < len(chunks):
                         pending = one.submit(load, chunks[k + 2])
                     staged = stage(loaded)
-                if prev is not None:               # read batch k-1 now that batch k is in the queue
-                    for item in finish(prev):
-                        yield item
+                if prev is not None:               # hand out batch k-1 now that batch k is in the queue
+                    yield prev
                 prev = cur
-            for item in finish(prev):
-                yield item
+            yield prev
 
     def evaluate(self):
         import pandas as pd
@@ -490,6 +521,56 @@ class FaceDetector(object):
                     print(n + 1, '/', len(files), file_name)
                 self._write_rows(f, file_name, boxes)
         merge_rank_files(out_path, self.world, self.rank)
+
+    # ------------------------------------------------------------------ validate (hps['validate'])
+    def _make_validator(self):
+        from .det_metric import Validator
+        conf = getattr(self, 'validation', None) or data.validate_conf(True, self.conf.get('test_path'))
+        return Validator(self.model.ctx, self.model.dev, conf)
+
+    def validate(self, epoch=None):
+        """cal_mAP_sweep of what evaluate() would write for the held-out set of hps['validate'] (absent: the defaults over
+        conf['test_path']), without a csv, an annotated image or a host metric: the batched input path of test(), then per batch
+        fv_decode_nms -> fv_det_rows_from_nms -> fv_det_match_rows with nothing copied to the host (three-scale head: the rows come
+        from the host tail of detect and are uploaded), one fv_det_ap_sweep over the set and one small D2H copy.  Inference on the
+        moving statistics in the inference workspace: no parameter, BN statistic, optimiser state or random generator of train() is
+        touched.  -> dict: epoch, iou_ths, ap (per threshold), mean_ap, precision, recall (final, per threshold), n_det, n_images,
+        n_gt."""
+        import torch
+        from . import det_metric
+        data.refuse_validate_on_ranks({'validate': True}, self.world)
+        if getattr(self, '_validator', None) is None:
+            self._validator = self._make_validator()
+        v = self._validator
+        ctx, dev = self.model.ctx, self.model.dev
+        state = {'i0': 0}
+
+        def launch(x, geoms):
+            i0, n = state['i0'], int(x.shape[0])
+            state['i0'] = i0 + n
+            if self.three_scale:
+                return i0, self._detect_launch(x)
+            res = decode_nms(ctx, self.model.predict_device(x), self.image_size, self.hps['face_conf_th'], self.hps['nms_iou_th'],
+                             self.hps['num_cands'])
+            geom = torch.tensor(geoms, dtype=torch.int32).reshape(n, 6).to(dev, non_blocking=True)
+            det_metric.rows_from_nms(ctx, res, geom, self.image_size, v.rows[i0:i0 + n], v.nrows[i0:i0 + n])
+            v.match(ctx, i0, n)
+            return i0, None
+
+        for _chunk, _raws, geoms, (i0, launched), _imgs in self._launched_batches(v.files, launch, need_raw=False):
+            if launched is None:
+                continue
+            boxes = self._detect_collect(launched)
+            for b, geom in zip(boxes, geoms):
+                self._project_back(b, geom)
+            rows, nrows = det_metric.rows_from_boxes(boxes)
+            n = len(boxes)
+            v.rows[i0:i0 + n].copy_(torch.from_numpy(rows))
+            v.nrows[i0:i0 + n].copy_(torch.from_numpy(nrows))
+            v.match(ctx, i0, n)
+        res = v.finish(ctx)
+        res['epoch'] = epoch
+        return res
 
 
 class YoloV3BaseModel(object):
@@ -793,6 +874,8 @@ def main():
     if conf['mode'] not in ('train', 'evaluate', 'test'):
         return
     n = int(conf.get('num_gpus', 1)) if conf.get('multi_gpu') else 1
+    if conf['mode'] == 'train':
+        data.refuse_validate_on_ranks(conf.get('hps', {}), n)            # before a rank is started
     if n > 1 and 'WORLD_SIZE' not in os.environ:
         # multi_gpu_model(model, gpus=num_gpus) (fd.py:358-371) is one process driving num_gpus towers; here it is one process
         # per GPU, started from this one BEFORE it makes any GPU call -- the reference's command line stays what it was

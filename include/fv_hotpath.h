@@ -150,6 +150,47 @@ int fv_decode_nms(fv_ctx* ctx, const float* head, int nimg, int grid, int image_
  * the reference's Python-float arithmetic (nan / inf for a zero union, as NumPy division gives). */
 int fv_bbox_iou_pairs(fv_ctx* ctx, const double* boxes_a, const double* boxes_b, int64_t npairs, double* iou);
 
+/* ------------------------------------------------------------------ detection metric on the device (FaceDetector.validate)
+ * cal_mAP_fd (evaluate.py:27-127) without the csv round trip: DESIGN.md section 28.  Every buffer is on the device unless it says
+ * host; no call waits for the stream; no float atomics, so the same inputs give the same bytes whatever the launch geometry.
+ *
+ * fv_det_rows_from_nms: fv_decode_nms's result -> the rows FaceDetector.evaluate would have written.  boxes [nimg][num_cands][4],
+ * score [nimg][num_cands], count [nimg] as fv_decode_nms leaves them; geom [nimg][6] int32 (h, w, pad_t, pad_b, pad_l, pad_r), the
+ * letterbox geometry of fv_letterbox_batch.  Image i keeps its first min(count[i], FV_DET_ROWS) detections in that order
+ * (_write_rows' boxes[:60]), undoes the letterbox with _project_back's float64 operations in its order (int -> double, subtract,
+ * max, multiply, divide, min; both w >= h branches) and writes rows [nimg][FV_DET_ROWS][5] float64 = x, y, w = xmax - xmin,
+ * h = ymax - ymin, conf = (double)min(score, 1) -- the doubles float() reads back from the csv fields -- and nrows [nimg].  Rows
+ * past nrows[i] are written as zeros. */
+#define FV_DET_ROWS 60
+#define FV_DET_MAX_GT 4096
+#define FV_DET_MAX_TH 16
+int fv_det_rows_from_nms(fv_ctx* ctx, const int32_t* boxes, const float* score, const int32_t* count, const int32_t* geom, int nimg,
+                         int num_cands, int image_size, double* rows, int32_t* nrows);
+/* The greedy assignment of cal_mAP_fd per image (evaluate.py:46-95), one workgroup per image: rows / nrows as above (nrows is
+ * clamped to [0, FV_DET_ROWS]); gt [total][4] float64 x, y, w, h and gt_off [nimg + 1] int64, image i's boxes being
+ * gt[gt_off[i] .. gt_off[i + 1]).  IoUs are fv_bbox_iou_pairs' on the corners (x, y, x + w, y + h).  Pairs with IoU > 0 are taken
+ * in descending IoU order, equal IoUs by the smaller ground-truth index, then the smaller detection index, each box and each
+ * detection at most once; nan is never > 0, +inf is.  iou [nimg][FV_DET_ROWS]: a detection's assigned IoU, -1.0 without one (and
+ * past nrows); flag [nimg]: 1 when some pair overlapped, 0 when none did (the reference then drops the image's detections).
+ * max_gt is the caller's bound on gt_off[i + 1] - gt_off[i]; more than FV_DET_MAX_GT is FV_ERR_INVALID and nothing is enqueued.  An
+ * image the device finds outside [0, FV_DET_MAX_GT] all the same gets flag -1 and no box of it is read. */
+int fv_det_match_rows(fv_ctx* ctx, const double* rows, const int32_t* nrows, const double* gt, const int64_t* gt_off, int nimg,
+                      int max_gt, double* iou, int32_t* flag);
+/* Ranking and precision / recall sweep (evaluate.py:104-125) over n_img images' rows, iou and flag as the two calls above leave
+ * them.  The detections of images with flag > 0, in image order then row order, are the N (conf, iou) pairs; they are ranked by
+ * descending conf, equal confidences by the earlier position (np.argsort(-conf, kind='stable'); conf must not be nan); per
+ * threshold t (host, 1 <= n_th <= FV_DET_MAX_TH) tp_k = the inclusive running count of iou >= thresholds[t] along the ranking, and
+ *   result[t]            = sum_{k=1}^{N-1} (r_k - r_{k-1}) * (p_k + p_{k-1}) / 2,  p_k = tp_k / (k + 1),  r_k = tp_k / gt_count
+ *                          (float64; the exact integral of the linear interpolant the reference hands to quad; 0 for N < 2),
+ *   result[n_th + t]     = p_{N-1},   result[2 * n_th + t] = r_{N-1}   (0 for N == 0),
+ * n_det [1] int32 = N.  order (may be NULL) [n_img * FV_DET_ROWS] int32 receives the ranking in its first N entries, counts (may be
+ * NULL) [n_th][n_img * FV_DET_ROWS] int32 tp_k in the first N entries of each row.  gt_count >= 1.  workspace:
+ * fv_det_ap_sweep_workspace_bytes(n_img) bytes, 8-byte aligned; its contents on entry are ignored. */
+size_t fv_det_ap_sweep_workspace_bytes(int n_img);
+int fv_det_ap_sweep(fv_ctx* ctx, const double* rows, const int32_t* nrows, const double* iou, const int32_t* flag, int n_img,
+                    const double* thresholds, int n_th, int64_t gt_count, void* workspace, size_t workspace_bytes, double* result,
+                    int32_t* n_det, int32_t* order, int32_t* counts);
+
 /* ------------------------------------------------------------------ network description
  * The FaceDetector network: the first 52 conv+BN+LeakyReLU(0.1) layers / 23 residual adds of
  * make_yolov3_model (yd.py:221-267) as re-wired by FaceDetector.YOLOV3Base (fd.py:404-593), plus
