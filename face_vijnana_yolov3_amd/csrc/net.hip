@@ -85,25 +85,13 @@ int fv_train_step(fv_ctx* ctx, const float* params, float* bn_state, const float
     const int nb = p.nl - 1;
     const Train t{ctx, N.L, p.k, batch, image_size, params, bn_state, grads};
 
-    FV_HIP(ctx, hipMemsetAsync(grads, 0, (size_t)N.nparam * sizeof(float), ctx->stream));
-    FV_HIP(ctx, hipMemsetAsync(p.k.slots[0], 0, p.k.slots_bytes, ctx->stream));   // forward and backward accumulators
-    // weight images for this step: packed first layer, transposed kernels for the data-gradients
-    if (int rc = fv_ew_pad_rows(ctx, params + N.L[0].w_off, p.w0p, 32, 27, 32)) return rc;
-    if (int rc = transpose_weights(ctx, N.L, params, p.k.wt, HEAD_PAD)) return rc;
-
+    if (int rc = train_step_begin(ctx, N.L, params, grads, N.nparam, {&p.k}, p.w0p, HEAD_PAD)) return rc;
     // ---------------- forward (training-mode BN)
-    const float* cur = x;
-    const float* skip = nullptr;
-    for (int l = 0; l < nb; ++l) {
-        const auto& d = N.L[l];
-        if (d.role == 1) skip = cur;
-        if (int rc = train_bn_forward(t, l, cur, l == 0 ? p.w0p : params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
-        cur = p.k.a[l];
-    }
+    if (int rc = base_train_forward(t, nb, x, p.w0p)) return rc;
     if (int rc = train_bn_forward_end(t)) return rc;
     // the head conv has 6 output channels: K-split like the batch-1 inference path (conv_small and conv_bm64 never take it)
     const auto& h = N.L[nb];
-    if (int rc = infer_conv(Infer{ctx, params, batch, image_size, nullptr, nullptr, nullptr, p.head_slab}, h, cur, nullptr, p.yhat)) return rc;
+    if (int rc = infer_conv(Infer{ctx, params, batch, image_size, nullptr, nullptr, nullptr, p.head_slab}, h, p.k.a[nb - 1], nullptr, p.yhat)) return rc;
     // ---------------- loss + its gradient (fd.py:381 'mse')
     const int G = image_size / h.in_div;
     if (int rc = fv_ew_mse(ctx, p.yhat, y_true, batch * G * G, HEAD_C, HEAD_PAD, loss, p.dyp, grads + h.beta_off, (double*)p.mse_part,

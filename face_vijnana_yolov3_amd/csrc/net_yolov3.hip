@@ -271,10 +271,7 @@ static int yolov3_train_step_body(fv_ctx* ctx, const float* params, float* bn_st
     EmaReset ema_reset{ctx};
     const Train t{ctx, N.L, p.k, B, S, params, bn_state, grads};
 
-    FV_HIP(ctx, hipMemsetAsync(grads, 0, (size_t)N.nparam * sizeof(float), ctx->stream));
-    FV_HIP(ctx, hipMemsetAsync(p.k.slots[0], 0, p.k.slots_bytes, ctx->stream));
-    if (int rc = fv_ew_pad_rows(ctx, params + N.L[0].w_off, p.w0p, 32, 27, 32)) return rc;
-    if (int rc = transpose_weights(ctx, N.L, params, p.k.wt, p.cpad)) return rc;
+    if (int rc = train_step_begin(ctx, N.L, params, grads, N.nparam, {&p.k}, p.w0p, p.cpad)) return rc;
     const int l35 = find_base(N, 35), l60 = find_base(N, 60);
     const int P79 = nb + 4, P80 = nb + 5, D13 = nb + 6, P84 = nb + 7, P87 = nb + 8, P91 = nb + 12, P92 = nb + 13, D26 = nb + 14, P96 = nb + 15,
               P99 = nb + 16, P104 = nb + 21, D52 = nb + 22;

@@ -1,7 +1,7 @@
-// Host-side pieces shared by the two network schedules (net.hip: FaceDetector, net_yolov3.hip: the three-scale graph):
-// workspace carving and sizing, the batch check, the inference conv dispatch, the training forward of a BN layer and the
-// backward pass with its side-stream weight-gradient pipeline.  No kernels here: every helper enqueues operator launches.
-// Included by the two schedule files only.
+// Host-side pieces shared by the network schedules (net.hip: FaceDetector, net_yolov3.hip: the three-scale graph, net_fid.hip:
+// the FaceIdentifier's towers): workspace carving and sizing, the batch check, the inference conv dispatch, a training step's
+// preamble, the training forward of a BN layer and of the base, and the backward pass with its side-stream weight-gradient
+// pipeline.  No kernels here: every helper enqueues operator launches.  Included by the schedule files only.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -308,6 +308,31 @@ int train_bn_forward_end(const Train& t) {
     const float* skip = t.deferred_skip;
     t.deferred = -1; t.deferred_skip = nullptr;
     return train_bn_pass(t, l, skip);
+}
+
+// What every training step enqueues first: the gradient vector and the accumulator slots (forward and backward) of each plan's
+// kept tensors zeroed, then the weight images of this step -- the first layer's kernel packed into w0p and the transposed kernels
+// for the data-gradients in kept[0]'s wt -- made once, whichever plans share them.
+int train_step_begin(fv_ctx* ctx, const Layers& L, const float* params, float* grads, int64_t nparam,
+                     const std::vector<const Kept*>& kept, float* w0p, int cpad) {
+    FV_HIP(ctx, hipMemsetAsync(grads, 0, (size_t)nparam * sizeof(float), ctx->stream));
+    for (const Kept* k : kept) FV_HIP(ctx, hipMemsetAsync(k->slots[0], 0, k->slots_bytes, ctx->stream));
+    if (int rc = fv_ew_pad_rows(ctx, params + L[0].w_off, w0p, 32, 27, 32)) return rc;
+    return transpose_weights(ctx, L, params, kept[0]->wt, cpad);
+}
+
+// Training forward of the Darknet-53 base L[0, nb) from x into t.k.a[nb - 1]; the caller ends the pass (train_bn_forward_end)
+// where its own forward stops.
+int base_train_forward(const Train& t, int nb, const float* x, const float* w0p) {
+    const float* cur = x;
+    const float* skip = nullptr;
+    for (int l = 0; l < nb; ++l) {
+        const auto& d = t.L[l];
+        if (d.role == 1) skip = cur;
+        if (int rc = train_bn_forward(t, l, cur, l == 0 ? w0p : t.params + d.w_off, d.role == 2 ? skip : nullptr)) return rc;
+        cur = t.k.a[l];
+    }
+    return FV_OK;
 }
 
 // Every data-gradient also reduces d-beta / d-gamma of the BN layer whose output gradient it produces (conv.h FV_EPI_BNRED):

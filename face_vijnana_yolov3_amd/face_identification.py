@@ -160,17 +160,30 @@ class FidModel(Model):
         return loss
 
     # ------------------------------------------------------------------ training on a labelled batch
-    def _batch_workspace(self, M):
-        """The workspace of fv_fid_batch_train_step, under a key of its own: the triplet step's and extraction's stay.  One buffer,
-        grown to the largest batch so far (a PK batch is short where a subject has fewer than K crops)."""
-        n = int(lib().fv_fid_batch_workspace_bytes(M, self.image_size))
+    def _grown_workspace(self, name, n, what, shape):
+        """The workspace of a one-tower step, under a key of its own: the triplet step's and extraction's stay.  One buffer of n
+        bytes, grown to the largest call so far (a PK batch is short where a subject has fewer than K crops)."""
         if n == 0:
-            raise FvError('unsupported batch/image_size %r' % ((M, self.image_size),))
-        key = (0, self.image_size, 'labelled_batch')
+            raise FvError('unsupported %s %r' % (what, shape))
+        key = (0, self.image_size, name)
         if key not in self._ws or self._ws[key].numel() < n:
             self._ws.pop(key, None)
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
+            self._ws[key] = torch.empty(int(n), dtype=torch.uint8, device=self.dev)
         return self._ws[key]
+
+    def _batch_workspace(self, M):
+        """The workspace of fv_fid_batch_train_step."""
+        return self._grown_workspace('labelled_batch', lib().fv_fid_batch_workspace_bytes(M, self.image_size), 'batch/image_size',
+                                     (M, self.image_size))
+
+    def _row_ints(self, who, what, values, M):
+        """values (a subject or a label per image of the batch) -> (M,) int32 on the device; a batch is at most BATCH_MAX_ROWS."""
+        rows = torch.as_tensor(values if torch.is_tensor(values) else np.asarray(values)).to(device=self.dev, dtype=torch.int32).contiguous()
+        if rows.dim() != 1 or rows.shape[0] != M:
+            raise ValueError('%s expects one %s per image (%d images, %ss of shape %r)' % (who, what, M, what, tuple(rows.shape)))
+        if M > BATCH_MAX_ROWS:
+            raise ValueError('%s takes at most %d images, got %d' % (who, BATCH_MAX_ROWS, M))
+        return rows
 
     def forward_backward_batch(self, x, subjects, mode='batch_hard', margin=None):
         """One tower over the labelled batch x (M,S,S,3), subjects (M,) int32 (< 0: an unknown identity), triplets mined inside
@@ -180,12 +193,7 @@ class FidModel(Model):
         self.ensure_optimizer()
         x = self._as_input(x)
         M = x.shape[0]
-        sub = torch.as_tensor(np.asarray(subjects) if not torch.is_tensor(subjects) else subjects)
-        sub = sub.to(device=self.dev, dtype=torch.int32).contiguous()
-        if sub.dim() != 1 or sub.shape[0] != M:
-            raise ValueError('forward_backward_batch expects one subject per image (%d images, subjects of shape %r)' % (M, tuple(sub.shape)))
-        if M > BATCH_MAX_ROWS:
-            raise ValueError('forward_backward_batch takes at most %d images, got %d' % (BATCH_MAX_ROWS, M))
+        sub = self._row_ints('forward_backward_batch', 'subject', subjects, M)
         code = BATCH_MINING_MODES.get(mode, mode)
         if isinstance(code, bool) or code not in (0, 1):
             raise ValueError('forward_backward_batch: mode %r (available: %s)' % (mode, ', '.join(sorted(BATCH_MINING_MODES))))
@@ -193,15 +201,12 @@ class FidModel(Model):
         sel = dict(pos_index=torch.empty(M, dtype=torch.int32, device=self.dev), neg_index=torch.empty(M, dtype=torch.int32, device=self.dev),
                    kind=torch.empty(M, dtype=torch.int32, device=self.dev), d_ap=torch.empty(M, dtype=torch.float64, device=self.dev),
                    d_an=torch.empty(M, dtype=torch.float64, device=self.dev))
-        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
-        rc = lib().fv_fid_batch_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), ptr(sub), M, self.image_size,
-                                           int(code), float(TRIPLET_MARGIN if margin is None else margin), ptr(ws), ws.numel(),
-                                           ptr(self.grads), ptr(self._loss), ptr(sel['pos_index']), ptr(sel['neg_index']),
-                                           ptr(sel['kind']), ptr(sel['d_ap']), ptr(sel['d_an']))
-        self.ctx.check(rc, 'fv_fid_batch_train_step')
-        self.bn_updates += 1
+        loss = self._train_call('fv_fid_batch_train_step', ptr(x), ptr(sub), M, self.image_size, int(code),
+                                float(TRIPLET_MARGIN if margin is None else margin), ptr(ws), ws.numel(), ptr(self.grads), ptr(self._loss),
+                                ptr(sel['pos_index']), ptr(sel['neg_index']), ptr(sel['kind']), ptr(sel['d_ap']), ptr(sel['d_an']),
+                                bn_updates=1)
         self.batch_selection = sel
-        return self._loss
+        return loss
 
     def train_on_labelled_batch(self, x, subjects, mode, lr, beta_1, beta_2, decay=0.0, margin=None):
         loss = self.forward_backward_batch(x, subjects, mode, margin)
@@ -226,15 +231,10 @@ class FidModel(Model):
         self.class_v = torch.zeros_like(self.class_kernel)
 
     def _cls_workspace(self, M):
-        """The workspace of fv_fid_cls_train_step, under a key of its own (nothing else is evicted), grown to the largest call."""
-        n = int(lib().fv_fid_cls_workspace_bytes(M, int(self.class_kernel.shape[0]), self.image_size))
-        if n == 0:
-            raise FvError('unsupported batch/classes/image_size %r' % ((M, int(self.class_kernel.shape[0]), self.image_size),))
-        key = (0, self.image_size, 'classified_batch')
-        if key not in self._ws or self._ws[key].numel() < n:
-            self._ws.pop(key, None)
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        return self._ws[key]
+        """The workspace of fv_fid_cls_train_step."""
+        C = int(self.class_kernel.shape[0])
+        return self._grown_workspace('classified_batch', lib().fv_fid_cls_workspace_bytes(M, C, self.image_size),
+                                     'batch/classes/image_size', (M, C, self.image_size))
 
     def forward_backward_classes(self, x, labels, kind='cosface', scale=MARGIN_SOFTMAX_SCALE, margin=None):
         """One tower over the labelled batch x (M,S,S,3), labels (M,) int32 class indices (< 0: an unknown identity), the margin
@@ -251,27 +251,18 @@ class FidModel(Model):
             labels = np.asarray(labels)
             if labels.size and int(labels.max()) >= C:
                 raise ValueError('forward_backward_classes: label %d is not below the %d classes' % (int(labels.max()), C))
-            labels = torch.as_tensor(labels)
-        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
-        if lab.dim() != 1 or lab.shape[0] != M:
-            raise ValueError('forward_backward_classes expects one label per image (%d images, labels of shape %r)' % (M, tuple(lab.shape)))
-        if M > BATCH_MAX_ROWS:
-            raise ValueError('forward_backward_classes takes at most %d images, got %d' % (BATCH_MAX_ROWS, M))
+        lab = self._row_ints('forward_backward_classes', 'label', labels, M)
         name = kind if isinstance(kind, str) else {v: k for k, v in MARGIN_SOFTMAX_KINDS.items()}.get(kind)
         if isinstance(kind, bool) or name not in MARGIN_SOFTMAX_KINDS:
             raise ValueError('forward_backward_classes: kind %r (available: %s)' % (kind, ', '.join(sorted(MARGIN_SOFTMAX_KINDS))))
         margin = MARGIN_SOFTMAX_MARGINS[name] if margin is None else margin
         ws = self._cls_workspace(M)
         sel = dict(pred=torch.empty(M, dtype=torch.int32, device=self.dev), cos_t=torch.empty(M, dtype=torch.float64, device=self.dev))
-        self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
-        rc = lib().fv_fid_cls_train_step(self.ctx.handle, ptr(self.params), ptr(self.state), ptr(x), ptr(lab), M, self.image_size,
-                                         ptr(self.class_kernel), C, MARGIN_SOFTMAX_KINDS[name], float(scale), float(margin), ptr(ws),
-                                         ws.numel(), ptr(self.grads), ptr(self.class_grads), ptr(self._loss), ptr(sel['pred']),
-                                         ptr(sel['cos_t']))
-        self.ctx.check(rc, 'fv_fid_cls_train_step')
-        self.bn_updates += 1
+        loss = self._train_call('fv_fid_cls_train_step', ptr(x), ptr(lab), M, self.image_size, ptr(self.class_kernel), C,
+                                MARGIN_SOFTMAX_KINDS[name], float(scale), float(margin), ptr(ws), ws.numel(), ptr(self.grads),
+                                ptr(self.class_grads), ptr(self._loss), ptr(sel['pred']), ptr(sel['cos_t']), bn_updates=1)
         self.class_selection = sel
-        return self._loss
+        return loss
 
     def train_on_classified_batch(self, x, labels, kind, scale, margin, lr, beta_1, beta_2, decay=0.0):
         """forward_backward_classes, then Adam over the class kernel (its own m / v; the same iteration, lr, betas and decay)
@@ -1493,19 +1484,20 @@ class FaceIdentifier(object):
         h = self.hps
         steps, epochs = int(h['step']), int(h['epochs'])
         pk = batch_mining_conf(h, self.image_size) if batch_mining_mode(h) is not None else None
-        if pk is not None:                 # one rank (refused above otherwise): no collective below
+        if pk is not None:                 # one rank (refused above otherwise): no collective in the loop
             self._train_pk(tr_gen, pk, steps, epochs)
+        elif margin_softmax_kind(h) is not None:      # one rank as well
+            self._train_classes(tr_gen, margin_softmax_conf(h, self.image_size), steps, epochs)
+        else:
+            self._train_triplets(tr_gen, trainer, steps, epochs)
+        if self.rank == 0:
             print('Save the model.')
             self.model.save(self.MODEL_PATH)
-            trainer.shutdown()
-            return
-        ms = margin_softmax_conf(h, self.image_size) if margin_softmax_kind(h) is not None else None
-        if ms is not None:                 # one rank (refused above otherwise): no collective below
-            self._train_classes(tr_gen, ms, steps, epochs)
-            print('Save the model.')
-            self.model.save(self.MODEL_PATH)
-            trainer.shutdown()
-            return
+        trainer.shutdown()
+
+    def _train_triplets(self, tr_gen, trainer, steps, epochs):
+        """train() over the sequence's triplets (mined anew where hps['triplet_mining'] says so), on every rank."""
+        h = self.hps
         inputs = self._triplet_inputs(tr_gen)
         # one rank: the global numpy stream, as before; several: one seeded generator, the same batch order on every rank
         rng = np.random.default_rng(0) if self.world > 1 else np.random
@@ -1541,10 +1533,6 @@ class FaceIdentifier(object):
         finally:
             if inputs is not None:
                 inputs.close()
-        if self.rank == 0:
-            print('Save the model.')
-            self.model.save(self.MODEL_PATH)
-        trainer.shutdown()
 
     def _train_pk(self, tr_gen, pk, steps, epochs):
         """train() with hps['batch_mining']: every epoch draws its PK batches (pk_batches, one generator
@@ -1553,40 +1541,52 @@ class FaceIdentifier(object):
         the epoch, the anchors of each kind and how many had a hinge that passes a gradient.  Nothing is read back before the
         epoch's last step is in the queue.  self.last_batch_mining: the batches (db row positions) of every epoch, the last
         epoch's counts."""
+        m, h = self.model, self.hps
+        last = self.last_batch_mining = dict(batches=[], counts=None, active=None)
+        sums = torch.zeros(5, dtype=torch.int64, device=m.dev)        # this epoch's anchors of each kind, active hinges
+
+        def step(x, subjects):
+            loss = m.train_on_labelled_batch(x, subjects, pk['mode'], h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0))
+            sel = m.batch_selection
+            valid = sel['kind'] != KIND_NONE
+            sums[:4] += torch.bincount(sel['kind'].to(torch.int64), minlength=4)[:4]
+            sums[4] += (valid & (sel['d_ap'] - sel['d_an'] + TRIPLET_MARGIN >= 0)).sum()     # NaN >= 0 is False
+            return loss
+
+        def report(e, mean):
+            c = [int(v) for v in sums.cpu()]
+            sums.zero_()
+            last.update(counts=c[:4], active=c[4])
+            print('Epoch %d/%d - loss: %.4f - anchors (%s) semi-hard: %d, violating: %d, easy: %d, without a triplet: %d, active: %d'
+                  % (e + 1, epochs, mean, pk['mode'], c[0], c[1], c[2], c[3], c[4]))
+        self._train_labelled(tr_gen, pk['P'], pk['K'], pk['seed'], steps, epochs, last['batches'], m._batch_workspace, step, report)
+
+    def _train_labelled(self, tr_gen, P, K, seed, steps, epochs, drawn, workspace, step, report):
+        """The loop of _train_pk and _train_classes.  workspace(P * K) allocates the step's workspace, before the store's budget is
+        taken from what is free; the crops come from a TripletInputs (hps['crop_store']: the store, else the host tier).  Every
+        epoch draws its batches of db row positions (pk_batches, one generator seeded with `seed` for the whole run), appends
+        them to `drawn`, runs min(steps, batches) of them through step(x, codes) -> loss and calls report(e, mean loss) once
+        the epoch's last step is in the queue: nothing is read back before."""
         from .crop_store import HOST, TripletInputs, store_budget
-        m, h, S = self.model, self.hps, self.image_size
+        m, h = self.model, self.hps
         labels = list(tr_gen.db.index)
         codes = subject_codes(list(tr_gen.db['subject_id']))
-        rng = np.random.default_rng(pk['seed'])
-        rows_most = pk['P'] * pk['K']
+        rng = np.random.default_rng(seed)
         m.ensure_optimizer()
-        m._batch_workspace(rows_most)      # before the store's budget is taken from what is free
+        workspace(P * K)
         if h.get('crop_store', CROP_STORE_DEFAULT):
-            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, store_budget(h, m.dev),
-                                   self._loader_threads(), slots=max(3 * tr_gen.batch_size, rows_most))
+            inputs = TripletInputs(m.ctx, m.dev, self.image_size, labels, tr_gen.path, tr_gen.batch_size, store_budget(h, m.dev),
+                                   self._loader_threads(), slots=max(3 * tr_gen.batch_size, P * K))
         else:
-            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, 0, self._loader_threads(), tier=HOST)
-        self.last_batch_mining = dict(batches=[], counts=None, active=None)
+            inputs = TripletInputs(m.ctx, m.dev, self.image_size, labels, tr_gen.path, tr_gen.batch_size, 0, self._loader_threads(),
+                                   tier=HOST)
         try:
             for e in range(epochs):
-                batches = pk_batches(codes, pk['P'], pk['K'], rng)[:steps]
-                self.last_batch_mining['batches'].append(batches)
-                losses = []
-                counts = torch.zeros(4, dtype=torch.int64, device=m.dev)
-                active = torch.zeros((), dtype=torch.int64, device=m.dev)
+                batches = pk_batches(codes, P, K, rng)[:steps]
+                drawn.append(batches)
                 feed = inputs.crop_batches([[labels[r] for r in b] for b in batches])
-                for b, x in zip(batches, feed):
-                    loss = m.train_on_labelled_batch(x, codes[b], pk['mode'], h['lr'], h['beta_1'], h['beta_2'], h.get('decay', 0.0))
-                    losses.append(loss.clone())
-                    sel = m.batch_selection
-                    valid = sel['kind'] != KIND_NONE
-                    counts += torch.bincount(sel['kind'].to(torch.int64), minlength=4)[:4]
-                    active += (valid & (sel['d_ap'] - sel['d_an'] + TRIPLET_MARGIN >= 0)).sum()     # NaN >= 0 is False
-                c = [int(v) for v in counts.cpu()]
-                self.last_batch_mining.update(counts=c, active=int(active.cpu()))
-                mean = float(torch.cat(losses).double().mean().cpu()) if losses else float('nan')
-                print('Epoch %d/%d - loss: %.4f - anchors (%s) semi-hard: %d, violating: %d, easy: %d, without a triplet: %d, active: %d'
-                      % (e + 1, epochs, mean, pk['mode'], c[0], c[1], c[2], c[3], self.last_batch_mining['active']))
+                losses = [step(x, codes[b]).clone() for b, x in zip(batches, feed)]
+                report(e, float(torch.cat(losses).double().mean().cpu()) if losses else float('nan'))
         finally:
             inputs.close()
 
@@ -1598,10 +1598,8 @@ class FaceIdentifier(object):
         epoch.  Per epoch one line: the mean loss, the training accuracy (pred == label over the labelled rows) and the mean
         target cosine, summed on the device and read back once.  self.last_margin_softmax: the batches of every epoch, the class
         count, the last epoch's accuracy and mean cosine."""
-        from .crop_store import HOST, TripletInputs, store_budget
         from .hdf5_lite import write_hdf5
-        m, h, S = self.model, self.hps, self.image_size
-        labels = list(tr_gen.db.index)
+        m, h = self.model, self.hps
         sids = list(tr_gen.db['subject_id'])
         codes = subject_codes(sids)
         C = int(codes.max()) + 1 if len(codes) else 0
@@ -1614,40 +1612,26 @@ class FaceIdentifier(object):
             m.init_classes(C, ms['seed'])
         else:
             m.set_classes(kernel)
-        rng = np.random.default_rng(ms['pk_seed'])
-        rows_most = ms['P'] * ms['K']
-        m.ensure_optimizer()
-        m._cls_workspace(rows_most)        # before the store's budget is taken from what is free
-        if h.get('crop_store', CROP_STORE_DEFAULT):
-            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, store_budget(h, m.dev),
-                                   self._loader_threads(), slots=max(3 * tr_gen.batch_size, rows_most))
-        else:
-            inputs = TripletInputs(m.ctx, m.dev, S, labels, tr_gen.path, tr_gen.batch_size, 0, self._loader_threads(), tier=HOST)
-        self.last_margin_softmax = dict(batches=[], classes=C, accuracy=None, cos_t=None)
-        try:
-            for e in range(epochs):
-                batches = pk_batches(codes, ms['P'], ms['K'], rng)[:steps]
-                self.last_margin_softmax['batches'].append(batches)
-                losses = []
-                sums = torch.zeros(3, dtype=torch.float64, device=m.dev)      # labelled rows, hits, sum of cos_t
-                feed = inputs.crop_batches([[labels[r] for r in b] for b in batches])
-                for b, x in zip(batches, feed):
-                    lab = torch.from_numpy(codes[b]).to(m.dev)
-                    loss = m.train_on_classified_batch(x, lab, ms['kind'], ms['scale'], ms['margin'], h['lr'], h['beta_1'], h['beta_2'],
-                                                       h.get('decay', 0.0))
-                    losses.append(loss.clone())
-                    sel = m.class_selection
-                    known = lab >= 0
-                    sums += torch.stack([known.sum().double(), ((sel['pred'] == lab) & known).sum().double(),
-                                         torch.where(known, sel['cos_t'], torch.zeros_like(sel['cos_t'])).sum()])
-                n, hits, cs = (float(v) for v in sums.cpu())
-                mean = float(torch.cat(losses).double().mean().cpu()) if losses else float('nan')
-                acc, ct = (hits / n, cs / n) if n else (float('nan'), float('nan'))
-                self.last_margin_softmax.update(accuracy=acc, cos_t=ct)
-                print('Epoch %d/%d - loss: %.4f - margin softmax (%s) accuracy: %.4f, target cosine: %.4f'
-                      % (e + 1, epochs, mean, ms['kind'], acc, ct))
-        finally:
-            inputs.close()
+        last = self.last_margin_softmax = dict(batches=[], classes=C, accuracy=None, cos_t=None)
+        sums = torch.zeros(3, dtype=torch.float64, device=m.dev)      # this epoch's labelled rows, hits, sum of cos_t
+
+        def step(x, row_codes):
+            lab = torch.from_numpy(row_codes).to(m.dev)
+            loss = m.train_on_classified_batch(x, lab, ms['kind'], ms['scale'], ms['margin'], h['lr'], h['beta_1'], h['beta_2'],
+                                               h.get('decay', 0.0))
+            sel = m.class_selection
+            known = lab >= 0
+            sums.add_(torch.stack([known.sum().double(), ((sel['pred'] == lab) & known).sum().double(),
+                                   torch.where(known, sel['cos_t'], torch.zeros_like(sel['cos_t'])).sum()]))
+            return loss
+
+        def report(e, mean):
+            n, hits, cs = (float(v) for v in sums.cpu())
+            sums.zero_()
+            acc, ct = (hits / n, cs / n) if n else (float('nan'), float('nan'))
+            last.update(accuracy=acc, cos_t=ct)
+            print('Epoch %d/%d - loss: %.4f - margin softmax (%s) accuracy: %.4f, target cosine: %.4f' % (e + 1, epochs, mean, ms['kind'], acc, ct))
+        self._train_labelled(tr_gen, ms['P'], ms['K'], ms['pk_seed'], steps, epochs, last['batches'], m._cls_workspace, step, report)
         write_hdf5(self.CLASSES_PATH, {'/class_kernel': m.class_kernel.cpu().numpy(), '/subject_ids': subjects})
 
     def _saved_classes(self, subjects):

@@ -160,15 +160,16 @@ class Model(object):
         self._bucket_cb = BUCKET_FN(cb)
         return self._bucket_cb, errors
 
-    def _train_call(self, name, *args, errors=()):
+    def _train_call(self, name, *args, errors=(), bn_updates=None):
         """lib().name(handle, params, state, *args) with the zero-debias step of this call set before it; bn_updates advances by
-        BN_UPDATES_PER_STEP.  Returns the loss, a 1-element CUDA tensor (no host sync)."""
+        BN_UPDATES_PER_STEP (bn_updates: by that many instead -- a step over fewer towers).  Returns the loss, a 1-element CUDA
+        tensor (no host sync)."""
         self.ctx.set_bn_zero_debias_step(self.bn_updates + 1 if self.bn_zero_debias else 0)
         rc = getattr(lib(), name)(self.ctx.handle, ptr(self.params), ptr(self.state), *args)
         self.ctx.check(rc, name)
         if errors:
             raise errors[0]
-        self.bn_updates += self.BN_UPDATES_PER_STEP
+        self.bn_updates += self.BN_UPDATES_PER_STEP if bn_updates is None else bn_updates
         return self._loss
 
     def adam_step(self, lr, beta_1, beta_2, decay=0.0, eps=1e-7):

@@ -116,6 +116,21 @@ def test_header_binding_and_modes_agree():
     assert 0 < L.fv_fid_batch_workspace_bytes(2, 64) < L.fv_fid_batch_workspace_bytes(6, 64) < L.fv_fid_batch_workspace_bytes(1024, 64)
 
 
+def test_the_training_workspaces_keep_their_sizes():
+    """The three training steps carve one workspace layout (1 or 3 tower plans, then the dense rows); the sizes are those the
+    three separate layouts had before they were merged, read from that build."""
+    from face_vijnana_yolov3_amd._lib import lib
+    L = lib()
+    assert [L.fv_fid_workspace_bytes(B, S, 1) for B, S in ((1, 32), (2, 64), (3, 96))] == [193323776, 236910080, 355215872]
+    assert L.fv_fid_workspace_bytes(3, 64, 0) == 10891264
+    assert [L.fv_fid_batch_workspace_bytes(M, S) for M, S in ((1, 32), (4, 64), (6, 64), (1024, 64))] == \
+        [173359360, 204493568, 221099008, 8697090304]
+    for (M, C, S), want in (((4, 3, 64), 204496128), ((6, 1000, 64), 221159680)):
+        assert L.fv_fid_cls_workspace_bytes(M, C, S) == want
+        # one tower's workspace rounded up to 256 bytes, then the loss's region
+        assert want == (L.fv_fid_batch_workspace_bytes(M, S) + 255) // 256 * 256 + L.fv_fid_margin_workspace_bytes(M, C)
+
+
 # ----------------------------------------------------------------------------- 3. the PK sampler
 CODES = np.asarray([0, 0, 0, 1, 1, -1, 2, 3, 3, 3, 3, 3, -1, 4, 4, 5, 5, 5, 6, 6], np.int32)     # 2: a single row; -1: unknown
 
