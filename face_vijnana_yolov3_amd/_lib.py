@@ -312,3 +312,10 @@ def ptr(t):
     """Raw device pointer of a contiguous torch tensor."""
     assert t.is_contiguous()
     return c_void_p(t.data_ptr())
+
+
+def packed_args(dbuf, offsets, hw):
+    """A packed batch -- device uint8 buffer, the images' byte offsets, [h0, w0, h1, w1, ...] -- as the four arguments every entry
+    that reads one takes after the context: (packed, offsets, hw, n)."""
+    n = len(offsets)
+    return ptr(dbuf), (ctypes.c_int64 * n)(*offsets), (ctypes.c_int32 * (2 * n))(*hw), n

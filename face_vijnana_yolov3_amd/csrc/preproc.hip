@@ -20,117 +20,83 @@ __device__ __forceinline__ void cubic_w(float t, float (&w)[4]) {
     w[3] = 1.f - w[0] - w[1] - w[2];
 }
 
-__global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* __restrict__ src, int h, int w, int S, int w_p,
-                                                        int h_p, int pad_t, int pad_l, float* __restrict__ dst) {
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= S || y >= S) return;
-    float r = 0.f, g = 0.f, b = 0.f;
-    const int xi = x - pad_l, yi = y - pad_t;
-    if (xi >= 0 && xi < w_p && yi >= 0 && yi < h_p) {
-        // source coordinates in double: at 1080p an fp32 coordinate already costs 5e-5 in the weights
-        const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
-        const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
-        const int sx = (int)floor(fx), sy = (int)floor(fy);
-        float wx[4], wy[4];
-        cubic_w((float)(fx - sx), wx);
-        cubic_w((float)(fy - sy), wy);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = min(max(sy - 1 + j, 0), h - 1);
-            float rr = 0.f, gg = 0.f, bb = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int xx = min(max(sx - 1 + i, 0), w - 1);
-                const unsigned char* p = src + ((size_t)yy * w + xx) * 3;
-                rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
-            }
-            r += wy[j] * rr; g += wy[j] * gg; b += wy[j] * bb;
-        }
-        r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); b *= (1.0f / 255.0f);
-    }
-    float* o = dst + ((size_t)y * S + x) * 3;
-    o[0] = r; o[1] = g; o[2] = b;
+// ONE resampling serves every bicubic kernel of this file: lb_axis (an output index -> floor of its source coordinate and four
+// weights) and lb_pixel (sixteen taps -> r, g, b).  The kernels below differ only in where a pixel's source and placement come from
+// and in how the finished pixels reach memory, so their bits agree by construction (tests/test_letterbox_bits_gpu.py pins them to
+// an independent float32 restatement).
+struct LbAxis { int s; float w[4]; };
+
+__device__ __forceinline__ LbAxis lb_axis(int i, int n_src, int n_dst) {
+    // source coordinates in double: at 1080p an fp32 coordinate already costs 5e-5 in the weights
+    const double f = (i + 0.5) * ((double)n_src / (double)n_dst) - 0.5;
+    LbAxis a;
+    a.s = (int)floor(f);
+    cubic_w((float)(f - a.s), a.w);
+    return a;
 }
 
-// the same for a whole batch in ONE launch: blockIdx.z = image; the images' bytes sit back to back in one
-// buffer (one host-to-device copy per batch), their geometry comes in the kernel arguments
-constexpr int LB_MAX = 64;
-struct LbTable { long long off[LB_MAX]; int h[LB_MAX], w[LB_MAX], w_p[LB_MAX], h_p[LB_MAX], pad_t[LB_MAX], pad_l[LB_MAX]; };
-
-__global__ __launch_bounds__(256) void letterbox_batch_kernel(const unsigned char* __restrict__ packed, LbTable t, int S,
-                                                              float* __restrict__ dst) {
-    const int b = blockIdx.z;
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= S || y >= S) return;
-    const unsigned char* __restrict__ src = packed + t.off[b];
-    const int h = t.h[b], w = t.w[b], w_p = t.w_p[b], h_p = t.h_p[b];
-    float r = 0.f, g = 0.f, bl = 0.f;
-    const int xi = x - t.pad_l[b], yi = y - t.pad_t[b];
-    if (xi >= 0 && xi < w_p && yi >= 0 && yi < h_p) {
-        const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
-        const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
-        const int sx = (int)floor(fx), sy = (int)floor(fy);
-        float wx[4], wy[4];
-        cubic_w((float)(fx - sx), wx);
-        cubic_w((float)(fy - sy), wy);
+// the pixel at (sx, sy) of the h x w source at `src` (`pitch` bytes per row), the border replicated at ITS edges (what cv.resize sees
+// after the reference's slice).  WIDE: where the four taps of a row are 12 contiguous bytes (an interior column) they come from one
+// (unaligned) 12-byte load instead of twelve byte loads; the values, and the arithmetic on them, are the same.
+template <bool WIDE>
+__device__ __forceinline__ void lb_pixel(const unsigned char* __restrict__ src, int pitch, int h, int w, int sx, const float (&wx)[4],
+                                         int sy, const float (&wy)[4], float& r, float& g, float& b) {
+    int xo[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = min(max(sy - 1 + j, 0), h - 1);
-            float rr = 0.f, gg = 0.f, bb = 0.f;
+    for (int i = 0; i < 4; ++i) xo[i] = min(max(sx - 1 + i, 0), w - 1) * 3;
+    const bool inner = WIDE && sx >= 1 && sx + 2 <= w - 1;
+    r = 0.f; g = 0.f; b = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int yy = min(max(sy - 1 + j, 0), h - 1);
+        const unsigned char* __restrict__ row = src + (size_t)yy * pitch;
+        float rr = 0.f, gg = 0.f, bb = 0.f;
+        if (inner) {
+            unsigned v[3];
+            __builtin_memcpy(v, row + xo[0], 12);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int xx = min(max(sx - 1 + i, 0), w - 1);
-                const unsigned char* p = src + ((size_t)yy * w + xx) * 3;
+                const float p0 = (float)((v[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u);
+                const float p1 = (float)((v[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u);
+                const float p2 = (float)((v[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u);
+                rr += wx[i] * p0; gg += wx[i] * p1; bb += wx[i] * p2;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned char* p = row + xo[i];
                 rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
             }
-            r += wy[j] * rr; g += wy[j] * gg; bl += wy[j] * bb;
         }
-        r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); bl *= (1.0f / 255.0f);
+        r += wy[j] * rr; g += wy[j] * gg; b += wy[j] * bb;
     }
-    float* o = dst + (((size_t)b * S + y) * S + x) * 3;
-    o[0] = r; o[1] = g; o[2] = bl;
+    r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); b *= (1.0f / 255.0f);
 }
 
-// many crops (sub-rectangles of the packed images) in one launch: blockIdx.z = crop.  Crop c starts at byte t.off[c] of `packed`
-// (its image's offset plus its top-left pixel) and advances t.pitch[c] bytes per row; everything else is letterbox_kernel for a
-// contiguous h x w image -- the same expressions in the same order, the border replicated at the CROP's edges (what cv.resize
-// sees after the reference's slice), so the pixels are bit-identical to fv_letterbox of a contiguous copy of the crop.
-constexpr int LBC_MAX = 64;    // crops per launch: the table travels in the kernel arguments (64 x 36 B); longer lists are chunked
-struct LbcTable { long long off[LBC_MAX]; int pitch[LBC_MAX], h[LBC_MAX], w[LBC_MAX], w_p[LBC_MAX], h_p[LBC_MAX], pad_t[LBC_MAX],
-                  pad_l[LBC_MAX]; };
+// A source: the h x w rectangle that starts at byte `off` of the packed buffer (its image's offset plus its top-left pixel; a whole
+// image is the crop with pitch = 3 w at its offset) and advances `pitch` bytes per row, resized to w_p x h_p.  Every table is made of
+// these; the tables travel in the kernel arguments (no device allocation, no host-to-device copy of a pageable table, nothing that
+// has to outlive the call), so longer lists are chunked.
+struct LbSrc { long long off; int pitch, h, w, w_p, h_p; };
 
-__global__ __launch_bounds__(256) void letterbox_crops_kernel(const unsigned char* __restrict__ packed, LbcTable t, int S,
-                                                              float* __restrict__ dst) {
+// fv_letterbox, fv_letterbox_batch and fv_letterbox_crops: blockIdx.z = entry, one thread per output pixel, any S.  N = the table's
+// capacity: LB_MAX for the lists, 1 for fv_letterbox (back-to-back one-image calls are bound by the launch, and 2.5 KB of kernel
+// arguments made one 0.6 us longer than 40 B do).
+constexpr int LB_MAX = 64;          // entries per launch (64 x 40 B of kernel arguments)
+template <int N> struct LbTable { LbSrc src[N]; int pad_t[N], pad_l[N]; };
+
+template <int N>
+__global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* __restrict__ packed, LbTable<N> t, int S, float* __restrict__ dst) {
     const int c = blockIdx.z;
     const int x = blockIdx.x * 16 + (threadIdx.x & 15);
     const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= S || y >= S) return;
-    const unsigned char* __restrict__ src = packed + t.off[c];
-    const int h = t.h[c], w = t.w[c], w_p = t.w_p[c], h_p = t.h_p[c], pitch = t.pitch[c];
+    const LbSrc s = t.src[c];
     float r = 0.f, g = 0.f, b = 0.f;
     const int xi = x - t.pad_l[c], yi = y - t.pad_t[c];
-    if (xi >= 0 && xi < w_p && yi >= 0 && yi < h_p) {
-        const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
-        const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
-        const int sx = (int)floor(fx), sy = (int)floor(fy);
-        float wx[4], wy[4];
-        cubic_w((float)(fx - sx), wx);
-        cubic_w((float)(fy - sy), wy);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int yy = min(max(sy - 1 + j, 0), h - 1);
-            float rr = 0.f, gg = 0.f, bb = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int xx = min(max(sx - 1 + i, 0), w - 1);
-                const unsigned char* p = src + (size_t)yy * pitch + (size_t)xx * 3;
-                rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
-            }
-            r += wy[j] * rr; g += wy[j] * gg; b += wy[j] * bb;
-        }
-        r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); b *= (1.0f / 255.0f);
+    if (xi >= 0 && xi < s.w_p && yi >= 0 && yi < s.h_p) {
+        const LbAxis ax = lb_axis(xi, s.w, s.w_p), ay = lb_axis(yi, s.h, s.h_p);
+        lb_pixel<false>(packed + s.off, s.pitch, s.h, s.w, ax.s, ax.w, ay.s, ay.w, r, g, b);
     }
     float* o = dst + (((size_t)c * S + y) * S + x) * 3;
     o[0] = r; o[1] = g; o[2] = b;
@@ -147,11 +113,12 @@ constexpr int CNU_ITERS = 4;                          // chunks per thread: the 
 constexpr int CNU_CHUNKS = CNU_THREADS * CNU_ITERS;
 constexpr int CNU_MAX_S = 4096;                       // 3S int32 of LDS <= 48 KiB
 
-__global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsigned char* __restrict__ packed, LbcTable t, int S,
+__global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsigned char* __restrict__ packed, LbTable<LB_MAX> t, int S,
                                                                       unsigned char* __restrict__ dst) {
     extern __shared__ __attribute__((aligned(16))) int cnu_src[];      // [3S]: source byte offset inside a row of output byte b, or -1
     const int c = blockIdx.y;
-    const int h = t.h[c], w = t.w[c], w_p = t.w_p[c], h_p = t.h_p[c], pitch = t.pitch[c], pad_t = t.pad_t[c], pad_l = t.pad_l[c];
+    const LbSrc s = t.src[c];
+    const int h = s.h, w = s.w, w_p = s.w_p, h_p = s.h_p, pitch = s.pitch, pad_t = t.pad_t[c], pad_l = t.pad_l[c];
     const double ifx = 1.0 / ((double)w_p / (double)w), ify = 1.0 / ((double)h_p / (double)h);
     for (int x = threadIdx.x; x < S; x += CNU_THREADS) {
         const int xi = x - pad_l;
@@ -160,7 +127,7 @@ __global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsi
         cnu_src[3 * x] = o; cnu_src[3 * x + 1] = o < 0 ? -1 : o + 1; cnu_src[3 * x + 2] = o < 0 ? -1 : o + 2;
     }
     __syncthreads();
-    const unsigned char* __restrict__ src = packed + t.off[c];
+    const unsigned char* __restrict__ src = packed + s.off;
     const int row_chunks = 3 * S / 16, n_chunks = S * row_chunks;
     uint4* __restrict__ out = reinterpret_cast<uint4*>(dst + (size_t)c * S * S * 3);
 #pragma unroll
@@ -185,19 +152,22 @@ __global__ __launch_bounds__(CNU_THREADS) void crop_nearest_u8_kernel(const unsi
     }
 }
 
-// Training augmentation (hps['augment']): letterbox_crops_kernel for ONE crop per image, letterboxed into a T x T box
-// at (oy, ox) of the otherwise zero S x S canvas, the finished canvas optionally mirrored (x -> S - 1 - x) and the pixel's colour
-// distorted in HSV, in the same pass.  The resampling is letterbox_crops_kernel's -- the same expressions in the same order -- so
-// without colour the box holds that kernel's bits.  A workgroup makes LBA_TW x LBA_TH output pixels: the fp64 source coordinate and
-// the four weights of each of its columns and rows are computed once (80 threads) into LDS; then every thread makes four pixels
-// of one column (64 columns x 4 rows per pass, the passes unrolled so that their loads are in flight together), the tile is staged
-// in LDS and stored as 16-byte chunks on consecutive lanes (768 B per row segment).
-constexpr int LBA_MAX = 64;         // images per launch: the table travels in the kernel arguments (64 x 52 B); longer batches are chunked
-constexpr int LBA_TW = 64, LBA_TH = 16, LBA_ROWS = 4;       // tile; rows per pass (256 threads = 64 columns x 4 rows)
-constexpr int LBA_OUT = -2147483647 - 1;  // a column / row outside the placed content
-struct LbaTable { long long off[LBA_MAX]; int pitch[LBA_MAX], h[LBA_MAX], w[LBA_MAX], w_p[LBA_MAX], h_p[LBA_MAX], top[LBA_MAX],
-                  left[LBA_MAX], mode[LBA_MAX];     // mode: bit 0 = flip, bit 1 = the colour stage runs
-                  float dh[LBA_MAX], sat[LBA_MAX], ex[LBA_MAX]; };
+// The tile stage of the training augmentations (hps['augment']; hps['mosaic']).  A TILE is a source
+// letterboxed into a T x T box at (oy, ox) of the S x S canvas -- the box may reach beyond the canvas -- optionally mirrored in place
+// (local column c -> T - 1 - c), its colour optionally distorted in HSV, all in the pass that resamples it.  The resampling is
+// lb_axis / lb_pixel, so without colour a tile holds letterbox_kernel's bits at image size T.  A workgroup makes LBT_W x LBT_H
+// canvas pixels: the fp64 source coordinate and the four weights of each of its columns and rows are computed once (80 threads)
+// into LDS; then every thread makes four pixels of one column (64 columns x 4 rows per pass, the passes unrolled so that their loads
+// are in flight together); the rectangle is staged in LDS and stored as 16-byte chunks on consecutive lanes (768 B per row segment).
+constexpr int LBT_W = 64, LBT_H = 16, LBT_ROWS = 4;         // the rectangle; rows per pass (256 threads = 64 columns x 4 rows)
+constexpr int LBT_OUT = -2147483647 - 1;                    // a column / row outside the tile's window or content
+struct LbPlace { int top,           // canvas row of the content's first row
+                     xa,            // content column xi of canvas column x: x - xa, under a flip xa - x
+                     mode;          // bit 0 = flip, bit 1 = the colour stage runs
+                 float dh, sat, ex; };
+struct LbTile { int s[LBT_W + LBT_H];                                    // floor of the source coordinate of the rectangle's columns,
+                __attribute__((aligned(16))) float w[LBT_W + LBT_H][4];  // then rows, or LBT_OUT; their weights
+                __attribute__((aligned(16))) float out[LBT_H][LBT_W * 3]; };
 
 // Darknet's distort_image in float32: clamp, RGB -> HSV (h in turns), h += dh (wrapped), s *= sat, v *= ex, HSV -> RGB, clamp
 __device__ __forceinline__ void lba_colour(float& r, float& g, float& b, float dh, float sat, float ex) {
@@ -223,222 +193,104 @@ __device__ __forceinline__ void lba_colour(float& r, float& g, float& b, float d
     r = fminf(fmaxf(r, 0.f), 1.f); g = fminf(fmaxf(g, 0.f), 1.f); b = fminf(fmaxf(b, 0.f), 1.f);
 }
 
-__global__ __launch_bounds__(256) void letterbox_augment_kernel(const unsigned char* __restrict__ packed, LbaTable t, int S,
-                                                                float* __restrict__ dst) {
-    __shared__ int col_s[LBA_TW], row_s[LBA_TH];                                  // floor of the source coordinate, or LBA_OUT
-    __shared__ __attribute__((aligned(16))) float col_w[LBA_TW][4], row_w[LBA_TH][4];
-    __shared__ __attribute__((aligned(16))) float out_s[LBA_TH][LBA_TW * 3];
-    const int b = blockIdx.z, x0 = blockIdx.x * LBA_TW, y0 = blockIdx.y * LBA_TH, tid = threadIdx.x;
-    const int h = t.h[b], w = t.w[b], w_p = t.w_p[b], h_p = t.h_p[b], pitch = t.pitch[b], mode = t.mode[b];
-    if (tid < LBA_TW) {
-        const int x = x0 + tid;
-        const int xi = ((mode & 1) ? S - 1 - x : x) - t.left[b];                  // undo the flip, then the placement
-        int s = LBA_OUT;
-        float wx[4] = {0.f, 0.f, 0.f, 0.f};
-        if (x < S && xi >= 0 && xi < w_p) {
-            const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
-            s = (int)floor(fx);
-            cubic_w((float)(fx - s), wx);
-        }
-        col_s[tid] = s;
+// the tables of the rectangle at (x0, y0) for one tile seen through the window [wy0, wy1) x [wx0, wx1) of the canvas
+__device__ __forceinline__ void lbt_tables(LbTile& l, const LbSrc& s, const LbPlace& p, int x0, int y0, int wy0, int wx0, int wy1, int wx1) {
+    const int tid = threadIdx.x;
+    if (tid >= LBT_W + LBT_H) return;
+    const bool col = tid < LBT_W;
+    const int at = col ? x0 + tid : y0 + tid - LBT_W;                            // canvas column / row
+    const int i = col ? ((p.mode & 1) ? p.xa - at : at - p.xa) : at - p.top;     // undo the placement and the in-box flip
+    const int n_src = col ? s.w : s.h, n_dst = col ? s.w_p : s.h_p;
+    LbAxis a = {LBT_OUT, {0.f, 0.f, 0.f, 0.f}};
+    if (at >= (col ? wx0 : wy0) && at < (col ? wx1 : wy1) && i >= 0 && i < n_dst) a = lb_axis(i, n_src, n_dst);
+    l.s[tid] = a.s;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) col_w[tid][i] = wx[i];
-    } else if (tid < LBA_TW + LBA_TH) {
-        const int j = tid - LBA_TW, y = y0 + j;
-        const int yi = y - t.top[b];
-        int s = LBA_OUT;
-        float wy[4] = {0.f, 0.f, 0.f, 0.f};
-        if (y < S && yi >= 0 && yi < h_p) {
-            const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
-            s = (int)floor(fy);
-            cubic_w((float)(fy - s), wy);
-        }
-        row_s[j] = s;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) row_w[j][i] = wy[i];
-    }
-    __syncthreads();
-    const unsigned char* __restrict__ src = packed + t.off[b];
-    const int lx = tid & (LBA_TW - 1), ly = tid >> 6;
-    const int sx = col_s[lx];
-    const float4 wxv = *reinterpret_cast<const float4*>(col_w[lx]);
+    for (int k = 0; k < 4; ++k) l.w[tid][k] = a.w[k];
+}
+
+// a thread's four pixels of the rectangle into the stage.  FILL: a pixel outside the tile is written as +0 (the tile is the only
+// one of its canvas); otherwise it is left as it is (zeroed before, or another tile's).
+template <bool FILL>
+__device__ __forceinline__ void lbt_pixels(LbTile& l, const unsigned char* __restrict__ src, const LbSrc& s, const LbPlace& p) {
+    const int lx = threadIdx.x & (LBT_W - 1), ly = threadIdx.x >> 6;
+    const int sx = l.s[lx];
+    const float4 wxv = *reinterpret_cast<const float4*>(l.w[lx]);
     const float wx[4] = {wxv.x, wxv.y, wxv.z, wxv.w};
-    int xo[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) xo[i] = sx == LBA_OUT ? 0 : min(max(sx - 1 + i, 0), w - 1) * 3;
-    // interior columns: the four taps are 12 contiguous bytes of a source row -- one (unaligned) 12-byte load per tap row instead of
-    // twelve byte loads; the values, and the arithmetic on them, are the same
-    const bool inner = sx != LBA_OUT && sx >= 1 && sx + 2 <= w - 1;
-    const float dh = t.dh[b], sat = t.sat[b], ex = t.ex[b];
-#pragma unroll
-    for (int pass = 0; pass < LBA_TH / LBA_ROWS; ++pass) {
-        const int j0 = pass * LBA_ROWS + ly;
-        const int sy = row_s[j0];
-        float r = 0.f, g = 0.f, bl = 0.f;
-        if (sx != LBA_OUT && sy != LBA_OUT) {
-            const float4 wyv = *reinterpret_cast<const float4*>(row_w[j0]);
+    for (int pass = 0; pass < LBT_H / LBT_ROWS; ++pass) {
+        const int j0 = pass * LBT_ROWS + ly;
+        const int sy = l.s[LBT_W + j0];
+        const bool in = sx != LBT_OUT && sy != LBT_OUT;
+        float r = 0.f, g = 0.f, b = 0.f;
+        if (in) {
+            const float4 wyv = *reinterpret_cast<const float4*>(l.w[LBT_W + j0]);
             const float wy[4] = {wyv.x, wyv.y, wyv.z, wyv.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int yy = min(max(sy - 1 + j, 0), h - 1);
-                const unsigned char* __restrict__ row = src + (size_t)yy * pitch;
-                float rr = 0.f, gg = 0.f, bb = 0.f;
-                if (inner) {
-                    unsigned v[3];
-                    __builtin_memcpy(v, row + xo[0], 12);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float p0 = (float)((v[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u);
-                        const float p1 = (float)((v[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u);
-                        const float p2 = (float)((v[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u);
-                        rr += wx[i] * p0; gg += wx[i] * p1; bb += wx[i] * p2;
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const unsigned char* p = row + xo[i];
-                        rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
-                    }
-                }
-                r += wy[j] * rr; g += wy[j] * gg; bl += wy[j] * bb;
-            }
-            r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); bl *= (1.0f / 255.0f);
-            if (mode & 2) lba_colour(r, g, bl, dh, sat, ex);
+            lb_pixel<true>(src, s.pitch, s.h, s.w, sx, wx, sy, wy, r, g, b);
+            if (p.mode & 2) lba_colour(r, g, b, p.dh, p.sat, p.ex);
         }
-        out_s[j0][3 * lx] = r; out_s[j0][3 * lx + 1] = g; out_s[j0][3 * lx + 2] = bl;
-    }
-    __syncthreads();
-    // the tile as 16-byte chunks, consecutive lanes on consecutive chunks of a row segment (768 B where the tile is full)
-    constexpr int ROW_Q = LBA_TW * 3 / 4;
-    const int row_q = 3 * min(LBA_TW, S - x0) / 4;                                 // chunks of this tile's row segment (S % 4 == 0)
-#pragma unroll
-    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) {
-        const int rr = q / ROW_Q, k = q - rr * ROW_Q;
-        const int y = y0 + rr;
-        if (y < S && k < row_q)
-            reinterpret_cast<float4*>(dst + (((size_t)b * S + y) * S + x0) * 3)[k] = reinterpret_cast<const float4*>(out_s[rr])[k];
+        if (FILL || in) { l.out[j0][3 * lx] = r; l.out[j0][3 * lx + 1] = g; l.out[j0][3 * lx + 2] = b; }
     }
 }
 
-// Mosaic (hps['mosaic']): a canvas is made of up to four TILES.  A tile is letterbox_augment_kernel's placed crop -- the
-// ch x cw crop letterboxed into a T x T box at (oy, ox), which may reach beyond the canvas -- seen through a WINDOW [wy0, wy1) x
-// [wx0, wx1) of the canvas; a tile's flip mirrors its box in place (local column c -> T - 1 - c).  The windows of a canvas are
-// disjoint; a pixel outside every window, or inside a window but outside the tile's content, is +0.  A workgroup makes the same
-// 64 x 16 output pixels as letterbox_augment_kernel: it zero-fills its LDS stage, then for every tile of its canvas whose window
-// meets its rectangle (a workgroup-uniform test: most workgroups meet one tile, those on a seam two, the one on the centre four)
-// builds the column / row tables and evaluates the taps -- letterbox_augment_kernel's expressions in the same order, so a tile
-// holds letterbox_crops_kernel's bits at image size T -- writing the lanes inside window and content; one barrier, then the same
-// 16-byte row-segment stores.  The tile table travels in the kernel arguments, MOS_TILES tiles (whole canvases) per launch.
-constexpr int MOS_TILES = 48;       // tiles per launch (48 x 68 B of kernel arguments); MOS_PER = tiles per canvas at most
+// the stage as 16-byte chunks, consecutive lanes on consecutive chunks of a row segment (768 B where the rectangle is full)
+__device__ __forceinline__ void lbt_store(const LbTile& l, float* __restrict__ canvas, int S, int x0, int y0) {
+    constexpr int ROW_Q = LBT_W * 3 / 4;
+    const int row_q = 3 * min(LBT_W, S - x0) / 4;                                  // chunks of this rectangle's row segment (S % 4 == 0)
+#pragma unroll
+    for (int q = threadIdx.x; q < LBT_H * ROW_Q; q += 256) {
+        const int rr = q / ROW_Q, k = q - rr * ROW_Q;
+        const int y = y0 + rr;
+        if (y < S && k < row_q)
+            reinterpret_cast<float4*>(canvas + ((size_t)y * S + x0) * 3)[k] = reinterpret_cast<const float4*>(l.out[rr])[k];
+    }
+}
+
+// fv_letterbox_augment_batch: ONE tile per canvas, inside it, seen through the whole canvas; blockIdx.z = canvas
+constexpr int LBA_MAX = 64;         // canvases per launch (64 x 56 B of kernel arguments)
+struct LbaTable { LbSrc src[LBA_MAX]; LbPlace place[LBA_MAX]; };
+
+__global__ __launch_bounds__(256) void letterbox_augment_kernel(const unsigned char* __restrict__ packed, LbaTable t, int S,
+                                                                float* __restrict__ dst) {
+    __shared__ LbTile l;
+    const int b = blockIdx.z, x0 = blockIdx.x * LBT_W, y0 = blockIdx.y * LBT_H;
+    const LbSrc s = t.src[b];
+    const LbPlace p = t.place[b];
+    lbt_tables(l, s, p, x0, y0, 0, 0, S, S);
+    __syncthreads();
+    lbt_pixels<true>(l, packed + s.off, s, p);
+    __syncthreads();
+    lbt_store(l, dst + (size_t)b * S * S * 3, S, x0, y0);
+}
+
+// fv_letterbox_mosaic_batch: a canvas is made of up to MOS_PER tiles with disjoint windows; a pixel outside every window, or inside a
+// window but outside the tile's content, is +0.  A workgroup zero-fills its stage, then runs the tile stage for every tile of its
+// canvas whose window meets its rectangle (a workgroup-uniform test: most workgroups meet one tile, those on a seam two, the one on
+// the centre four).  This form measured 5 % slower on one-tile canvases than the kernel above, so both stay.
+constexpr int MOS_TILES = 48;       // tiles (whole canvases) per launch (48 x 72 B of kernel arguments); MOS_PER = tiles per canvas at most
 constexpr int MOS_PER = 4;
-struct MosTable { long long off[MOS_TILES]; int pitch[MOS_TILES], h[MOS_TILES], w[MOS_TILES], w_p[MOS_TILES], h_p[MOS_TILES],
-                  top[MOS_TILES],          // canvas row of the content's first row
-                  xa[MOS_TILES],           // content column xi of canvas column x: x - xa, under a flip xa - x
-                  mode[MOS_TILES],         // bit 0 = flip, bit 1 = the colour stage runs
-                  wy0[MOS_TILES], wx0[MOS_TILES], wy1[MOS_TILES], wx1[MOS_TILES];
-                  float dh[MOS_TILES], sat[MOS_TILES], ex[MOS_TILES];
+struct MosTable { LbSrc src[MOS_TILES]; LbPlace place[MOS_TILES];
+                  int win[MOS_TILES][4];                    // wy0, wx0, wy1, wx1
                   unsigned char first[MOS_TILES + 1]; };    // canvas z of the launch owns the tiles [first[z], first[z + 1])
 
 __global__ __launch_bounds__(256) void letterbox_mosaic_kernel(const unsigned char* __restrict__ packed, MosTable t, int S,
                                                                float* __restrict__ dst) {
-    __shared__ int col_s[LBA_TW], row_s[LBA_TH];                                  // floor of the source coordinate, or LBA_OUT
-    __shared__ __attribute__((aligned(16))) float col_w[LBA_TW][4], row_w[LBA_TH][4];
-    __shared__ __attribute__((aligned(16))) float out_s[LBA_TH][LBA_TW * 3];
-    const int b = blockIdx.z, x0 = blockIdx.x * LBA_TW, y0 = blockIdx.y * LBA_TH, tid = threadIdx.x;
-    constexpr int ROW_Q = LBA_TW * 3 / 4;
+    __shared__ LbTile l;
+    const int b = blockIdx.z, x0 = blockIdx.x * LBT_W, y0 = blockIdx.y * LBT_H;
 #pragma unroll
-    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) reinterpret_cast<float4*>(&out_s[0][0])[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int lx = tid & (LBA_TW - 1), ly = tid >> 6;
+    for (int q = threadIdx.x; q < LBT_H * LBT_W * 3 / 4; q += 256) reinterpret_cast<float4*>(&l.out[0][0])[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     const int k1 = t.first[b + 1];
     for (int k = t.first[b]; k < k1; ++k) {
-        const int wy0 = t.wy0[k], wx0 = t.wx0[k], wy1 = t.wy1[k], wx1 = t.wx1[k];
-        if (wx1 <= x0 || wx0 >= x0 + LBA_TW || wy1 <= y0 || wy0 >= y0 + LBA_TH) continue;    // the same in every lane of the workgroup
-        const int h = t.h[k], w = t.w[k], w_p = t.w_p[k], h_p = t.h_p[k], pitch = t.pitch[k], mode = t.mode[k];
+        const int wy0 = t.win[k][0], wx0 = t.win[k][1], wy1 = t.win[k][2], wx1 = t.win[k][3];
+        if (wx1 <= x0 || wx0 >= x0 + LBT_W || wy1 <= y0 || wy0 >= y0 + LBT_H) continue;    // the same in every lane of the workgroup
+        const LbSrc s = t.src[k];
+        const LbPlace p = t.place[k];
         __syncthreads();                                                          // the tables of the tile before are read; the stage is zeroed
-        if (tid < LBA_TW) {
-            const int x = x0 + tid;
-            const int xi = (mode & 1) ? t.xa[k] - x : x - t.xa[k];                // undo the window's placement and the in-box flip
-            int s = LBA_OUT;
-            float wx[4] = {0.f, 0.f, 0.f, 0.f};
-            if (x >= wx0 && x < wx1 && xi >= 0 && xi < w_p) {
-                const double fx = (xi + 0.5) * ((double)w / (double)w_p) - 0.5;
-                s = (int)floor(fx);
-                cubic_w((float)(fx - s), wx);
-            }
-            col_s[tid] = s;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) col_w[tid][i] = wx[i];
-        } else if (tid < LBA_TW + LBA_TH) {
-            const int j = tid - LBA_TW, y = y0 + j;
-            const int yi = y - t.top[k];
-            int s = LBA_OUT;
-            float wy[4] = {0.f, 0.f, 0.f, 0.f};
-            if (y >= wy0 && y < wy1 && yi >= 0 && yi < h_p) {
-                const double fy = (yi + 0.5) * ((double)h / (double)h_p) - 0.5;
-                s = (int)floor(fy);
-                cubic_w((float)(fy - s), wy);
-            }
-            row_s[j] = s;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) row_w[j][i] = wy[i];
-        }
+        lbt_tables(l, s, p, x0, y0, wy0, wx0, wy1, wx1);
         __syncthreads();
-        const unsigned char* __restrict__ src = packed + t.off[k];
-        const int sx = col_s[lx];
-        const float4 wxv = *reinterpret_cast<const float4*>(col_w[lx]);
-        const float wx[4] = {wxv.x, wxv.y, wxv.z, wxv.w};
-        int xo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xo[i] = sx == LBA_OUT ? 0 : min(max(sx - 1 + i, 0), w - 1) * 3;
-        const bool inner = sx != LBA_OUT && sx >= 1 && sx + 2 <= w - 1;           // the four taps are 12 contiguous bytes of a source row
-        const float dh = t.dh[k], sat = t.sat[k], ex = t.ex[k];
-#pragma unroll
-        for (int pass = 0; pass < LBA_TH / LBA_ROWS; ++pass) {
-            const int j0 = pass * LBA_ROWS + ly;
-            const int sy = row_s[j0];
-            if (sx != LBA_OUT && sy != LBA_OUT) {
-                float r = 0.f, g = 0.f, bl = 0.f;
-                const float4 wyv = *reinterpret_cast<const float4*>(row_w[j0]);
-                const float wy[4] = {wyv.x, wyv.y, wyv.z, wyv.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int yy = min(max(sy - 1 + j, 0), h - 1);
-                    const unsigned char* __restrict__ row = src + (size_t)yy * pitch;
-                    float rr = 0.f, gg = 0.f, bb = 0.f;
-                    if (inner) {
-                        unsigned v[3];
-                        __builtin_memcpy(v, row + xo[0], 12);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float p0 = (float)((v[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u);
-                            const float p1 = (float)((v[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u);
-                            const float p2 = (float)((v[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u);
-                            rr += wx[i] * p0; gg += wx[i] * p1; bb += wx[i] * p2;
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const unsigned char* p = row + xo[i];
-                            rr += wx[i] * (float)p[0]; gg += wx[i] * (float)p[1]; bb += wx[i] * (float)p[2];
-                        }
-                    }
-                    r += wy[j] * rr; g += wy[j] * gg; bl += wy[j] * bb;
-                }
-                r *= (1.0f / 255.0f); g *= (1.0f / 255.0f); bl *= (1.0f / 255.0f);
-                if (mode & 2) lba_colour(r, g, bl, dh, sat, ex);
-                out_s[j0][3 * lx] = r; out_s[j0][3 * lx + 1] = g; out_s[j0][3 * lx + 2] = bl;   // a thread's own pixel in every tile
-            }
-        }
+        lbt_pixels<false>(l, packed + s.off, s, p);                               // a thread's own pixel in every tile
     }
     __syncthreads();
-    const int row_q = 3 * min(LBA_TW, S - x0) / 4;                                 // chunks of this tile's row segment (S % 4 == 0)
-#pragma unroll
-    for (int q = tid; q < LBA_TH * ROW_Q; q += 256) {
-        const int rr = q / ROW_Q, kq = q - rr * ROW_Q;
-        const int y = y0 + rr;
-        if (y < S && kq < row_q)
-            reinterpret_cast<float4*>(dst + (((size_t)b * S + y) * S + x0) * 3)[kq] = reinterpret_cast<const float4*>(out_s[rr])[kq];
-    }
+    lbt_store(l, dst + (size_t)b * S * S * 3, S, x0, y0);
 }
 
 bool lb_geometry(int h, int w, int S, int* g) {
@@ -454,211 +306,117 @@ bool lb_geometry(int h, int w, int S, int* g) {
     return w_p >= 1 && h_p >= 1;
 }
 
-// every record of a crop list (image, y0, x0, h, w) inside its image and letterboxable: checked before anything is enqueued,
-// so a bad record leaves dst untouched
-int lbc_validate(fv_ctx* ctx, const char* who, const int64_t* offsets, const int32_t* hw, int n_img, const int32_t* crops, int n, int S) {
-    for (int c = 0; c < n; ++c) {
-        const int* r = crops + 5 * c;
-        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-        FV_REQUIRE(ctx, im >= 0 && im < n_img, "%s: crop %d names image %d of %d", who, c, im, n_img);
-        const int H = hw[2 * im], W = hw[2 * im + 1];
-        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "%s: bad image %d", who, im);
-        FV_REQUIRE(ctx, h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
-                   "%s: crop %d (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", who, c, y0, x0, h, w, im, H, W);
-        int g[6];
-        FV_REQUIRE(ctx, lb_geometry(h, w, S, g), "%s: crop %d (%d x %d) too elongated for image_size %d", who, c, h, w, S);
+// ---- the host's one path to a source record.  Every record of a call is checked before anything is enqueued, so a bad one
+// leaves dst untouched.
+
+// the h x w crop at (y0, x0) of image `im`, to be letterboxed into a side of T: the image exists, the crop lies inside it and its
+// letterbox has at least one row and one column.  `rec` k names the record in the messages ("crop 3", "tile 7", "image 0").
+int lb_src_check(fv_ctx* ctx, const char* who, const char* rec, int k, const int64_t* offsets, const int32_t* hw, int n_img, int im,
+                 int y0, int x0, int h, int w, int T) {
+    FV_REQUIRE(ctx, im >= 0 && im < n_img, "%s: %s %d names image %d of %d", who, rec, k, im, n_img);
+    const int H = hw[2 * im], W = hw[2 * im + 1];
+    FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "%s: bad image %d", who, im);
+    FV_REQUIRE(ctx, h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
+               "%s: %s %d (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", who, rec, k, y0, x0, h, w, im, H, W);
+    int g[6];
+    FV_REQUIRE(ctx, lb_geometry(h, w, T, g), "%s: %s %d (%d x %d) too elongated for a side of %d", who, rec, k, h, w, T);
+    return FV_OK;
+}
+
+// the checked record as the kernels' source and its letterbox geometry g[6] in T; -> its source bytes
+double lb_src_fill(LbSrc& s, int* g, const int64_t* offsets, const int32_t* hw, int im, int y0, int x0, int h, int w, int T) {
+    const int W = hw[2 * im + 1];
+    lb_geometry(h, w, T, g);
+    s.off = offsets[im] + ((long long)y0 * W + x0) * 3; s.pitch = W * 3;
+    s.h = h; s.w = w; s.w_p = g[0]; s.h_p = g[1];
+    return (double)h * w * 3;
+}
+
+// entry k of a list: the crop record (image, y0, x0, h, w) crops + 5 k, or without `crops` the whole image k
+struct LbRec { int im, y0, x0, h, w; };
+LbRec lb_rec(const int32_t* hw, const int32_t* crops, int k) {
+    if (crops) return {crops[5 * k], crops[5 * k + 1], crops[5 * k + 2], crops[5 * k + 3], crops[5 * k + 4]};
+    return {k, 0, 0, hw[2 * k], hw[2 * k + 1]};
+}
+
+int lb_list_check(fv_ctx* ctx, const char* who, const int64_t* offsets, const int32_t* hw, int n_img, const int32_t* crops, int n, int S) {
+    for (int k = 0; k < n; ++k) {
+        const LbRec r = lb_rec(hw, crops, k);
+        if (int rc = lb_src_check(ctx, who, crops ? "crop" : "image", k, offsets, hw, n_img, r.im, r.y0, r.x0, r.h, r.w, S)) return rc;
     }
     return FV_OK;
 }
 
-// crops [c0, c0 + nc) as the kernels' table; -> source bytes of those crops
-double lbc_fill(LbcTable& t, const int64_t* offsets, const int32_t* hw, const int32_t* crops, int c0, int nc, int S) {
+// entries [k0, k0 + nk) as a table (geom: their 6 geometry values each, or null); -> their source bytes
+template <int N>
+double lb_list_fill(LbTable<N>& t, const int64_t* offsets, const int32_t* hw, const int32_t* crops, int k0, int nk, int S, int32_t* geom) {
     double bytes = 0.0;
-    for (int i = 0; i < nc; ++i) {
-        const int* r = crops + 5 * (c0 + i);
-        const int im = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-        const int W = hw[2 * im + 1];
+    for (int i = 0; i < nk; ++i) {
+        const LbRec r = lb_rec(hw, crops, k0 + i);
         int g[6];
-        lb_geometry(h, w, S, g);
-        t.off[i] = offsets[im] + ((long long)y0 * W + x0) * 3; t.pitch[i] = W * 3;
-        t.h[i] = h; t.w[i] = w; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
-        bytes += (double)h * w * 3;
+        bytes += lb_src_fill(t.src[i], g, offsets, hw, r.im, r.y0, r.x0, r.h, r.w, S);
+        t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
+        if (geom) for (int k = 0; k < 6; ++k) geom[6 * (k0 + i) + k] = g[k];
     }
     return bytes;
 }
 
+// fv_letterbox, fv_letterbox_batch and fv_letterbox_crops: check, then N entries per launch; `label` is the profile record's
+template <int N>
+int lb_run(fv_ctx* ctx, const char* who, const char* label, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+           const int32_t* crops, int n, int S, float* dst, int32_t* geom) {
+    if (int rc = lb_list_check(ctx, who, offsets, hw, n_img, crops, n, S)) return rc;
+    for (int k0 = 0; k0 < n; k0 += N) {
+        const int nk = n - k0 < N ? n - k0 : N;
+        LbTable<N> t{};
+        const double bytes = lb_list_fill(t, offsets, hw, crops, k0, nk, S, geom) + 12.0 * S * S * nk;
+        FvProfScope ps(ctx, label, 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_kernel<N>, dim3((S + 15) / 16, (S + 15) / 16, nk), dim3(256), 0, ctx->stream, packed, t, S,
+                           dst + (size_t)k0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+// a tile's box: side T at (oy, ox), flip, three colour parameters (or null)
+int lb_place_check(fv_ctx* ctx, const char* who, const char* rec, int k, int flip, const float* c) {
+    FV_REQUIRE(ctx, flip == 0 || flip == 1, "%s: %s %d: flip %d is neither 0 nor 1", who, rec, k, flip);
+    FV_REQUIRE(ctx, !c || (std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2])), "%s: %s %d: colour parameters are not finite",
+               who, rec, k);
+    return FV_OK;
+}
+
+// ox is the box's column AFTER an in-place flip; g the content's geometry inside the box
+void lb_place_fill(LbPlace& p, const int* g, int T, int oy, int ox, int flip, const float* c) {
+    const bool col = c && !(c[0] == 0.f && c[1] == 1.f && c[2] == 1.f);           // exactly (0, 1, 1): the stage is skipped
+    p.top = oy + g[2];
+    p.xa = flip ? ox + T - 1 - g[4] : ox + g[4];
+    p.mode = flip | (col ? 2 : 0);
+    p.dh = col ? c[0] : 0.f; p.sat = col ? c[1] : 1.f; p.ex = col ? c[2] : 1.f;
+}
+
 }  // namespace
+
+extern "C" int fv_letterbox(fv_ctx* ctx, const uint8_t* src, int h, int w, int image_size, float* dst, int32_t* geom) {
+    if (!ctx) return FV_ERR_INVALID;
+    FV_REQUIRE(ctx, src && dst && image_size >= 1, "letterbox: bad arguments");
+    const int64_t off = 0;
+    const int32_t hw[2] = {h, w};
+    return lb_run<1>(ctx, "letterbox", "letterbox_kernel", src, &off, hw, 1, nullptr, 1, image_size, dst, geom);
+}
 
 extern "C" int fv_letterbox_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
                                   int image_size, float* dst, int32_t* geom) {
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, packed && offsets && hw && dst && n >= 1 && image_size >= 1, "letterbox_batch: bad arguments");
-    const int S = image_size;
-    for (int b0 = 0; b0 < n; b0 += LB_MAX) {
-        const int nb = n - b0 < LB_MAX ? n - b0 : LB_MAX;
-        LbTable t{};
-        double bytes = 0.0;
-        for (int i = 0; i < nb; ++i) {
-            const int h = hw[2 * (b0 + i)], w = hw[2 * (b0 + i) + 1];
-            int g[6];
-            FV_REQUIRE(ctx, h >= 1 && w >= 1 && offsets[b0 + i] >= 0, "letterbox_batch: bad image %d", b0 + i);
-            FV_REQUIRE(ctx, lb_geometry(h, w, S, g), "letterbox_batch: image %d too elongated for image_size %d", b0 + i, S);
-            t.off[i] = offsets[b0 + i]; t.h[i] = h; t.w[i] = w; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.pad_t[i] = g[2]; t.pad_l[i] = g[4];
-            if (geom) for (int k = 0; k < 6; ++k) geom[6 * (b0 + i) + k] = g[k];
-            bytes += (double)h * w * 3 + 12.0 * S * S;
-        }
-        FvProfScope ps(ctx, "letterbox_batch_kernel", 0.0, bytes);
-        hipLaunchKernelGGL(letterbox_batch_kernel, dim3((S + 15) / 16, (S + 15) / 16, nb), dim3(256), 0, ctx->stream, packed, t, S,
-                           dst + (size_t)b0 * S * S * 3);
-        FV_LAUNCH_CHECK(ctx);
-    }
-    return FV_OK;
+    return lb_run<LB_MAX>(ctx, "letterbox_batch", "letterbox_batch_kernel", packed, offsets, hw, n, nullptr, n, image_size, dst, geom);
 }
 
 extern "C" int fv_letterbox_crops(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
                                   const int32_t* crops, int n, int image_size, float* dst) {
     if (!ctx) return FV_ERR_INVALID;
     FV_REQUIRE(ctx, packed && offsets && hw && crops && dst && n_img >= 1 && n >= 1 && image_size >= 1, "letterbox_crops: bad arguments");
-    const int S = image_size;
-    if (int rc = lbc_validate(ctx, "letterbox_crops", offsets, hw, n_img, crops, n, S)) return rc;
-    for (int c0 = 0; c0 < n; c0 += LBC_MAX) {
-        const int nc = n - c0 < LBC_MAX ? n - c0 : LBC_MAX;
-        LbcTable t{};
-        const double bytes = lbc_fill(t, offsets, hw, crops, c0, nc, S) + 12.0 * S * S * nc;
-        FvProfScope ps(ctx, "letterbox_crops_kernel", 0.0, bytes);
-        hipLaunchKernelGGL(letterbox_crops_kernel, dim3((S + 15) / 16, (S + 15) / 16, nc), dim3(256), 0, ctx->stream, packed, t, S,
-                           dst + (size_t)c0 * S * S * 3);
-        FV_LAUNCH_CHECK(ctx);
-    }
-    return FV_OK;
-}
-
-extern "C" int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
-                                          int image_size, const int32_t* place, const float* colour, float* dst) {
-    if (!ctx) return FV_ERR_INVALID;
-    FV_REQUIRE(ctx, packed && offsets && hw && place && dst && n >= 1 && image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
-               "letterbox_augment_batch: bad arguments (image_size a multiple of 4 and dst 16-byte aligned: rows are stored 16 bytes at a time)");
-    const int S = image_size;
-    // every record before anything is enqueued: a bad one leaves dst untouched
-    for (int i = 0; i < n; ++i) {
-        const int H = hw[2 * i], W = hw[2 * i + 1];
-        const int* r = place + 8 * i;
-        const int cy0 = r[0], cx0 = r[1], ch = r[2], cw = r[3], T = r[4], oy = r[5], ox = r[6], flip = r[7];
-        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[i] >= 0, "letterbox_augment_batch: bad image %d", i);
-        FV_REQUIRE(ctx, ch >= 1 && cw >= 1 && cy0 >= 0 && cx0 >= 0 && cy0 <= H - ch && cx0 <= W - cw,
-                   "letterbox_augment_batch: crop (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", cy0, cx0, ch, cw, i, H, W);
-        FV_REQUIRE(ctx, T >= 1 && T <= S && oy >= 0 && ox >= 0 && oy <= S - T && ox <= S - T,
-                   "letterbox_augment_batch: image %d: box of side %d at (y %d, x %d) outside the %d x %d canvas", i, T, oy, ox, S, S);
-        int g[6];
-        FV_REQUIRE(ctx, lb_geometry(ch, cw, T, g), "letterbox_augment_batch: image %d: crop %d x %d too elongated for a box of side %d", i, ch, cw, T);
-        FV_REQUIRE(ctx, flip == 0 || flip == 1, "letterbox_augment_batch: image %d: flip %d is neither 0 nor 1", i, flip);
-        if (colour)
-            FV_REQUIRE(ctx, std::isfinite(colour[3 * i]) && std::isfinite(colour[3 * i + 1]) && std::isfinite(colour[3 * i + 2]),
-                       "letterbox_augment_batch: image %d: colour parameters are not finite", i);
-    }
-    for (int b0 = 0; b0 < n; b0 += LBA_MAX) {
-        const int nb = n - b0 < LBA_MAX ? n - b0 : LBA_MAX;
-        LbaTable t{};
-        double bytes = 0.0;
-        for (int i = 0; i < nb; ++i) {
-            const int W = hw[2 * (b0 + i) + 1];
-            const int* r = place + 8 * (b0 + i);
-            const float* c = colour ? colour + 3 * (b0 + i) : nullptr;
-            int g[6];
-            lb_geometry(r[2], r[3], r[4], g);
-            t.off[i] = offsets[b0 + i] + ((long long)r[0] * W + r[1]) * 3; t.pitch[i] = W * 3;
-            t.h[i] = r[2]; t.w[i] = r[3]; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.top[i] = r[5] + g[2]; t.left[i] = r[6] + g[4];
-            const bool col = c && !(c[0] == 0.f && c[1] == 1.f && c[2] == 1.f);       // exactly (0, 1, 1): the stage is skipped
-            t.mode[i] = r[7] | (col ? 2 : 0);
-            t.dh[i] = col ? c[0] : 0.f; t.sat[i] = col ? c[1] : 1.f; t.ex[i] = col ? c[2] : 1.f;
-            bytes += (double)r[2] * r[3] * 3 + 12.0 * S * S;
-        }
-        FvProfScope ps(ctx, "letterbox_augment_kernel", 0.0, bytes);
-        hipLaunchKernelGGL(letterbox_augment_kernel, dim3((S + LBA_TW - 1) / LBA_TW, (S + LBA_TH - 1) / LBA_TH, nb), dim3(256), 0,
-                           ctx->stream, packed, t, S, dst + (size_t)b0 * S * S * 3);
-        FV_LAUNCH_CHECK(ctx);
-    }
-    return FV_OK;
-}
-
-extern "C" int fv_letterbox_mosaic_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
-                                         int image_size, int n_out, const int32_t* tiles, const float* colour, int n_tiles, float* dst) {
-    if (!ctx) return FV_ERR_INVALID;
-    FV_REQUIRE(ctx, packed && offsets && hw && tiles && dst && n_img >= 1 && n_out >= 1 && n_tiles >= n_out && n_tiles <= MOS_PER * (long long)n_out &&
-                        image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
-               "letterbox_mosaic_batch: bad arguments (1 to 4 tiles per canvas, image_size a multiple of 4 and dst 16-byte aligned: rows are "
-               "stored 16 bytes at a time)");
-    const int S = image_size;
-    // every record before anything is enqueued: a bad one leaves dst untouched
-    int canvas = 0, first = 0;                                       // the canvas being read and its first tile
-    for (int k = 0; k < n_tiles; ++k) {
-        const int* r = tiles + 14 * k;
-        const int cv = r[0], im = r[1], cy0 = r[2], cx0 = r[3], ch = r[4], cw = r[5], T = r[6], oy = r[7], ox = r[8], flip = r[9];
-        const int wy0 = r[10], wx0 = r[11], wy1 = r[12], wx1 = r[13];
-        FV_REQUIRE(ctx, cv >= 0 && cv < n_out && (cv == canvas || (cv == canvas + 1 && k > first)),
-                   "letterbox_mosaic_batch: tile %d names canvas %d after canvas %d (of %d): the tiles are sorted by canvas and every canvas "
-                   "has at least one", k, cv, canvas, n_out);
-        if (cv != canvas) { canvas = cv; first = k; }
-        FV_REQUIRE(ctx, k - first < MOS_PER, "letterbox_mosaic_batch: canvas %d has more than %d tiles", cv, MOS_PER);
-        FV_REQUIRE(ctx, im >= 0 && im < n_img, "letterbox_mosaic_batch: tile %d names image %d of %d", k, im, n_img);
-        const int H = hw[2 * im], W = hw[2 * im + 1];
-        FV_REQUIRE(ctx, H >= 1 && W >= 1 && offsets[im] >= 0, "letterbox_mosaic_batch: bad image %d", im);
-        FV_REQUIRE(ctx, ch >= 1 && cw >= 1 && cy0 >= 0 && cx0 >= 0 && cy0 <= H - ch && cx0 <= W - cw,
-                   "letterbox_mosaic_batch: tile %d: crop (y0 %d, x0 %d, h %d, w %d) outside image %d (%d x %d)", k, cy0, cx0, ch, cw, im, H, W);
-        FV_REQUIRE(ctx, T >= 1 && T <= 4LL * S && oy >= -T && ox >= -T && oy <= S && ox <= S,
-                   "letterbox_mosaic_batch: tile %d: box of side %d at (y %d, x %d): 1 <= side <= 4 x %d and -side <= y, x <= %d", k, T, oy, ox, S, S);
-        int g[6];
-        FV_REQUIRE(ctx, lb_geometry(ch, cw, T, g), "letterbox_mosaic_batch: tile %d: crop %d x %d too elongated for a box of side %d", k, ch, cw, T);
-        FV_REQUIRE(ctx, flip == 0 || flip == 1, "letterbox_mosaic_batch: tile %d: flip %d is neither 0 nor 1", k, flip);
-        FV_REQUIRE(ctx, wy0 >= 0 && wx0 >= 0 && wy0 < wy1 && wx0 < wx1 && wy1 <= S && wx1 <= S,
-                   "letterbox_mosaic_batch: tile %d: window rows [%d, %d) columns [%d, %d) is empty or outside the %d x %d canvas", k, wy0, wy1,
-                   wx0, wx1, S, S);
-        for (int j = first; j < k; ++j) {
-            const int* q = tiles + 14 * j;
-            FV_REQUIRE(ctx, wy1 <= q[10] || q[12] <= wy0 || wx1 <= q[11] || q[13] <= wx0,
-                       "letterbox_mosaic_batch: the windows of tiles %d and %d of canvas %d overlap", j, k, cv);
-        }
-        if (colour)
-            FV_REQUIRE(ctx, std::isfinite(colour[3 * k]) && std::isfinite(colour[3 * k + 1]) && std::isfinite(colour[3 * k + 2]),
-                       "letterbox_mosaic_batch: tile %d: colour parameters are not finite", k);
-    }
-    FV_REQUIRE(ctx, canvas == n_out - 1, "letterbox_mosaic_batch: canvas %d of %d has no tile", canvas + 1, n_out);
-    // whole canvases per launch, as many as MOS_TILES tiles hold
-    for (int k0 = 0, c0 = 0; k0 < n_tiles;) {
-        MosTable t{};
-        double bytes = 0.0;
-        int nt = 0, nc = 0;
-        while (k0 + nt < n_tiles) {
-            int m = 1;
-            while (k0 + nt + m < n_tiles && tiles[14 * (k0 + nt + m)] == tiles[14 * (k0 + nt)]) ++m;    // the tiles of the next canvas
-            if (nt + m > MOS_TILES) break;
-            t.first[nc] = (unsigned char)nt;
-            for (int i = nt; i < nt + m; ++i) {
-                const int* r = tiles + 14 * (k0 + i);
-                const float* c = colour ? colour + 3 * (k0 + i) : nullptr;
-                const int W = hw[2 * r[1] + 1];
-                int g[6];
-                lb_geometry(r[4], r[5], r[6], g);
-                t.off[i] = offsets[r[1]] + ((long long)r[2] * W + r[3]) * 3; t.pitch[i] = W * 3;
-                t.h[i] = r[4]; t.w[i] = r[5]; t.w_p[i] = g[0]; t.h_p[i] = g[1]; t.top[i] = r[7] + g[2];
-                t.xa[i] = r[9] ? r[8] + r[6] - 1 - g[4] : r[8] + g[4];
-                const bool col = c && !(c[0] == 0.f && c[1] == 1.f && c[2] == 1.f);       // exactly (0, 1, 1): the stage is skipped
-                t.mode[i] = r[9] | (col ? 2 : 0);
-                t.wy0[i] = r[10]; t.wx0[i] = r[11]; t.wy1[i] = r[12]; t.wx1[i] = r[13];
-                t.dh[i] = col ? c[0] : 0.f; t.sat[i] = col ? c[1] : 1.f; t.ex[i] = col ? c[2] : 1.f;
-                bytes += (double)r[4] * r[5] * 3;
-            }
-            nt += m; ++nc;
-            t.first[nc] = (unsigned char)nt;
-        }
-        bytes += 12.0 * S * S * nc;
-        FvProfScope ps(ctx, "letterbox_mosaic_kernel", 0.0, bytes);
-        hipLaunchKernelGGL(letterbox_mosaic_kernel, dim3((S + LBA_TW - 1) / LBA_TW, (S + LBA_TH - 1) / LBA_TH, nc), dim3(256), 0,
-                           ctx->stream, packed, t, S, dst + (size_t)c0 * S * S * 3);
-        FV_LAUNCH_CHECK(ctx);
-        k0 += nt; c0 += nc;
-    }
-    return FV_OK;
+    return lb_run<LB_MAX>(ctx, "letterbox_crops", "letterbox_crops_kernel", packed, offsets, hw, n_img, crops, n, image_size, dst, nullptr);
 }
 
 extern "C" int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
@@ -671,15 +429,12 @@ extern "C" int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int6
     FV_REQUIRE(ctx, packed && offsets && hw && crops && dst && n_img >= 1 && ((uintptr_t)dst & 15) == 0,
                "crop_nearest_u8: bad arguments (dst must be 16-byte aligned)");
     const int S = image_size;
-    if (int rc = lbc_validate(ctx, "crop_nearest_u8", offsets, hw, n_img, crops, n, S)) return rc;
-    // The crop table travels in the kernel arguments, LBC_MAX crops per launch, as in fv_letterbox_crops: no device allocation, no
-    // host-to-device copy of a pageable table (which would block the host) and nothing that has to outlive the call; one launch of
-    // 64 crops is already ~2 000 workgroups at 416.
-    const int blocks = (S * (3 * S / 16) + CNU_CHUNKS - 1) / CNU_CHUNKS;
-    for (int c0 = 0; c0 < n; c0 += LBC_MAX) {
-        const int nc = n - c0 < LBC_MAX ? n - c0 : LBC_MAX;
-        LbcTable t{};
-        const double bytes = lbc_fill(t, offsets, hw, crops, c0, nc, S) + 3.0 * S * S * nc;
+    if (int rc = lb_list_check(ctx, "crop_nearest_u8", offsets, hw, n_img, crops, n, S)) return rc;
+    const int blocks = (S * (3 * S / 16) + CNU_CHUNKS - 1) / CNU_CHUNKS;       // one launch of 64 crops is already ~2 000 workgroups at 416
+    for (int c0 = 0; c0 < n; c0 += LB_MAX) {
+        const int nc = n - c0 < LB_MAX ? n - c0 : LB_MAX;
+        LbTable<LB_MAX> t{};
+        const double bytes = lb_list_fill(t, offsets, hw, crops, c0, nc, S, nullptr) + 3.0 * S * S * nc;
         FvProfScope ps(ctx, "crop_nearest_u8_kernel", 0.0, bytes);
         hipLaunchKernelGGL(crop_nearest_u8_kernel, dim3(blocks, nc), dim3(CNU_THREADS), 3 * S * sizeof(int), ctx->stream, packed, t,
                            S, dst + (size_t)c0 * S * S * 3);
@@ -688,23 +443,96 @@ extern "C" int fv_crop_nearest_u8(fv_ctx* ctx, const uint8_t* packed, const int6
     return FV_OK;
 }
 
-extern "C" int fv_letterbox(fv_ctx* ctx, const uint8_t* src, int h, int w, int image_size, float* dst, int32_t* geom) {
+extern "C" int fv_letterbox_augment_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                          int image_size, const int32_t* place, const float* colour, float* dst) {
     if (!ctx) return FV_ERR_INVALID;
-    FV_REQUIRE(ctx, src && dst && h >= 1 && w >= 1 && image_size >= 1, "letterbox: bad arguments");
+    const char* who = "letterbox_augment_batch";
+    FV_REQUIRE(ctx, packed && offsets && hw && place && dst && n >= 1 && image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
+               "%s: bad arguments (image_size a multiple of 4 and dst 16-byte aligned: rows are stored 16 bytes at a time)", who);
     const int S = image_size;
-    int w_p, h_p, pad_t = 0, pad_b = 0, pad_l = 0, pad_r = 0;
-    if (w >= h) {   // face_detection.py:120-133
-        w_p = S; h_p = (int)((double)h / (double)w * S);
-        int pad = S - h_p; pad_t = pad / 2; pad_b = pad - pad_t;
-    } else {        // face_detection.py:134-147
-        h_p = S; w_p = (int)((double)w / (double)h * S);
-        int pad = S - w_p; pad_l = pad / 2; pad_r = pad - pad_l;
+    for (int i = 0; i < n; ++i) {
+        const int* r = place + 8 * i;                                    // cy0, cx0, ch, cw, T, oy, ox, flip
+        const int T = r[4], oy = r[5], ox = r[6];
+        FV_REQUIRE(ctx, T >= 1 && T <= S && oy >= 0 && ox >= 0 && oy <= S - T && ox <= S - T,
+                   "%s: image %d: box of side %d at (y %d, x %d) outside the %d x %d canvas", who, i, T, oy, ox, S, S);
+        if (int rc = lb_src_check(ctx, who, "crop", i, offsets, hw, n, i, r[0], r[1], r[2], r[3], T)) return rc;
+        if (int rc = lb_place_check(ctx, who, "image", i, r[7], colour ? colour + 3 * i : nullptr)) return rc;
     }
-    FV_REQUIRE(ctx, w_p >= 1 && h_p >= 1, "letterbox: image too elongated for image_size %d", S);
-    if (geom) { geom[0] = w_p; geom[1] = h_p; geom[2] = pad_t; geom[3] = pad_b; geom[4] = pad_l; geom[5] = pad_r; }
-    FvProfScope ps(ctx, "letterbox_kernel", 0.0, (double)h * w * 3 + 12.0 * S * S);
-    hipLaunchKernelGGL(letterbox_kernel, dim3((S + 15) / 16, (S + 15) / 16), dim3(256), 0, ctx->stream, src, h, w, S, w_p, h_p,
-                       pad_t, pad_l, dst);
-    FV_LAUNCH_CHECK(ctx);
+    for (int b0 = 0; b0 < n; b0 += LBA_MAX) {
+        const int nb = n - b0 < LBA_MAX ? n - b0 : LBA_MAX;
+        LbaTable t{};
+        double bytes = 12.0 * S * S * nb;
+        for (int i = 0; i < nb; ++i) {
+            const int* r = place + 8 * (b0 + i);
+            int g[6];
+            bytes += lb_src_fill(t.src[i], g, offsets, hw, b0 + i, r[0], r[1], r[2], r[3], r[4]);
+            // the flip mirrors the canvas: the box in place at the mirrored column
+            lb_place_fill(t.place[i], g, r[4], r[5], r[7] ? S - r[4] - r[6] : r[6], r[7], colour ? colour + 3 * (b0 + i) : nullptr);
+        }
+        FvProfScope ps(ctx, "letterbox_augment_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_augment_kernel, dim3((S + LBT_W - 1) / LBT_W, (S + LBT_H - 1) / LBT_H, nb), dim3(256), 0,
+                           ctx->stream, packed, t, S, dst + (size_t)b0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+    }
+    return FV_OK;
+}
+
+extern "C" int fv_letterbox_mosaic_batch(fv_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n_img,
+                                         int image_size, int n_out, const int32_t* tiles, const float* colour, int n_tiles, float* dst) {
+    if (!ctx) return FV_ERR_INVALID;
+    const char* who = "letterbox_mosaic_batch";
+    FV_REQUIRE(ctx, packed && offsets && hw && tiles && dst && n_img >= 1 && n_out >= 1 && n_tiles >= n_out && n_tiles <= MOS_PER * (long long)n_out &&
+                        image_size >= 4 && image_size % 4 == 0 && ((uintptr_t)dst & 15) == 0,
+               "%s: bad arguments (1 to 4 tiles per canvas, image_size a multiple of 4 and dst 16-byte aligned: rows are stored 16 bytes at a "
+               "time)", who);
+    const int S = image_size;
+    int canvas = 0, first = 0;                                       // the canvas being read and its first tile
+    for (int k = 0; k < n_tiles; ++k) {
+        const int* r = tiles + 14 * k;          // canvas, image, cy0, cx0, ch, cw, T, oy, ox, flip, wy0, wx0, wy1, wx1
+        const int cv = r[0], T = r[6], oy = r[7], ox = r[8], wy0 = r[10], wx0 = r[11], wy1 = r[12], wx1 = r[13];
+        FV_REQUIRE(ctx, cv >= 0 && cv < n_out && (cv == canvas || (cv == canvas + 1 && k > first)),
+                   "%s: tile %d names canvas %d after canvas %d (of %d): the tiles are sorted by canvas and every canvas has at least one", who,
+                   k, cv, canvas, n_out);
+        if (cv != canvas) { canvas = cv; first = k; }
+        FV_REQUIRE(ctx, k - first < MOS_PER, "%s: canvas %d has more than %d tiles", who, cv, MOS_PER);
+        FV_REQUIRE(ctx, T >= 1 && T <= 4LL * S && oy >= -T && ox >= -T && oy <= S && ox <= S,
+                   "%s: tile %d: box of side %d at (y %d, x %d): 1 <= side <= 4 x %d and -side <= y, x <= %d", who, k, T, oy, ox, S, S);
+        if (int rc = lb_src_check(ctx, who, "tile", k, offsets, hw, n_img, r[1], r[2], r[3], r[4], r[5], T)) return rc;
+        if (int rc = lb_place_check(ctx, who, "tile", k, r[9], colour ? colour + 3 * k : nullptr)) return rc;
+        FV_REQUIRE(ctx, wy0 >= 0 && wx0 >= 0 && wy0 < wy1 && wx0 < wx1 && wy1 <= S && wx1 <= S,
+                   "%s: tile %d: window rows [%d, %d) columns [%d, %d) is empty or outside the %d x %d canvas", who, k, wy0, wy1, wx0, wx1, S, S);
+        for (int j = first; j < k; ++j) {
+            const int* q = tiles + 14 * j;
+            FV_REQUIRE(ctx, wy1 <= q[10] || q[12] <= wy0 || wx1 <= q[11] || q[13] <= wx0, "%s: the windows of tiles %d and %d of canvas %d overlap",
+                       who, j, k, cv);
+        }
+    }
+    FV_REQUIRE(ctx, canvas == n_out - 1, "%s: canvas %d of %d has no tile", who, canvas + 1, n_out);
+    // whole canvases per launch, as many as MOS_TILES tiles hold
+    for (int k0 = 0, c0 = 0; k0 < n_tiles;) {
+        MosTable t{};
+        int nt = 0, nc = 0;
+        double bytes = 0.0;
+        while (k0 + nt < n_tiles) {
+            int m = 1;
+            while (k0 + nt + m < n_tiles && tiles[14 * (k0 + nt + m)] == tiles[14 * (k0 + nt)]) ++m;    // the tiles of the next canvas
+            if (nt + m > MOS_TILES) break;
+            for (int i = nt; i < nt + m; ++i) {
+                const int* r = tiles + 14 * (k0 + i);
+                int g[6];
+                bytes += lb_src_fill(t.src[i], g, offsets, hw, r[1], r[2], r[3], r[4], r[5], r[6]);
+                lb_place_fill(t.place[i], g, r[6], r[7], r[8], r[9], colour ? colour + 3 * (k0 + i) : nullptr);
+                for (int j = 0; j < 4; ++j) t.win[i][j] = r[10 + j];
+            }
+            nt += m;
+            t.first[++nc] = (unsigned char)nt;
+        }
+        bytes += 12.0 * S * S * nc;
+        FvProfScope ps(ctx, "letterbox_mosaic_kernel", 0.0, bytes);
+        hipLaunchKernelGGL(letterbox_mosaic_kernel, dim3((S + LBT_W - 1) / LBT_W, (S + LBT_H - 1) / LBT_H, nc), dim3(256), 0,
+                           ctx->stream, packed, t, S, dst + (size_t)c0 * S * S * 3);
+        FV_LAUNCH_CHECK(ctx);
+        k0 += nt; c0 += nc;
+    }
     return FV_OK;
 }

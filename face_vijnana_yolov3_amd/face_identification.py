@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from . import weights
-from ._lib import Context, FvError, lib, ptr
+from ._lib import Context, FvError, lib, packed_args, ptr
 from .annotate import MaskBlend, Outline, _font, annotation_prims, pack_masks      # noqa: F401 (part of this module's surface)
 from .model import Model
 from .weights import NUM_BASE_LAYERS
@@ -993,16 +993,13 @@ def fid_mine_negatives(ctx, ids, subjects, anchors, pos_off, positives, margin=T
 def letterbox_crops(ctx, images, crops, image_size, out=None):
     """fv_letterbox_crops: images = (device uint8 buffer, offsets, hw) of a batch (letterbox_batch_device's `keep`), crops = list
     of (image index, y0, x0, rows, cols) -> (n, S, S, 3) float32 CUDA tensor."""
-    import ctypes
-    dbuf, offs, hw = images
-    n, ni, S = len(crops), len(offs), int(image_size)
+    n, S = len(crops), int(image_size)
     if out is None:
-        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=dbuf.device)
+        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=images[0].device)
     if n == 0:
         return out
     flat = [int(v) for c in crops for v in c]
-    rc = lib().fv_letterbox_crops(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni,
-                                  (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
+    rc = lib().fv_letterbox_crops(ctx.handle, *packed_args(*images), (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
     ctx.check(rc, 'fv_letterbox_crops')
     return out
 
@@ -1010,13 +1007,11 @@ def letterbox_crops(ctx, images, crops, image_size, out=None):
 def crop_nearest_u8(ctx, images, crops, image_size, out=None):
     """fv_crop_nearest_u8: images and crops as for letterbox_crops -> (n, S, S, 3) uint8 CUDA tensor, each crop resized by
     nearest neighbour to its letterbox size and zero padded (create_db_fi's cv.resize(INTER_NEAREST) + cv.copyMakeBorder)."""
-    dbuf, offs, hw = images
-    n, ni, S = len(crops), len(offs), int(image_size)
+    n, S = len(crops), int(image_size)
     if out is None:
-        out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dbuf.device)
+        out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=images[0].device)
     flat = [int(v) for c in crops for v in c]
-    rc = lib().fv_crop_nearest_u8(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni,
-                                  (ctypes.c_int32 * max(1, 5 * n))(*flat), n, S, ptr(out))
+    rc = lib().fv_crop_nearest_u8(ctx.handle, *packed_args(*images), (ctypes.c_int32 * max(1, 5 * n))(*flat), n, S, ptr(out))
     ctx.check(rc, 'fv_crop_nearest_u8')
     return out
 
@@ -1065,7 +1060,7 @@ def draw_prims_u8(ctx, images, prims, masks):
         if not all(-2 ** 31 <= a < 2 ** 31 for a in v[:7]) or not all(0 <= c <= 255 for c in v[7:10]):
             raise ValueError('draw_prims_u8: primitive %d out of range: %r' % (k, p))
         table[k] = DrawPrim(*v)
-    rc = lib().fv_draw_prims_u8(ctx.handle, ptr(dbuf), (ctypes.c_int64 * ni)(*offs), (ctypes.c_int32 * (2 * ni))(*hw), ni, table, n,
+    rc = lib().fv_draw_prims_u8(ctx.handle, *packed_args(dbuf, offs, hw), table, n,
                                 None if masks is None else ptr(masks), 0 if masks is None else masks.numel())
     ctx.check(rc, 'fv_draw_prims_u8')
 

@@ -4,7 +4,7 @@ Mirrors the tail of FaceDetector.detect (reference face_detection.py:900-949) an
 record (reference yolov3_detect.py:126-163)."""
 import numpy as np
 
-from ._lib import lib, ptr
+from ._lib import lib, packed_args, ptr
 
 
 class BoundBox(object):
@@ -170,53 +170,38 @@ def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None,
     else:
         buf, offs, hw = packed if packed is not None else pack_images(raws)
         dbuf = buf.to(device, non_blocking=True)
-    n = len(offs)
-    S = int(image_size)
+    n, S = len(offs), int(image_size)
+    if mosaic is not None and aug is not None:
+        raise ValueError('letterbox_batch_device: aug and mosaic are given together (the mosaic tables carry the augmentation)')
+    # the records of the launch (`per` ints each), their colour parameters (3 floats each, or None) and the number of canvases
     if mosaic is not None:
-        if aug is not None:
-            raise ValueError('letterbox_batch_device: aug and mosaic are given together (the mosaic tables carry the augmentation)')
-        tiles, colour, n_out = mosaic
-        tiles = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1))
-        n_tiles, n_out = tiles.size // 14, int(n_out)
-        if tiles.size != 14 * n_tiles or n_tiles < 1:
-            raise ValueError('letterbox_batch_device: %d tile values (14 each, at least one tile)' % tiles.size)
-        cp = None
+        (recs, colour, n_out), per, what = mosaic, 14, 'tiles'
+    else:
+        (recs, colour), n_out, per, what = (aug if aug is not None else (None, None)), n, 8, 'images'
+    n_out, rp, cp = int(n_out), None, None
+    if recs is not None:
+        recs = np.ascontiguousarray(np.asarray(recs, np.int32).reshape(-1))
+        n_rec = max(1, recs.size // per) if mosaic is not None else n
+        if recs.size != per * n_rec:
+            raise ValueError('letterbox_batch_device: %d record values for %d %s (%d each)' % (recs.size, n_rec, what, per))
+        rp = recs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         if colour is not None:
             colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(-1))
-            if colour.size != 3 * n_tiles:
-                raise ValueError('letterbox_batch_device: %d colour values for %d tiles (3 each)' % (colour.size, n_tiles))
+            if colour.size != 3 * n_rec:
+                raise ValueError('letterbox_batch_device: %d colour values for %d %s (3 each)' % (colour.size, n_rec, what))
             cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        if out is None:
-            out = torch.empty((n_out, S, S, 3), dtype=torch.float32, device=device)
-        rc = lib().fv_letterbox_mosaic_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, n_out,
-                                             tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, n_tiles, ptr(out))
-        ctx.check(rc, 'fv_letterbox_mosaic_batch')
-        if keep is not None:
-            keep.append((dbuf, list(offs), list(hw)))
-        return out, None
     if out is None:
-        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=device)
-    if aug is not None:
-        place, colour = aug
-        place = np.ascontiguousarray(np.asarray(place, np.int32).reshape(-1))
-        if place.size != 8 * n:
-            raise ValueError('letterbox_batch_device: %d placement values for %d images (8 each)' % (place.size, n))
-        cp = None
-        if colour is not None:
-            colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(-1))
-            if colour.size != 3 * n:
-                raise ValueError('letterbox_batch_device: %d colour values for %d images (3 each)' % (colour.size, n))
-            cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        rc = lib().fv_letterbox_augment_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S,
-                                              place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, ptr(out))
-        ctx.check(rc, 'fv_letterbox_augment_batch')
-        if keep is not None:
-            keep.append((dbuf, list(offs), list(hw)))
-        return out, None
-    geom = (ctypes.c_int32 * (6 * n))()
-    rc = lib().fv_letterbox_batch(ctx.handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, ptr(out), geom)
-    ctx.check(rc, 'fv_letterbox_batch')
+        out = torch.empty((n_out, S, S, 3), dtype=torch.float32, device=device)
+    head = (ctx.handle,) + packed_args(dbuf, offs, hw)
+    geom = None
+    if mosaic is not None:
+        name, rc = 'fv_letterbox_mosaic_batch', lib().fv_letterbox_mosaic_batch(*head, S, n_out, rp, cp, n_rec, ptr(out))
+    elif aug is not None:
+        name, rc = 'fv_letterbox_augment_batch', lib().fv_letterbox_augment_batch(*head, S, rp, cp, ptr(out))
+    else:
+        geom = (ctypes.c_int32 * (6 * n))()
+        name, rc = 'fv_letterbox_batch', lib().fv_letterbox_batch(*head, S, ptr(out), geom)
+    ctx.check(rc, name)
     if keep is not None:
         keep.append((dbuf, list(offs), list(hw)))
-    geoms = [(hw[2 * i], hw[2 * i + 1], geom[6 * i + 2], geom[6 * i + 3], geom[6 * i + 4], geom[6 * i + 5]) for i in range(n)]
-    return out, geoms
+    return out, None if geom is None else [(hw[2 * i], hw[2 * i + 1]) + tuple(geom[6 * i + 2:6 * i + 6]) for i in range(n)]

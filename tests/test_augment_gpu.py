@@ -16,7 +16,7 @@ import torch
 import letterbox_augment_ref as ref
 from face_vijnana_yolov3_amd import data
 from face_vijnana_yolov3_amd import face_identification as fi
-from face_vijnana_yolov3_amd._lib import Context, FvError, lib, ptr
+from face_vijnana_yolov3_amd._lib import Context, FvError, lib, packed_args, ptr
 from face_vijnana_yolov3_amd.postproc import letterbox_batch_device
 
 pytestmark = pytest.mark.gpu
@@ -58,8 +58,8 @@ def _augment(images, place, colour, S, out=None):
     if colour is not None:
         colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(n, 3))
         cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-    rc = lib().fv_letterbox_augment_batch(_ctx().handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S,
-                                          place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, ptr(out))
+    rc = lib().fv_letterbox_augment_batch(_ctx().handle, *packed_args(dbuf, offs, hw), S, place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          cp, ptr(out))
     _ctx().check(rc, 'fv_letterbox_augment_batch')
     return out
 

@@ -14,7 +14,7 @@ import letterbox_augment_ref as aref
 import letterbox_mosaic_ref as mref
 from face_vijnana_yolov3_amd import data
 from face_vijnana_yolov3_amd import face_identification as fi
-from face_vijnana_yolov3_amd._lib import Context, FvError, lib, ptr
+from face_vijnana_yolov3_amd._lib import Context, FvError, lib, packed_args, ptr
 from face_vijnana_yolov3_amd.postproc import letterbox_batch_device
 
 pytestmark = pytest.mark.gpu
@@ -41,17 +41,15 @@ def _upload(raws):
 
 
 def _mosaic(images, tiles, colour, S, n_out, out=None, fill=float('nan')):
-    dbuf, offs, hw = images
-    n = len(offs)
     if out is None:
-        out = torch.full((n_out, S, S, 3), fill, dtype=torch.float32, device=dbuf.device)     # every element must be written
+        out = torch.full((n_out, S, S, 3), fill, dtype=torch.float32, device=images[0].device)     # every element must be written
     tiles = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 14))
     cp = None
     if colour is not None:
         colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(len(tiles), 3))
         cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-    rc = lib().fv_letterbox_mosaic_batch(_ctx().handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S, n_out,
-                                         tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, len(tiles), ptr(out))
+    rc = lib().fv_letterbox_mosaic_batch(_ctx().handle, *packed_args(*images), S, n_out, tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp,
+                                         len(tiles), ptr(out))
     _ctx().check(rc, 'fv_letterbox_mosaic_batch')
     return out
 
@@ -65,8 +63,8 @@ def _augment(images, place, colour, S):
     if colour is not None:
         colour = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(n, 3))
         cp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-    rc = lib().fv_letterbox_augment_batch(_ctx().handle, ptr(dbuf), (ctypes.c_int64 * n)(*offs), (ctypes.c_int32 * (2 * n))(*hw), n, S,
-                                          place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, ptr(out))
+    rc = lib().fv_letterbox_augment_batch(_ctx().handle, *packed_args(dbuf, offs, hw), S, place.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          cp, ptr(out))
     _ctx().check(rc, 'fv_letterbox_augment_batch')
     return out
 
