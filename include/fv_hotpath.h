@@ -46,12 +46,20 @@ int fv_create(int device, void* stream, fv_ctx** out);
  * DESIGN 6.) */
 void fv_destroy(fv_ctx* ctx);
 const char* fv_last_error(const fv_ctx* ctx);
+/* Rebinds the context to another hipStream_t (NULL = the default stream); a host setter, nothing is enqueued.  The stream
+ * contract: every launch, memset and table upload of the calls that follow goes to this stream in call order, so an entry point
+ * reads its inputs and writes its outputs in stream order; the only calls that wait for the host are fv_fid_pair_dists,
+ * fv_fid_mine_negatives and fv_profile_collect.  Work already enqueued stays where it is: the caller orders the old stream and the
+ * new one itself, and zero-fills what a call accumulates into (dw, statistics slots) on the stream the context is bound to.
+ * tests/test_stream_order_gpu.py runs every entry point on a delayed non-default stream. */
 int fv_set_stream(fv_ctx* ctx, void* stream);
 /* Where fv_bucket_fn fires.  Default (0): after the context's stream has been made to wait for the range's weight-gradient --
  * work the callback enqueues on the context's stream sees the finished range.  on = 1 (with the overlap on): as soon as the
  * range's weight-gradient kernels are in the SIDE stream's queue -- the callback must enqueue its work (the all-reduce of the
  * bucket) on fv_side_stream(ctx), where it is ordered behind them and runs beside the data-gradient chain without an event
- * between the context's stream and the communication; the side stream is joined before fv_train_step returns. */
+ * between the context's stream and the communication.  Before fv_train_step returns, the context's stream has been made to wait
+ * for every weight-gradient kernel on the side stream (the event is recorded before the callback fires); what the callback itself
+ * enqueued on the side stream is NOT joined by the library: the caller joins it (once, before fv_adam_step). */
 int fv_set_bucket_on_side(fv_ctx* ctx, int on);
 void* fv_side_stream(fv_ctx* ctx);   /* the hipStream_t of the internal side stream */
 /* Update rule of the BatchNormalization moving mean / variance in every training-mode BN launch that follows (reference
