@@ -93,6 +93,8 @@ def _declare(L):
         'fv_det_match_rows': (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp]),
         'fv_det_ap_sweep_workspace_bytes': (sz, [i32]),
         'fv_det_ap_sweep': (i32, [vp, vp, vp, vp, vp, i32, ctypes.POINTER(f64), i32, i64, vp, sz, vp, vp, vp, vp]),
+        'fv_tile_merge_workspace_bytes': (sz, [i32]),                     # csrc/tile_merge.h
+        'fv_tile_merge': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, sz, vp, vp, vp, vp]),
         'fv_num_layers': (i32, []),
         'fv_layer': (i32, [i32, ctypes.POINTER(LayerDesc)]),
         'fv_param_count': (i64, []),

@@ -296,6 +296,98 @@ def validate_line(res):
     return ' '.join(parts)
 
 
+# ----------------------------------------------------------------------------- tiled inference (hps['tiles'])
+TILES_DEFAULTS = {'size': 1024, 'overlap': 0.2, 'full': True, 'metric': 'ios', 'merge_th': 0.5, 'max_tiles': 64}
+TILE_METRICS = ('ios', 'iou')          # FV_TILE_METRIC_IOS, FV_TILE_METRIC_IOU of csrc/tile_merge.h, in this order
+TILE_MAX_CANDS = 4096                  # FV_TILE_MAX_CANDS
+TILE_MAX_TILES = 64
+
+
+def tiles_conf(value, head='single'):
+    """fd_conf.hps['tiles'] -> None (absent, None or false: every frame is letterboxed whole, as without the key) or the complete
+    parameter dict (true: TILES_DEFAULTS; an object: its keys over the defaults).  ValueError for another type, an unknown key, a
+    bool where a number is expected or a value outside its range: size (tile side in source pixels) an int >= 32, overlap (share
+    of size neighbouring tiles have in common) in [0, 0.5], full (the whole frame as one more view) a bool, metric 'ios'
+    (intersection over the smaller area) or 'iou', merge_th in (0, 1], max_tiles (per frame) an int in [1, 64].
+    NotImplementedError with the three-scale head.  Not in the reference; pure host code."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError('fd_conf.hps.tiles %r is not valid (false, true or an object with the keys %s)'
+                         % (value, ', '.join(sorted(TILES_DEFAULTS))))
+    unknown = sorted(set(value) - set(TILES_DEFAULTS))
+    if unknown:
+        raise ValueError('fd_conf.hps.tiles has unknown key(s) %s (available: %s)' % (', '.join(map(repr, unknown)),
+                                                                                   ', '.join(sorted(TILES_DEFAULTS))))
+    c = dict(TILES_DEFAULTS)
+    c.update(value)
+
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not (is_int(c['size']) and c['size'] >= 32):
+        raise ValueError('fd_conf.hps.tiles.size %r is not valid (source pixels, an int >= 32)' % (c['size'],))
+    if not (_is_number(c['overlap']) and 0 <= c['overlap'] <= 0.5):
+        raise ValueError('fd_conf.hps.tiles.overlap %r is not valid (a share of size in [0, 0.5])' % (c['overlap'],))
+    if not isinstance(c['full'], bool):
+        raise ValueError('fd_conf.hps.tiles.full %r is not valid (true or false)' % (c['full'],))
+    if not (isinstance(c['metric'], str) and c['metric'] in TILE_METRICS):
+        raise ValueError('fd_conf.hps.tiles.metric %r is not valid (%s)' % (c['metric'], ' or '.join(map(repr, TILE_METRICS))))
+    if not (_is_number(c['merge_th']) and 0 < c['merge_th'] <= 1):
+        raise ValueError('fd_conf.hps.tiles.merge_th %r is not valid (an overlap in (0, 1])' % (c['merge_th'],))
+    if not (is_int(c['max_tiles']) and 1 <= c['max_tiles'] <= TILE_MAX_TILES):
+        raise ValueError('fd_conf.hps.tiles.max_tiles %r is not valid (an int in [1, %d])' % (c['max_tiles'], TILE_MAX_TILES))
+    if head == 'three_scale':
+        raise NotImplementedError("fd_conf.hps.tiles with nn_arch.head = 'three_scale' is not implemented: the merge kernel takes "
+                                  "the single-scale head's decode/NMS result")
+    c['overlap'], c['merge_th'] = float(c['overlap']), float(c['merge_th'])
+    return c
+
+
+def _tile_spans(length, size, stride):
+    if length <= size:
+        return [(0, length)]
+    starts, s = [], 0
+    while s + size < length:
+        starts.append(s)
+        s += stride
+    if not starts or starts[-1] != length - size:
+        starts.append(length - size)
+    return [(s, size) for s in starts]
+
+
+def tile_grid(h, w, conf):
+    """The views of an h x w frame under tiles_conf()'s dict -> [(y0, x0, th, tw)] ints.  Per axis of length L, with
+    stride = max(1, int(size * (1 - overlap))): one span [0, L) when L <= size; else the starts 0, stride, 2 * stride, ... while
+    start + size < L, then L - size (duplicates dropped), every span `size` long.  The tiles are the row-major product of the two
+    axes; with `full` the whole frame (0, 0, h, w) comes last, unless the grid is exactly that one tile.  More than max_tiles
+    views is a ValueError: the grid is never changed silently.  Pure host code."""
+    h, w, size = int(h), int(w), int(conf['size'])
+    if h < 1 or w < 1:
+        raise ValueError('fd_conf.hps.tiles: a frame of %d x %d pixels has no tile' % (w, h))
+    stride = max(1, int(size * (1 - conf['overlap'])))
+    grid = [(y0, x0, th, tw) for y0, th in _tile_spans(h, size, stride) for x0, tw in _tile_spans(w, size, stride)]
+    if conf['full'] and grid != [(0, 0, h, w)]:
+        grid.append((0, 0, h, w))
+    if len(grid) > conf['max_tiles']:
+        raise ValueError('fd_conf.hps.tiles.max_tiles = %d is too small: a frame of %d x %d pixels (width x height) makes %d views at '
+                         'size %d, overlap %g; raise size or max_tiles (at most %d)'
+                         % (conf['max_tiles'], w, h, len(grid), size, conf['overlap'], TILE_MAX_TILES))
+    return grid
+
+
+def tile_views(h, w, conf, num_cands):
+    """tile_grid for a frame whose views each hand fv_tile_merge up to num_cands candidates: ValueError when they could exceed
+    the kernel's cap (FV_TILE_MAX_CANDS per frame)."""
+    grid = tile_grid(h, w, conf)
+    if len(grid) * int(num_cands) > TILE_MAX_CANDS:
+        raise ValueError('fd_conf.hps.tiles.max_tiles: a frame of %d x %d pixels (width x height) makes %d views of up to %d '
+                         'candidates (hps.num_cands) each, more than the %d per frame the merge takes; raise tiles.size or lower '
+                         'num_cands' % (w, h, len(grid), int(num_cands), TILE_MAX_CANDS))
+    return grid
+
+
 # ----------------------------------------------------------------------------- training augmentation (hps['augment'])
 AUGMENT_DEFAULTS ={'zoom': [0.75, 1.25], 'flip': 0.5, 'hue': 0.1, 'saturation': 1.5, 'exposure': 1.5, 'seed': 0}
 

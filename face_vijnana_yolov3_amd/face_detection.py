@@ -36,6 +36,9 @@ ratios.csv, the model files).  Differences, all documented in DESIGN.md:
     every n-th epoch -- cal_mAP_fd's AP over cal_mAP_sweep's thresholds, for the rows evaluate() would write, computed on the device
     (fv_det_rows_from_nms / fv_det_match_rows / fv_det_ap_sweep) -- keeps the results in validation_history and, with save_best,
     the best epoch's model in face_detector_best.h5; validate() is public and works on a loaded model
+  * hps['tiles'] (not in the reference, off unless asked for; data.tiles_conf) cuts every frame of evaluate() / test() / validate() /
+    detect_frame() into overlapping tiles, runs the detector on the tiles and the whole frame as one batch and merges what the views
+    saw of the same face on the device (fv_tile_merge); the rows of a frame then come in descending score; single-scale head only
 """
 import glob
 import json
@@ -48,6 +51,7 @@ import numpy as np
 
 from . import data
 from .postproc import BoundBox, PinnedRing, decode_nms, letterbox_batch_device, pack_images, to_boundboxes
+from .postproc import decode_nms_buffers, letterbox_crops, tile_merge, tile_merge_workspace, TILE_ROWS
 
 DEBUG = True
 
@@ -108,6 +112,7 @@ class FaceDetector(object):
     OUTPUT_FILE_NAME = 'solution.csv'
     EVALUATION_FILE_NAME = 'eval.csv'
     CELL_SIZE = 13
+    TILE_MAX_VIEWS = 4096                          # hps['tiles']: views per fv_tile_merge launch; a frame batch with more is cut
 
     TrainingSequence = data.TrainingSequence
 
@@ -123,6 +128,7 @@ class FaceDetector(object):
         self.mosaic = data.mosaic_conf(self.hps.get('mosaic'))         # likewise
         self.det_loss = data.det_loss_conf(self.hps.get('loss'), self.nn_arch.get('head', 'single'))    # likewise
         self.validation = data.validate_conf(self.hps.get('validate'), conf.get('test_path'))          # likewise
+        self.tiles = data.tiles_conf(self.hps.get('tiles'), self.nn_arch.get('head', 'single'))        # likewise (NotImplementedError: three-scale head)
         self.validation_history = []
         self._validator = None
         if self.image_size % 32:
@@ -301,6 +307,8 @@ class FaceDetector(object):
     def _detect_collect(self, launched):
         tag, host, ev, n = launched
         ev.synchronize()
+        if tag == 'tiles':
+            return [self._tile_boxes(host, b) for b in range(n)]
         if tag == 'three_scale':
             return [self._three_scale_boxes(host, b) for b in range(n)]
         return [to_boundboxes(host, b) for b in range(n)]
@@ -319,6 +327,113 @@ class FaceDetector(object):
         keep = np.nonzero(score > 0)[0]
         keep = keep[np.argsort(score[keep], kind='stable')][:self.hps['num_cands']]
         return [BoundBox(bx[k, 0], bx[k, 1], bx[k, 2], bx[k, 3], objness=ob[k], classes=list(cl[k])) for k in keep]
+
+    # ------------------------------------------------------------------ tiled inference (hps['tiles'])
+    def _eval_batch(self):
+        return max(1, int(self.hps.get('eval_batch_size', default_eval_batch(self.image_size))))
+
+    def _tiles_run(self, x, imgs, rows=None, nrows=None):
+        """The tiled form of network + decode/NMS for one frame batch, everything on the device and nothing waited for: x the
+        (n,S,S,3) letterboxed whole frames, imgs = (device uint8 buffer, offsets, hw), the batch's decoded frames.  Every frame's
+        views (data.tile_views) are letterboxed from imgs (fv_letterbox_crops; a view that is the whole frame is x's own row, not
+        letterboxed a second time), run through the network and fv_decode_nms in chunks of at most eval_batch_size views -- every
+        chunk but a group's last is full -- into one result per group of frames, and merged per frame by one fv_tile_merge launch
+        per group (a group: as many consecutive frames as have at most TILE_MAX_VIEWS views together; one group unless
+        eval_batch_size x views per frame is beyond that).  -> dict of device tensors for the n frames: corners (n,60,4), rows
+        (n,60,5) (written into `rows` / `nrows` when given), nrows (n,), src (n,60), and obj, score (n,60) float32 gathered from
+        the views' results (0 past nrows)."""
+        import torch
+        conf, ctx, dev, S = self.tiles, self.model.ctx, self.model.dev, self.image_size
+        K = int(self.hps['num_cands'])
+        hw, n = imgs[2], len(imgs[1])
+        grids = [data.tile_views(hw[2 * i], hw[2 * i + 1], conf, K) for i in range(n)]         # ValueError before anything is queued
+        out = dict(corners=torch.empty((n, TILE_ROWS, 4), dtype=torch.float64, device=dev),
+                   rows=rows if rows is not None else torch.empty((n, TILE_ROWS, 5), dtype=torch.float64, device=dev),
+                   nrows=nrows if nrows is not None else torch.empty((n,), dtype=torch.int32, device=dev),
+                   src=torch.empty((n, TILE_ROWS), dtype=torch.int32, device=dev),
+                   obj=torch.empty((n, TILE_ROWS), dtype=torch.float32, device=dev),
+                   score=torch.empty((n, TILE_ROWS), dtype=torch.float32, device=dev))
+        bs = self._eval_batch()
+        f0 = 0
+        while f0 < n:
+            f1, nv = f0 + 1, len(grids[f0])
+            while f1 < n and nv + len(grids[f1]) <= self.TILE_MAX_VIEWS:
+                nv += len(grids[f1])
+                f1 += 1
+            views = [(i, g) for i in range(f0, f1) for g in grids[i]]
+            table = np.array([(i - f0,) + tuple(g) for i, g in views], np.int32).reshape(nv, 5)
+            off = np.cumsum([0] + [len(grids[i]) for i in range(f0, f1)]).astype(np.int32)
+            res = decode_nms_buffers(nv, K, dev)
+            xc = torch.empty((min(bs, nv), S, S, 3), dtype=torch.float32, device=dev)
+            for c0 in range(0, nv, bs):
+                c1 = min(c0 + bs, nv)
+                run = []                                  # consecutive tile views of the chunk: one fv_letterbox_crops call each run
+
+                def flush(end):
+                    if run:
+                        letterbox_crops(ctx, imgs, run, S, out=xc[end - c0 - len(run):end - c0])
+                        del run[:]
+                for j in range(c0, c1):
+                    i, g = views[j]
+                    if g == (0, 0, hw[2 * i], hw[2 * i + 1]):                  # the whole frame: already letterboxed
+                        flush(j)
+                        xc[j - c0].copy_(x[i])
+                    else:
+                        run.append((i,) + tuple(g))
+                flush(c1)
+                y = self.model.predict_device(xc[:c1 - c0])
+                decode_nms(ctx, y, S, self.hps['face_conf_th'], self.hps['nms_iou_th'], K, out={k: v[c0:c1] for k, v in res.items()})
+            part = {k: out[k][f0:f1] for k in ('corners', 'rows', 'nrows', 'src')}
+            tile_merge(ctx, res, torch.from_numpy(table).to(dev, non_blocking=True), torch.from_numpy(off).to(dev, non_blocking=True),
+                       S, conf['metric'], conf['merge_th'], workspace=self._tile_workspace(f1 - f0), out=part)
+            pick = part['src'].clamp(min=0).long()
+            live = part['src'] >= 0
+            out['obj'][f0:f1] = torch.where(live, res['obj'].reshape(-1)[pick], 0.0)
+            out['score'][f0:f1] = torch.where(live, res['score'].reshape(-1)[pick], 0.0)
+            f0 = f1
+        return out
+
+    def _tile_workspace(self, n_frames):
+        ws = getattr(self, '_tile_ws', None)
+        if ws is None or ws[0] < n_frames:
+            ws = self._tile_ws = (n_frames, tile_merge_workspace(n_frames, self.model.dev))
+        return ws[1]
+
+    def _tiles_launch(self, x, imgs):
+        """_detect_launch with tiles on: _tiles_run and the copy of the (small) merged result into pinned host memory behind an
+        event; no host sync."""
+        import torch
+        res = self._tiles_run(x, imgs)
+        host = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True).copy_(v, non_blocking=True)
+                for k, v in res.items() if k != 'rows'}
+        ev = torch.cuda.Event()
+        ev.record()
+        return ('tiles', host, ev, int(x.shape[0]))
+
+    def _tile_boxes(self, host, b):
+        """Frame b of a merged batch -> list[BoundBox] in FRAME coordinates (np.float64), descending score, at most 60."""
+        n = int(host['nrows'][b])
+        if n < 0:
+            raise ValueError('fd_conf.hps.tiles: a frame holds more candidates than the merge takes (%d); raise tiles.size or lower '
+                             'num_cands' % data.TILE_MAX_CANDS)
+        c = host['corners'][b, :n].numpy(); o = host['obj'][b, :n].numpy(); s = host['score'][b, :n].numpy()
+        return [BoundBox(c[k, 0], c[k, 1], c[k, 2], c[k, 3], objness=o[k], classes=[s[k]]) for k in range(n)]
+
+    def detect_frame(self, image_u8):
+        """One decoded frame, (H,W,3) uint8 (numpy or tensor) -> list[BoundBox] in FRAME coordinates: letterbox -> detect -> project
+        back (ascending score, as detect()); with hps['tiles'] the tiled form (descending score, at most 60).  detect() and
+        detect_batch() keep taking letterboxed input and are never tiled."""
+        import torch
+        a = image_u8.cpu().numpy() if torch.is_tensor(image_u8) else np.asarray(image_u8)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError('detect_frame: an (H, W, 3) uint8 frame is expected, got %s %r' % (a.dtype, a.shape))
+        keep = []
+        x, geoms = letterbox_batch_device(self.model.ctx, [a], self.image_size, self.model.dev, keep=keep)
+        if getattr(self, 'tiles', None) is not None:
+            return self._detect_collect(self._tiles_launch(x, keep[0]))[0]
+        boxes = self._detect_collect(self._detect_launch(x))[0]
+        self._project_back(boxes, geoms[0])
+        return boxes
 
     # ------------------------------------------------------------------ evaluate / test
     def _project_back(self, boxes, geom):
@@ -359,19 +474,26 @@ class FaceDetector(object):
         launch of _detect_launch, each batch's result turned into BoundBoxes and projected back one batch behind the queue.
         _with_images (FaceIdentifier.test): every item gains a fourth element ((device uint8 buffer, offsets, hw), index) -- the
         batch's decoded images as fv_letterbox_batch read them, kept alive and usable on the current stream."""
+        tiled = getattr(self, 'tiles', None) is not None     # hps['tiles']: the frames stay on the device and _tiles_launch cuts them
+
         def finish(done):
             chunk_, raws_, geoms_, launched, imgs_ = done
             for i, (name, boxes, geom) in enumerate(zip(chunk_, self._detect_collect(launched), geoms_)):
-                self._project_back(boxes, geom)
+                if not tiled:                                 # the merged boxes are in frame coordinates already
+                    self._project_back(boxes, geom)
                 if _with_images:
                     yield name, (raws_[i] if raws_ is not None else None), boxes, (imgs_, i)
                 else:
                     yield name, (raws_[i] if raws_ is not None else None), boxes
-        for done in self._launched_batches(files, lambda x, geoms: self._detect_launch(x), need_raw, _with_images):
+        if tiled:
+            batches = self._launched_batches(files, lambda x, geoms, imgs: self._tiles_launch(x, imgs), need_raw, True, _launch_images=True)
+        else:
+            batches = self._launched_batches(files, lambda x, geoms: self._detect_launch(x), need_raw, _with_images)
+        for done in batches:
             for item in finish(done):
                 yield item
 
-    def _launched_batches(self, files, launch, need_raw=True, _with_images=False):
+    def _launched_batches(self, files, launch, need_raw=True, _with_images=False, _launch_images=False):
         """The batched input path of evaluate() / test() / validate(): yield (chunk of file names, raw images or None, letterbox
         geometries, launch(x, geoms), device images or None) per batch of hps['eval_batch_size'] files, x the (n,S,S,3) letterboxed
         batch on the device, one batch behind the queue: batch k-1 is yielded once launch(k) was called and batch
@@ -380,7 +502,7 @@ class FaceDetector(object):
         the GIL) while batch k is letterboxed in one launch (fv_letterbox_batch) and runs ONE forward + ONE decode/NMS launch
         -- batch 1 is the slowest operating point of the network (1.3 ms/img against 0.4 at batch 16+).  Two deep: the loader
         thread fills a reused pinned buffer (PinnedRing) with batch k+1 while batch k is in the device queue and the consumer works on
-        batch k-1's result."""
+        batch k-1's result.  _launch_images (with _with_images): launch is called as launch(x, geoms, device images)."""
         bs = max(1, int(self.hps.get('eval_batch_size', default_eval_batch(self.image_size))))
         chunks = [files[i:i + bs] for i in range(0, len(files), bs)]
         if not chunks:
@@ -448,7 +570,7 @@ class FaceDetector(object):
                 x.record_stream(main)              # allocated on the staging stream, consumed on the compute stream
                 if imgs is not None:
                     imgs[0].record_stream(main)
-                cur = (chunk, raws, geoms, launch(x, geoms), imgs)
+                cur = (chunk, raws, geoms, launch(x, geoms, imgs) if _launch_images else launch(x, geoms), imgs)
                 if k + 1 < len(chunks):            # the host waits for the decode of k+1 while the GPU runs batch k, then stages it beside it
                     loaded = pending.result()
                     if k + 2 < len(chunks):
@@ -545,9 +667,15 @@ class FaceDetector(object):
         ctx, dev = self.model.ctx, self.model.dev
         state = {'i0': 0}
 
-        def launch(x, geoms):
+        tiled = getattr(self, 'tiles', None) is not None
+
+        def launch(x, geoms, imgs=None):
             i0, n = state['i0'], int(x.shape[0])
             state['i0'] = i0 + n
+            if tiled:          # hps['tiles']: fv_tile_merge's rows / nrows stand where fv_det_rows_from_nms' would
+                self._tiles_run(x, imgs, rows=v.rows[i0:i0 + n], nrows=v.nrows[i0:i0 + n])
+                v.match(ctx, i0, n)
+                return i0, None
             if self.three_scale:
                 return i0, self._detect_launch(x)
             res = decode_nms(ctx, self.model.predict_device(x), self.image_size, self.hps['face_conf_th'], self.hps['nms_iou_th'],
@@ -557,7 +685,8 @@ class FaceDetector(object):
             v.match(ctx, i0, n)
             return i0, None
 
-        for _chunk, _raws, geoms, (i0, launched), _imgs in self._launched_batches(v.files, launch, need_raw=False):
+        for _chunk, _raws, geoms, (i0, launched), _imgs in self._launched_batches(v.files, launch, need_raw=False, _with_images=tiled,
+                                                                                   _launch_images=tiled):
             if launched is None:
                 continue
             boxes = self._detect_collect(launched)
@@ -569,6 +698,9 @@ class FaceDetector(object):
             v.nrows[i0:i0 + n].copy_(torch.from_numpy(nrows))
             v.match(ctx, i0, n)
         res = v.finish(ctx)
+        if tiled and bool((v.nrows < 0).any()):          # the one read of nrows, after the set's only D2H copy
+            raise ValueError('fd_conf.hps.tiles: a frame of %s holds more candidates than the merge takes (%d); raise tiles.size or '
+                             'lower num_cands' % (v.conf['path'], data.TILE_MAX_CANDS))
         res['epoch'] = epoch
         return res
 

@@ -990,18 +990,7 @@ def fid_mine_negatives(ctx, ids, subjects, anchors, pos_off, positives, margin=T
     return neg, kind, d_ap, d_an
 
 
-def letterbox_crops(ctx, images, crops, image_size, out=None):
-    """fv_letterbox_crops: images = (device uint8 buffer, offsets, hw) of a batch (letterbox_batch_device's `keep`), crops = list
-    of (image index, y0, x0, rows, cols) -> (n, S, S, 3) float32 CUDA tensor."""
-    n, S = len(crops), int(image_size)
-    if out is None:
-        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=images[0].device)
-    if n == 0:
-        return out
-    flat = [int(v) for c in crops for v in c]
-    rc = lib().fv_letterbox_crops(ctx.handle, *packed_args(*images), (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
-    ctx.check(rc, 'fv_letterbox_crops')
-    return out
+from .postproc import letterbox_crops      # noqa: E402, F401 (lives next to the other letterbox wrappers; FaceDetector's tiles use it too)
 
 
 def crop_nearest_u8(ctx, images, crops, image_size, out=None):

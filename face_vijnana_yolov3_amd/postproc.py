@@ -38,20 +38,31 @@ class BoundBox(object):
                 int((self.xmax - self.xmin) / width * 100.), int((self.ymax - self.ymin) / height * 100.))
 
 
-def decode_nms(ctx, head, image_size, conf_th, iou_th, num_cands):
+def decode_nms_buffers(n, num_cands, device):
+    """The five result tensors of decode_nms for n images, uninitialised."""
+    import torch
+    k = int(num_cands)
+    return dict(boxes=torch.empty((n, k, 4), dtype=torch.int32, device=device),
+                cell=torch.empty((n, k), dtype=torch.int32, device=device),
+                obj=torch.empty((n, k), dtype=torch.float32, device=device),
+                score=torch.empty((n, k), dtype=torch.float32, device=device),
+                count=torch.empty((n,), dtype=torch.int32, device=device))
+
+
+def decode_nms(ctx, head, image_size, conf_th, iou_th, num_cands, out=None):
     """head: (n, G, G, 6) float32 CUDA tensor -> dict of CUDA tensors
-    boxes (n,K,4) i32, cell (n,K) i32, obj (n,K) f32, score (n,K) f32, count (n,) i32."""
+    boxes (n,K,4) i32, cell (n,K) i32, obj (n,K) f32, score (n,K) f32, count (n,) i32.  out: such a dict to write into (slices
+    along the first axis of decode_nms_buffers' tensors: the tiled path collects several calls in one result)."""
     import torch
     assert head.is_cuda and head.dtype == torch.float32 and head.dim() == 4 and head.shape[3] == 6
     head = head.contiguous()
     n, g = head.shape[0], head.shape[1]
     k = int(num_cands)
     dev = head.device
-    boxes = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
-    cell = torch.empty((n, k), dtype=torch.int32, device=dev)
-    obj = torch.empty((n, k), dtype=torch.float32, device=dev)
-    score = torch.empty((n, k), dtype=torch.float32, device=dev)
-    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    if out is None:
+        out = decode_nms_buffers(n, k, dev)
+    boxes, cell, obj, score, count = out['boxes'], out['cell'], out['obj'], out['score'], out['count']
+    assert tuple(boxes.shape) == (n, k, 4) and tuple(score.shape) == (n, k) and tuple(count.shape) == (n,)
     rc = lib().fv_decode_nms(ctx.handle, ptr(head), n, g, int(image_size), float(conf_th), float(iou_th), k,
                              ptr(boxes), ptr(cell), ptr(obj), ptr(score), ptr(count))
     ctx.check(rc, 'fv_decode_nms')
@@ -205,3 +216,63 @@ def letterbox_batch_device(ctx, raws, image_size, device, out=None, packed=None,
     if keep is not None:
         keep.append((dbuf, list(offs), list(hw)))
     return out, None if geom is None else [(hw[2 * i], hw[2 * i + 1]) + tuple(geom[6 * i + 2:6 * i + 6]) for i in range(n)]
+
+
+def letterbox_crops(ctx, images, crops, image_size, out=None):
+    """fv_letterbox_crops: images = (device uint8 buffer, offsets, hw) of a batch (letterbox_batch_device's `keep`), crops = list
+    of (image index, y0, x0, rows, cols) -> (n, S, S, 3) float32 CUDA tensor."""
+    import ctypes
+    import torch
+    n, S = len(crops), int(image_size)
+    if out is None:
+        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=images[0].device)
+    if n == 0:
+        return out
+    flat = [int(v) for c in crops for v in c]
+    rc = lib().fv_letterbox_crops(ctx.handle, *packed_args(*images), (ctypes.c_int32 * (5 * n))(*flat), n, S, ptr(out))
+    ctx.check(rc, 'fv_letterbox_crops')
+    return out
+
+
+TILE_ROWS = 60                # FV_DET_ROWS
+TILE_MAX_CANDS = 4096         # FV_TILE_MAX_CANDS of csrc/tile_merge.h
+TILE_METRICS = {'ios': 0, 'iou': 1}
+
+
+def tile_merge_workspace(n_frames, device):
+    """A CUDA tensor of fv_tile_merge_workspace_bytes(n_frames) bytes (float64, so 8-byte aligned); contents do not matter."""
+    import torch
+    need = int(lib().fv_tile_merge_workspace_bytes(int(n_frames)))
+    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+
+
+def tile_merge(ctx, res, tiles, frame_off, image_size, metric, merge_th, workspace=None, out=None):
+    """fv_tile_merge: decode_nms' device dict for T tile views, tiles (T, 5) int32 CUDA tensor (frame, y0, x0, th, tw) and frame_off
+    (F + 1,) int32 CUDA tensor (frame f owns the views frame_off[f] .. frame_off[f + 1]) -> dict of CUDA tensors corners
+    (F, 60, 4) float64 xmin, ymin, xmax, ymax in frame pixels, rows (F, 60, 5) float64 x, y, w, h, conf (what det_metric.match_rows
+    reads), nrows (F,) int32 (-1: the frame held more than 4096 candidates) and src (F, 60) int32 (view * K + slot, -1 past nrows).
+    metric 'ios' or 'iou'.  workspace: a CUDA tensor of at least fv_tile_merge_workspace_bytes(F) bytes (its contents are ignored);
+    out: a dict of the four tensors to write into (views of a longer buffer are fine).  No host sync."""
+    import torch
+    boxes, score, count = res['boxes'], res['score'], res['count']
+    T, K = int(boxes.shape[0]), int(boxes.shape[1])
+    F = int(frame_off.numel()) - 1
+    dev = boxes.device
+    assert boxes.dtype == torch.int32 and score.dtype == torch.float32 and count.dtype == torch.int32
+    assert tuple(score.shape) == (T, K) and tuple(count.shape) == (T,)
+    assert tiles.dtype == torch.int32 and tuple(tiles.shape) == (T, 5) and frame_off.dtype == torch.int32 and frame_off.dim() == 1
+    if metric not in TILE_METRICS:
+        raise ValueError("tile_merge: metric %r is not valid ('ios' or 'iou')" % (metric,))
+    ws = workspace if workspace is not None else tile_merge_workspace(F, dev)
+    if out is None:
+        out = dict(corners=torch.empty((F, TILE_ROWS, 4), dtype=torch.float64, device=dev),
+                   rows=torch.empty((F, TILE_ROWS, 5), dtype=torch.float64, device=dev),
+                   nrows=torch.empty((F,), dtype=torch.int32, device=dev),
+                   src=torch.empty((F, TILE_ROWS), dtype=torch.int32, device=dev))
+    assert tuple(out['corners'].shape) == (F, TILE_ROWS, 4) and tuple(out['rows'].shape) == (F, TILE_ROWS, 5)
+    assert tuple(out['nrows'].shape) == (F,) and tuple(out['src'].shape) == (F, TILE_ROWS)
+    rc = lib().fv_tile_merge(ctx.handle, ptr(boxes), ptr(score), ptr(count), ptr(tiles), ptr(frame_off), T, F, K, int(image_size),
+                             TILE_METRICS[metric], float(merge_th), ptr(ws), ws.numel() * ws.element_size(), ptr(out['corners']),
+                             ptr(out['rows']), ptr(out['nrows']), ptr(out['src']))
+    ctx.check(rc, 'fv_tile_merge')
+    return out
