@@ -119,7 +119,8 @@ struct FvWgradArgs {
     const float *bn_z, *bn_scale, *bn_shift, *bn_mean, *bn_invstd;
     const double* bn_slots;
     int bn_nslot;
-    float bn_inv_count, bn_leaky;
+    double bn_count;       // rows of the BN layer (B * H * W)
+    float bn_leaky;
     float *bn_dbeta, *bn_dgamma;
     int bn_accumulate;
     int B, Hin, Win, Cin;  // x dims

@@ -17,19 +17,24 @@ __device__ __forceinline__ float4 fv_bn_leaky4(float4 v, const float4& sc, const
     return v;
 }
 
-// dz = scale * (gy - dbeta/M - xhat * dgamma/M), gy = g * LeakyReLU'(z * scale + shift)
-__device__ __forceinline__ float fv_bn_bwd_dz(float g, float z, float sc, float sh, float mu, float is, float db, float dg,
-                                              float inv_count, float leaky) {
+// total / M of a published (float) d-beta or d-gamma, rounded once.  A product with float(1 / M) instead carries the rounding of the
+// reciprocal (0.8 u at M = 1000) into every element of dz with one sign: at 1000 rows that put dz 2.016 ulp from the float64
+// expression (tests/test_exact_bn_gpu.py); with the quotient a CPU emulation gives 1.64.
+__device__ __forceinline__ float fv_bn_mean_of(float total, double count) { return (float)((double)total / count); }
+
+// dz = scale * (gy - dbeta/M - xhat * dgamma/M), gy = g * LeakyReLU'(z * scale + shift); mb = fv_bn_mean_of(dbeta, M),
+// mg = fv_bn_mean_of(dgamma, M), formed once per channel where the caller has a prologue
+__device__ __forceinline__ float fv_bn_bwd_dz(float g, float z, float sc, float sh, float mu, float is, float mb, float mg, float leaky) {
     const float gy = (z * sc + sh) > 0.f ? g : g * leaky;
-    return sc * (gy - db * inv_count - (z - mu) * is * (dg * inv_count));
+    return sc * (gy - mb - (z - mu) * is * mg);
 }
 __device__ __forceinline__ float4 fv_bn_bwd_dz4(const float4& g, const float4& z, const float4& sc, const float4& sh, const float4& mu,
-                                                const float4& is, const float4& db, const float4& dg, float inv_count, float leaky) {
+                                                const float4& is, const float4& mb, const float4& mg, float leaky) {
     float4 o;
-    o.x = fv_bn_bwd_dz(g.x, z.x, sc.x, sh.x, mu.x, is.x, db.x, dg.x, inv_count, leaky);
-    o.y = fv_bn_bwd_dz(g.y, z.y, sc.y, sh.y, mu.y, is.y, db.y, dg.y, inv_count, leaky);
-    o.z = fv_bn_bwd_dz(g.z, z.z, sc.z, sh.z, mu.z, is.z, db.z, dg.z, inv_count, leaky);
-    o.w = fv_bn_bwd_dz(g.w, z.w, sc.w, sh.w, mu.w, is.w, db.w, dg.w, inv_count, leaky);
+    o.x = fv_bn_bwd_dz(g.x, z.x, sc.x, sh.x, mu.x, is.x, mb.x, mg.x, leaky);
+    o.y = fv_bn_bwd_dz(g.y, z.y, sc.y, sh.y, mu.y, is.y, mb.y, mg.y, leaky);
+    o.z = fv_bn_bwd_dz(g.z, z.z, sc.z, sh.z, mu.z, is.z, mb.z, mg.z, leaky);
+    o.w = fv_bn_bwd_dz(g.w, z.w, sc.w, sh.w, mu.w, is.w, mb.w, mg.w, leaky);
     return o;
 }
 

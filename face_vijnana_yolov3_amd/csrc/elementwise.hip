@@ -217,12 +217,13 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
     }
 }
 
-// pass 2: dz = scale * (gy - dbeta/M - xhat * dgamma/M)
+// pass 2: dz = scale * (gy - dbeta/M - xhat * dgamma/M).  The operator-level form (the training steps run the slot form below): it has
+// no per-channel prologue, so the two quotients are formed per element
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float4* __restrict__ g, const float4* __restrict__ z,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
                                                            const float* __restrict__ dbeta, const float* __restrict__ dgamma,
-                                                           float inv_count, long long n4, int C, float leaky, float4* __restrict__ dz) {
+                                                           double count, long long n4, int C, float leaky, float4* __restrict__ dz) {
     const int c4n = C >> 2;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const int cstep = (int)(stride % c4n);
@@ -234,13 +235,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float4* __restr
         const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
         const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
         const float4 db = *reinterpret_cast<const float4*>(dbeta + c), dg = *reinterpret_cast<const float4*>(dgamma + c);
-        float4 o;
-        float gy;
-        gy = (zv.x * sc.x + sh.x) > 0.f ? gv.x : gv.x * leaky; o.x = sc.x * (gy - db.x * inv_count - (zv.x - mu.x) * is.x * (dg.x * inv_count));
-        gy = (zv.y * sc.y + sh.y) > 0.f ? gv.y : gv.y * leaky; o.y = sc.y * (gy - db.y * inv_count - (zv.y - mu.y) * is.y * (dg.y * inv_count));
-        gy = (zv.z * sc.z + sh.z) > 0.f ? gv.z : gv.z * leaky; o.z = sc.z * (gy - db.z * inv_count - (zv.z - mu.z) * is.z * (dg.z * inv_count));
-        gy = (zv.w * sc.w + sh.w) > 0.f ? gv.w : gv.w * leaky; o.w = sc.w * (gy - db.w * inv_count - (zv.w - mu.w) * is.w * (dg.w * inv_count));
-        dz[i] = o;
+        const float4 mb = make_float4(fv_bn_mean_of(db.x, count), fv_bn_mean_of(db.y, count), fv_bn_mean_of(db.z, count), fv_bn_mean_of(db.w, count));
+        const float4 mg = make_float4(fv_bn_mean_of(dg.x, count), fv_bn_mean_of(dg.y, count), fv_bn_mean_of(dg.z, count), fv_bn_mean_of(dg.w, count));
+        dz[i] = fv_bn_bwd_dz4(gv, zv, sc, sh, mu, is, mb, mg, leaky);
     }
 }
 
@@ -251,13 +248,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_slots_kernel(const float4* _
                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                  const double* __restrict__ slots, int nslot,
                                                                  float* __restrict__ dbeta, float* __restrict__ dgamma,
-                                                                 float inv_count, long long n4, int C, float leaky, float4* __restrict__ dz,
+                                                                 double count, long long n4, int C, float leaky, float4* __restrict__ dz,
                                                                  int accumulate) {
-    __shared__ __attribute__((aligned(16))) float s_db[1024], s_dg[1024];
+    __shared__ __attribute__((aligned(16))) float s_db[1024], s_dg[1024];     // dbeta / M, dgamma / M
     __shared__ double s_part[2][256];
     const int tid = threadIdx.x;
     auto finish = [&](int c, double a, double b) {
-        s_db[c] = (float)a; s_dg[c] = (float)b;
+        s_db[c] = fv_bn_mean_of((float)a, count); s_dg[c] = fv_bn_mean_of((float)b, count);
         if (blockIdx.x == 0) {
             if (accumulate) { dbeta[c] += (float)a; dgamma[c] += (float)b; }
             else { dbeta[c] = (float)a; dgamma[c] = (float)b; }
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_slots_kernel(const float4* _
         const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
         const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
         const float4 db = *reinterpret_cast<const float4*>(s_db + c), dg = *reinterpret_cast<const float4*>(s_dg + c);
-        dz[i] = fv_bn_bwd_dz4(gv, zv, sc, sh, mu, is, db, dg, inv_count, leaky);
+        dz[i] = fv_bn_bwd_dz4(gv, zv, sc, sh, mu, is, db, dg, leaky);
     }
 }
 
@@ -667,7 +664,7 @@ int fv_ew_bn_bwd(fv_ctx* ctx, const float* g, const float* z, const float* scale
         long long n4s = rows * C / 4;
         FvProfScope ps(ctx, "bn_bwd_apply_slots_kernel", 0.0, 12.0 * rows * C);
         hipLaunchKernelGGL(bn_bwd_apply_slots_kernel, dim3(grid_for(n4s, 256, 256 * 4)), dim3(256), 0, ctx->stream, (const float4*)g,
-                           (const float4*)z, scale, shift, mean, invstd, slots, nslot, dbeta, dgamma, (float)(1.0 / (double)rows), n4s, C,
+                           (const float4*)z, scale, shift, mean, invstd, slots, nslot, dbeta, dgamma, (double)rows, n4s, C,
                            leaky, (float4*)dz, (int)accumulate);
         FV_LAUNCH_CHECK(ctx);
         return FV_OK;
@@ -678,7 +675,7 @@ int fv_ew_bn_bwd(fv_ctx* ctx, const float* g, const float* z, const float* scale
     long long n4 = rows * C / 4;
     FvProfScope ps(ctx, "bn_bwd_apply_kernel", 0.0, 12.0 * rows * C);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(n4, 256, 256 * 16)), dim3(256), 0, ctx->stream, (const float4*)g, (const float4*)z,
-                       scale, shift, mean, invstd, dbeta, dgamma, (float)(1.0 / (double)rows), n4, C, leaky, (float4*)dz);
+                       scale, shift, mean, invstd, dbeta, dgamma, (double)rows, n4, C, leaky, (float4*)dz);
     FV_LAUNCH_CHECK(ctx);
     return FV_OK;
 }

@@ -183,7 +183,7 @@ int fv_op_conv_wgrad(fv_ctx* ctx, const float* x, const float* dy, int B, int H,
                             bn_dy->dbeta && bn_dy->dgamma, "wgrad: the fused BN-backward apply needs its layer's tensors");
         a.bn_z = bn_dy->z; a.bn_scale = bn_dy->scale; a.bn_shift = bn_dy->shift; a.bn_mean = bn_dy->mean; a.bn_invstd = bn_dy->invstd;
         a.bn_slots = bn_dy->slots; a.bn_nslot = bn_dy->nslot; a.bn_leaky = bn_dy->leaky;
-        a.bn_inv_count = (float)(1.0 / (double)a.M);      // as fv_ew_bn_bwd forms it: rows = B * H * W
+        a.bn_count = (double)a.M;                         // as fv_ew_bn_bwd passes it: rows = B * H * W
         a.bn_dbeta = bn_dy->dbeta; a.bn_dgamma = bn_dy->dgamma; a.bn_accumulate = bn_dy->accumulate ? 1 : 0;
     }
     return fv_wgrad_launch(ctx, a);

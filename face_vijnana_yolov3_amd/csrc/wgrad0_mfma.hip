@@ -69,7 +69,7 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
         double sa, sb;
         fv_bn_slot_totals(a.bn_slots, a.bn_nslot, CN, tid, s_part, sa, sb);
         if (tid < CN) {
-            s_tot[tid] = (float)sa; s_tot[CN + tid] = (float)sb;
+            s_tot[tid] = fv_bn_mean_of((float)sa, a.bn_count); s_tot[CN + tid] = fv_bn_mean_of((float)sb, a.bn_count);   // dbeta / M, dgamma / M
             if (blockIdx.x == 0) {
                 if (a.bn_accumulate) { a.bn_dbeta[tid] += (float)sa; a.bn_dgamma[tid] += (float)sb; }
                 else { a.bn_dbeta[tid] = (float)sa; a.bn_dgamma[tid] = (float)sb; }
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(NTH, 3) void wgrad0_kernel(const FvWgradArgs a, int
                 const float4 o = fv_bn_bwd_dz4(
                     make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])),
                     make_float4(__uint_as_float(zv[0]), __uint_as_float(zv[1]), __uint_as_float(zv[2]), __uint_as_float(zv[3])),
-                    ksc, ksh, kmu, kis, kdb, kdg, a.bn_inv_count, a.bn_leaky);
+                    ksc, ksh, kmu, kis, kdb, kdg, a.bn_leaky);
                 const bool ok = (ry_ok >> p) & 1;
                 v[0] = ok ? __float_as_uint(o.x) : 0u; v[1] = ok ? __float_as_uint(o.y) : 0u;
                 v[2] = ok ? __float_as_uint(o.z) : 0u; v[3] = ok ? __float_as_uint(o.w) : 0u;
