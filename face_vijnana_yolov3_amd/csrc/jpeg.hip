@@ -5,11 +5,14 @@
 // about half of libjpeg-turbo's time per image).  fv_jpeg_parse / fv_jpeg_entropy_decode run on host threads and emit the
 // quantised coefficients (int16, natural order, one [64] block after another); fv_jpeg_reconstruct_batch turns the
 // coefficients of a whole batch into packed RGB on the device, where fv_letterbox_batch picks them up -- the RGB image never
-// exists on the host.  Arithmetic restated from the IJG / libjpeg-turbo sources so that the pixels are bit-identical to
-// Pillow's (the reference's reader): jdhuff.c, jidctint.c jpeg_idct_islow, jdsample.c h2v1/h2v2_fancy_upsample, jdcolor.c
-// ycc_rgb_convert; checked against Pillow itself (tests/test_jpeg_cpu.py, tests/test_jpeg_gpu.py) and against
-// oracle/jpeg_oracle.py.  Supported: SOF0 / SOF1 (8-bit, Huffman), 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0, restart
-// intervals.  Everything else returns FV_ERR_INVALID and the caller decodes that file with Pillow.
+// exists on the host.  Arithmetic restated from the IJG / libjpeg-turbo sources (jdhuff.c, jidctint.c jpeg_idct_islow,
+// jdsample.c h2v1/h2v2_fancy_upsample and their replicating fall-backs, jdcolor.c ycc_rgb_convert) so that, FOR EVERY STREAM
+// THE HOST HALF ACCEPTS, the pixels are bit-identical to Pillow's (the reference's reader); checked against Pillow itself
+// (tests/test_jpeg_cpu.py, tests/test_jpeg_gpu.py) and against oracle/jpeg_oracle.py.  Accepted: SOF0 / SOF1 (8-bit, Huffman),
+// 1 or 3 components that libjpeg takes for YCbCr, 4:4:4 / 4:2:2 / 4:2:0, restart intervals, a scan that is complete (no bit
+// taken from behind a marker or the end of the data, every RSTn in place, EOI behind the last MCU) and whose dequantised blocks
+// stay inside the range where libjpeg's 16-bit SIMD inverse DCT and its C one agree (block_in_range below, DESIGN.md
+// section 12).  Everything else returns FV_ERR_INVALID and the caller decodes that file with Pillow, which then decides.
 #include <cstring>
 #include "common.h"
 
@@ -64,6 +67,7 @@ int parse(const uint8_t* b, size_t n, Parsed& P) {
     bool have_qt[4] = {false, false, false, false}, have_sof = false;
     int tq[3] = {0, 0, 0}, cid[3] = {0, 0, 0};
     int adobe = -1;
+    bool jfif = false;
     while (p + 4 <= n) {
         if (b[p] != 0xFF) return FV_ERR_INVALID;
         while (p + 1 < n && b[p + 1] == 0xFF) ++p;      // fill bytes
@@ -116,6 +120,8 @@ int parse(const uint8_t* b, size_t n, Parsed& P) {
         } else if (m == 0xDD) {
             if (sl < 2) return FV_ERR_INVALID;
             P.info.restart_interval = (s[0] << 8) | s[1];
+        } else if (m == 0xE0 && sl >= 14 && memcmp(s, "JFIF", 5) == 0) {
+            jfif = true;
         } else if (m == 0xEE && sl >= 12 && memcmp(s, "Adobe", 5) == 0) {
             adobe = s[11];
         } else if (m == 0xDA) {
@@ -133,7 +139,11 @@ int parse(const uint8_t* b, size_t n, Parsed& P) {
         p += len;
     }
     if (!have_sof || !P.scan_begin || P.info.width < 1 || P.info.height < 1) return FV_ERR_INVALID;
+    // the colour space as libjpeg decides it (jdapimin.c default_decompress_parms): a JFIF APP0 means YCbCr; else an Adobe APP14
+    // decides by its transform; else the component ids do, and 'R','G','B' means RGB, which is not converted.  Only YCbCr is
+    // taken (an Adobe transform other than 1 is refused whatever else the file holds)
     if (P.info.ncomp == 3 && adobe != -1 && adobe != 1) return FV_ERR_INVALID;              // Adobe RGB / CMYK-style files
+    if (P.info.ncomp == 3 && !jfif && adobe == -1 && cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B') return FV_ERR_INVALID;
     int hmax = 1, vmax = 1;
     for (int i = 0; i < P.info.ncomp; ++i) {
         if (P.info.h[i] < 1 || P.info.h[i] > 2 || P.info.v[i] < 1 || P.info.v[i] > 2 || !have_qt[tq[i]]) return FV_ERR_INVALID;
@@ -156,11 +166,14 @@ int parse(const uint8_t* b, size_t n, Parsed& P) {
     return FV_OK;
 }
 
-// ---- bit reader (byte stuffing: FF 00 -> FF; any other FF xx is a marker: stop in front of it and feed zeros)
+// ---- bit reader (byte stuffing: FF 00 -> FF; any other FF xx is a marker: stop in front of it and feed zeros).  The zeros are
+// prefetch only: `invented` counts them, they are the LAST bits of the accumulator, so one of them was consumed exactly when
+// nbits < invented -- looked at where a restart interval or the scan ends (at_boundary), not per symbol
 struct BitReader {
     const uint8_t* p; const uint8_t* end;
     uint64_t acc = 0; int nbits = 0;
     bool marker = false;
+    int64_t invented = 0;
     inline void fill() {
         while (nbits <= 56) {
             unsigned byte = 0;
@@ -168,12 +181,27 @@ struct BitReader {
                 byte = *p++;
                 if (byte == 0xFF) {
                     if (p < end && *p == 0) ++p;
-                    else { --p; marker = true; byte = 0; }
+                    else { --p; marker = true; byte = 0; invented += 8; }
                 }
+            } else {
+                invented += 8;
             }
             acc = (acc << 8) | byte;
             nbits += 8;
         }
+    }
+    // The MCUs in front of a marker are decoded: true when no invented bit was consumed, less than one whole byte of real data
+    // is left over (the encoder's padding of the last byte), and the next bytes are FF, any number of fill FFs, `code`.  The
+    // reader then stands behind the marker with an empty accumulator
+    inline bool at_boundary(unsigned code) {
+        if (nbits < invented || nbits - invented >= 8) return false;
+        const uint8_t* q = p;
+        if (q >= end || *q != 0xFF) return false;
+        while (q < end && *q == 0xFF) ++q;
+        if (q >= end || *q != code) return false;
+        p = q + 1;
+        acc = 0; nbits = 0; invented = 0; marker = false;
+        return true;
     }
     inline unsigned peek(int n) { return (unsigned)((acc >> (nbits - n)) & ((1u << n) - 1)); }
     inline void skip(int n) { nbits -= n; }
@@ -181,6 +209,28 @@ struct BitReader {
 };
 
 inline int extend(unsigned v, int n) { return (int)v < (1 << (n - 1)) ? (int)v - (1 << n) + 1 : (int)v; }
+
+// The range of dequantised blocks this decoder takes.  With d[k][c] the dequantised coefficient of
+// vertical frequency k in column c and W_k = max_r |sqrt2 cos((2r+1) k pi / 16)| (1 for k = 0, 4; 1.38704 for odd k; 1.30656
+// for k = 2, 6), U_c = sum_k W_k |d[k][c]| bounds |pass-1 output| / 4 of jpeg_idct_islow for column c.  libjpeg-turbo's SIMD
+// version keeps the pass-1 outputs in 16 bits and adds pairs of them in 16 bits, so it equals the C code (and the kernel below)
+// as long as U_a + U_b <= 8190 for any two columns: 4 * 8190 + rounding < 32768.  Weights in 1/1024, rounded up.
+constexpr int kRangeFast = 5900;                 // sum |d| over the block <= 5900 implies the above: 1.38704 * 5900 < 8190
+constexpr int64_t kRangeB = 8190;
+inline bool block_in_range(const int16_t* blk, const uint16_t* qt) {
+    static const int W[8] = {1024, 1421, 1338, 1421, 1024, 1421, 1338, 1421};
+    int64_t top = 0, second = 0;
+    for (int c = 0; c < 8; ++c) {
+        int64_t u = 0;
+        for (int k = 0; k < 8; ++k) {
+            const int v = blk[k * 8 + c];
+            u += (int64_t)W[k] * (v < 0 ? -v : v) * qt[k * 8 + c];
+        }
+        if (u > top) { second = top; top = u; }
+        else if (u > second) second = u;
+    }
+    return top + second <= kRangeB * 1024;
+}
 
 inline int decode_symbol(BitReader& br, const HuffDec& d) {
     if (br.nbits < 16) br.fill();
@@ -221,15 +271,15 @@ int fv_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, i
     BitReader br{data + P.scan_begin, data + nbytes};
     int pred[3] = {0, 0, 0};
     int to_go = I.restart_interval;
+    unsigned next_rst = 0xD0;
     for (int my = 0; my < mcuy; ++my)
         for (int mx = 0; mx < mcux; ++mx) {
             if (I.restart_interval) {
                 if (to_go == 0) {
-                    // byte-align, step over the RSTn marker (resynchronise on the next one if the stream is damaged)
-                    br.nbits = 0; br.acc = 0; br.marker = false;
-                    const uint8_t* q = br.p;
-                    while (q + 1 < br.end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
-                    br.p = q + 2 <= br.end ? q + 2 : br.end;
+                    // the interval is over: exactly here stands RSTn with the expected n, or the file is left to Pillow (libjpeg
+                    // would resynchronise with a warning; what it then makes of the data is its own affair)
+                    if (!br.at_boundary(next_rst)) return FV_ERR_INVALID;
+                    next_rst = 0xD0 | ((next_rst + 1) & 7);
                     pred[0] = pred[1] = pred[2] = 0;
                     to_go = I.restart_interval;
                 }
@@ -238,6 +288,7 @@ int fv_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, i
             for (int c = 0; c < I.ncomp; ++c) {
                 const HuffDec& hd = dc[P.td[c]];
                 const HuffDec& ha = ac[P.ta[c]];
+                const uint16_t* qc = I.qt[c];
                 for (int by = 0; by < I.v[c]; ++by)
                     for (int bx = 0; bx < I.h[c]; ++bx) {
                         int16_t* blk = coefs + I.coef_off[c] + ((int64_t)(my * I.v[c] + by) * I.blocks_w[c] + mx * I.h[c] + bx) * 64;
@@ -247,7 +298,10 @@ int fv_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, i
                             if (br.nbits < s) br.fill();
                             pred[c] += extend(br.get(s), s);
                         }
+                        const int dcmag = pred[c] < 0 ? -pred[c] : pred[c];
+                        if (dcmag > 32767) return FV_ERR_INVALID;                         // libjpeg keeps the DC in 16 bits too
                         blk[0] = (int16_t)pred[c];
+                        int mag = dcmag * qc[0];          // sum |dequantised coefficient| of the block: below 2^30 whatever the file
                         for (int k = 1; k < 64;) {
                             const int rs = decode_symbol(br, ha);
                             if (rs < 0) return FV_ERR_INVALID;
@@ -260,12 +314,18 @@ int fv_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, i
                             k += r;
                             if (k > 63) return FV_ERR_INVALID;
                             if (br.nbits < sz) br.fill();
-                            blk[kZigzag[k]] = (int16_t)extend(br.get(sz), sz);
+                            const int v = extend(br.get(sz), sz);
+                            const int at = kZigzag[k];
+                            blk[at] = (int16_t)v;
+                            mag += (v < 0 ? -v : v) * qc[at];
                             ++k;
                         }
+                        if (mag > kRangeFast && !block_in_range(blk, qc)) return FV_ERR_INVALID;
                     }
             }
         }
+    // behind the last MCU: EOI (fill bytes allowed), and no bit of the image was invented
+    if (!br.at_boundary(0xD9)) return FV_ERR_INVALID;
     return FV_OK;
 }
 
@@ -345,13 +405,14 @@ __global__ __launch_bounds__(128) void jpeg_idct_kernel(const int16_t* __restric
     }
 }
 
-// chroma sample at full resolution (jdsample.c fancy upsampling; edges replicate the last real row / column, jdmainct.c)
+// chroma sample at full resolution (jdsample.c: fancy upsampling where the downsampled width is above 2, else jinit_upsampler
+// picks the replicating h2v1_upsample / h2v2_upsample, in both directions; edges replicate the last real row / column, jdmainct.c)
 __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int stride, int cw, int ch, int x, int y, int fh, int fv) {
     if (fh == 1) return p[(long long)y * stride + x];
     const int cx = x >> 1;
+    if (cw <= 2) return p[(long long)(y >> (fv - 1)) * stride + cx];
     if (fv == 1) {                                                // h2v1
         const int v = p[(long long)y * stride + cx];
-        if (cw == 1) return v;
         if (x & 1) return cx == cw - 1 ? v : (3 * v + p[(long long)y * stride + cx + 1] + 2) >> 2;
         return cx == 0 ? v : (3 * v + p[(long long)y * stride + cx - 1] + 1) >> 2;
     }

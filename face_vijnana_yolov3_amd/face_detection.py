@@ -529,8 +529,9 @@ class FaceDetector(object):
                                     range(len(chunk)))
                             return None, ('jpeg', buf, plan)
                         except ValueError:
-                            # damaged scan data (a bad Huffman code, a run past the block): libjpeg -- the reference's reader
-                            # (skimage.io.imread, fd.py:798) -- only warns and returns an image; so the batch goes through Pillow.
+                            # scan data the strict decoder refuses (a bad Huffman code, a run past the block, a cut scan, a
+                            # misplaced RSTn, an out-of-range block): libjpeg -- the reference's reader (skimage.io.imread,
+                            # fd.py:798) -- warns and returns an image, or raises; either way the batch goes through Pillow.
                             # map_all has waited for every decoder task: nothing writes into the slot any more
                             ring.untake()
                 raws = list(pool.map(data._pil_loader, chunk))
@@ -780,7 +781,8 @@ class BatchFeeder(object):
             map_all(self.pool, lambda i: jpeg.entropy_decode(datas[i], infos[i], view[plan.coef_off[i]:plan.coef_off[i] + int(infos[i].total_coefs)]),
                     range(len(names)))
         except ValueError:
-            # damaged scan data: libjpeg (the reference's reader, fd.py:112) warns and still returns an image -- Pillow path
+            # scan data the strict decoder refuses: libjpeg (the reference's reader, fd.py:112) warns and still returns an image,
+            # or raises (a truncated file) -- Pillow path, which then does what the reference does
             # (every decoder task has finished: map_all waits for all of them before it raises)
             if slot is not None:
                 self.ring.untake()

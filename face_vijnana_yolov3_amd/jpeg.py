@@ -5,7 +5,9 @@
     entropy_decode(data, info, out_int16)    # quantised coefficients into a (pinned) host buffer; releases the GIL
     rgb = reconstruct_batch(ctx, ...)        # dequantise + IDCT + chroma upsampling + YCbCr->RGB for a whole batch
 
-The pixels are bit-identical to Pillow's (tests/test_jpeg_cpu.py, tests/test_jpeg_gpu.py).
+For every stream that parse() and entropy_decode() ACCEPT, the pixels are bit-identical to Pillow's; whatever cannot be held to
+that is refused -- parse() returns None, entropy_decode() raises ValueError -- and the caller decodes the file with Pillow, which
+then decides (tests/test_jpeg_cpu.py, tests/test_jpeg_gpu.py; DESIGN.md section 12 lists what is refused and why).
 
 JPEG output without a host-side image either (csrc/jpeg_enc.hip):
 
@@ -75,7 +77,7 @@ MAX_PIXELS = 178956970
 
 def parse(data):
     """JPEG bytes -> JpegInfo, or None when the file is not one this decoder takes (progressive, arithmetic-coded, CMYK, 12-bit,
-    unusual sampling, damaged header)."""
+    unusual sampling, three components that libjpeg would not take for YCbCr, damaged header)."""
     info = JpegInfo()
     data = data if isinstance(data, bytes) else bytes(data)
     rc = _fn().fv_jpeg_parse(ctypes.c_char_p(data), len(data), ctypes.byref(info))
@@ -86,7 +88,9 @@ def parse(data):
 
 def entropy_decode(data, info, out=None):
     """Huffman-decode the scan into `out` (int16 numpy array / memory of at least info.total_coefs elements; allocated when
-    None).  ctypes releases the GIL for the duration of the call: a thread pool decodes in parallel.  -> the int16 array."""
+    None).  ctypes releases the GIL for the duration of the call: a thread pool decodes in parallel.  -> the int16 array.
+    ValueError for a scan the decoder does not take: a bad code, a scan that is cut or lacks its EOI, an RSTn that is missing,
+    misplaced or misnumbered, a block outside the coefficient range in which libjpeg's inverse DCTs agree."""
     n = int(info.total_coefs)
     if out is None:
         out = np.empty(n, np.int16)
@@ -94,7 +98,7 @@ def entropy_decode(data, info, out=None):
     data = data if isinstance(data, bytes) else bytes(data)
     rc = _fn().fv_jpeg_entropy_decode(ctypes.c_char_p(data), len(data), ctypes.c_void_p(out.ctypes.data), out.size)
     if rc != 0:
-        raise ValueError('fv_jpeg_entropy_decode failed (%d): damaged scan data' % rc)
+        raise ValueError('fv_jpeg_entropy_decode failed (%d): damaged, incomplete or out-of-range scan data' % rc)
     return out
 
 

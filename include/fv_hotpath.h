@@ -523,8 +523,11 @@ int fv_draw_prims_u8(fv_ctx* ctx, uint8_t* packed, const int64_t* offsets, const
  * The host part (no context, thread-safe, pure CPU) parses the headers and Huffman-decodes the scan into quantised coefficients:
  * int16, natural (de-zigzagged) order, [64] per block, component after component, each component's block grid padded to whole
  * MCUs in raster order.  The device part dequantises, inverse-transforms (libjpeg's jpeg_idct_islow), upsamples the chroma
- * (libjpeg's "fancy" triangle filters) and converts YCbCr -> RGB for a whole batch in two launches: pixels bit-identical to
- * libjpeg-turbo's default decode (what Pillow / scikit-image return). */
+ * (libjpeg's "fancy" triangle filters, its replicating ones where there are at most two chroma columns) and converts
+ * YCbCr -> RGB for a whole batch in two launches: for every stream the host part ACCEPTS, pixels bit-identical to
+ * libjpeg-turbo's default decode (what Pillow / scikit-image return).  The host part refuses (FV_ERR_INVALID) whatever it cannot
+ * hold to that: colour spaces other than libjpeg's YCbCr decision, a scan that is cut, lacks or misnumbers an RSTn or lacks its
+ * EOI, a block outside the coefficient range in which libjpeg's inverse DCTs agree. */
 typedef struct fv_jpeg_info {
     int32_t width, height, ncomp, hmax, vmax, restart_interval;
     int32_t h[3], v[3], blocks_w[3], blocks_h[3];

@@ -7,8 +7,9 @@ Pinned by Pillow itself, which is importable here and on the GPU box: tests/test
 `PIL.Image.open(f).convert('RGB')` exactly; the product's host entropy decoder and device kernels are then checked against both.
 
 Algorithms restated from the IJG / libjpeg-turbo sources (third party, not in /root/reference): jdhuff.c (Huffman decoding),
-jidctint.c `jpeg_idct_islow` (CONST_BITS 13, PASS1_BITS 2), jdsample.c `h2v1_fancy_upsample` / `h2v2_fancy_upsample`,
-jdcolor.c `ycc_rgb_convert` (SCALEBITS 16), jdmainct.c edge handling (the last real row / column is replicated)."""
+jidctint.c `jpeg_idct_islow` (CONST_BITS 13, PASS1_BITS 2), jdsample.c `h2v1_fancy_upsample` / `h2v2_fancy_upsample` (both
+called with more than two chroma columns only) and the replicating `h2v1_upsample` / `h2v2_upsample` that `jinit_upsampler`
+selects for a downsampled width of 1 or 2, jdcolor.c `ycc_rgb_convert` (SCALEBITS 16), jdmainct.c edge handling (the last real row / column is replicated)."""
 import numpy as np
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -66,7 +67,9 @@ def parse(buf):
                 q += 17 + ns
         elif m == 0xDD:
             info['ri'] = (seg[0] << 8) | seg[1]
-        elif m == 0xEE and seg[:5] == b'Adobe':
+        elif m == 0xE0 and len(seg) >= 14 and seg[:5] == b'JFIF\0':
+            info['jfif'] = True
+        elif m == 0xEE and len(seg) >= 12 and seg[:5] == b'Adobe':
             info['adobe'] = seg[11]
         elif m == 0xDA:
             ns = seg[0]
@@ -85,8 +88,13 @@ def parse(buf):
     nc = len(info['comps'])
     if nc not in (1, 3):
         raise Unsupported('%d components' % nc)
+    if nc == 1:
+        info['comps'][0]['h'] = info['comps'][0]['v'] = 1       # a single component is never subsampled: one block per MCU
     if nc == 3 and info['adobe'] not in (None, 1):
         raise Unsupported('Adobe transform %r (not YCbCr)' % info['adobe'])
+    if nc == 3 and not info.get('jfif') and info['adobe'] is None and [c['id'] for c in info['comps']] == [82, 71, 66]:
+        # jdapimin.c default_decompress_parms: no JFIF, no Adobe marker -> the component ids decide, and 'R','G','B' is RGB
+        raise Unsupported("component ids 'R','G','B' without JFIF / Adobe marker: RGB, not YCbCr")
     return info
 
 
@@ -240,9 +248,6 @@ def _h2v1_fancy(row):
     x = row.astype(np.int32)
     w = x.shape[-1]
     out = np.empty(x.shape[:-1] + (2 * w,), np.int32)
-    if w == 1:
-        out[..., 0] = x[..., 0]; out[..., 1] = x[..., 0]
-        return out.astype(np.uint8)
     left = np.concatenate([x[..., :1], x[..., :-1]], -1)
     right = np.concatenate([x[..., 1:], x[..., -1:]], -1)
     out[..., 0::2] = (3 * x + left + 1) >> 2
@@ -265,12 +270,8 @@ def _h2v2_fancy(plane):
         nxt = np.concatenate([col[:, 1:], col[:, -1:]], 1)
         even = (3 * col + last + 8) >> 4
         odd = (3 * col + nxt + 7) >> 4
-        if w == 1:
-            even = odd = (4 * col + 8) >> 4
-            odd = (4 * col + 7) >> 4
-        else:
-            even[:, 0] = (4 * col[:, 0] + 8) >> 4
-            odd[:, -1] = (4 * col[:, -1] + 7) >> 4
+        even[:, 0] = (4 * col[:, 0] + 8) >> 4
+        odd[:, -1] = (4 * col[:, -1] + 7) >> 4
         out[v::2, 0::2] = even
         out[v::2, 1::2] = odd
     return out.astype(np.uint8)
@@ -285,6 +286,10 @@ def upsample(info, pl):
         fh, fv = hmax // c['h'], vmax // c['v']
         if (fh, fv) == (1, 1):
             u = p
+        elif fh == 2 and fv in (1, 2) and p.shape[1] <= 2:
+            # jinit_upsampler takes the fancy upsamplers only when downsampled_width > 2; below that h2v1_upsample /
+            # h2v2_upsample replicate every sample, in both directions
+            u = np.repeat(np.repeat(p, fv, axis=0), 2, axis=1)
         elif (fh, fv) == (2, 1):
             u = _h2v1_fancy(p)
         elif (fh, fv) == (2, 2):

@@ -2,7 +2,9 @@
 pixels the device reconstructs from the host's Huffman-decoded coefficients are bit-identical to Pillow's -- the reference's
 reader (`imread`, face_detection.py:112, 656, 798) -- for every sampling mode, odd sizes, restart intervals and mixed batches;
 the letterboxed network input is therefore the same tensor as through the Pillow path, and FaceDetector.test() writes the
-same rows either way."""
+same rows either way.  The differential contract of DESIGN.md section 12 on the device: every size 1..24 x 1..24, every file of
+the stream corpus (tests/jpeg_stream_ref.py) that the host half accepts, the kernels' grid-stride loops, and a truncated file
+through every loader."""
 import io
 import os
 
@@ -43,6 +45,130 @@ def test_device_pixels_equal_pillow_in_one_mixed_batch(ctx):
     for c, d, g in zip(cases, datas, got):
         want = np.asarray(Image.open(io.BytesIO(d)).convert('RGB'))
         assert g.shape == want.shape and np.array_equal(g, want), (c, int(np.abs(g.astype(int) - want.astype(int)).max()))
+
+
+def _against_pillow(names, datas, got):
+    bad = []
+    for name, d, g in zip(names, datas, got):
+        want = np.asarray(Image.open(io.BytesIO(d)).convert('RGB'))
+        if g.shape != want.shape or not np.array_equal(g, want):
+            bad.append((name, 'shape' if g.shape != want.shape else int(np.abs(g.astype(int) - want.astype(int)).max())))
+    return bad
+
+
+def test_size_sweep_on_the_device_equals_pillow(ctx):
+    """Every size 1..24 x 1..24 in every sampling mode (the CPU sweep's 2304 files) in ONE mixed batch: jpeg_color_kernel's
+    chroma_at replicates where the image has at most two chroma columns, as libjpeg's jinit_upsampler selects."""
+    from test_jpeg_cpu import sweep_files
+    names, datas = zip(*sweep_files())
+    got, _plan = _device_decode(ctx, list(datas))
+    bad = _against_pillow(names, datas, got)
+    assert not bad, (len(bad), bad[:20])
+
+
+def test_stream_corpus_on_the_device_equals_pillow(ctx):
+    """Every file of the stream corpus that the host half accepts, in one mixed batch: device pixels == Pillow's, per file --
+    among them the blocks AT the bound of the accepted coefficient range (int32 dequantisation, 64-bit IDCT temporaries)."""
+    import jpeg_stream_ref as sr
+    from test_jpeg_cpu import _product
+    files = [(name, data) for name, data, _planes, _expect in sr.corpus() if _product(data) is not None]
+    assert len(files) >= 100 and {'aligned_at_bound', 'random_at_bound', 'gray_long_ri1', 'ac_size_10'} <= {n for n, _ in files}
+    names, datas = zip(*files)
+    got, _plan = _device_decode(ctx, list(datas))
+    bad = _against_pillow(names, datas, got)
+    assert not bad, bad
+
+
+def test_grid_size_does_not_change_the_pixels(ctx):
+    """fv_jpeg_reconstruct_batch with the plan's max_blocks / max_pixels (the grid size) and with both 1: one workgroup per
+    image walks every block and every pixel in the kernels' grid-stride loops -- the same RGB buffer, and Pillow's."""
+    from face_vijnana_yolov3_amd import jpeg
+    from face_vijnana_yolov3_amd._lib import ptr
+    rng = np.random.default_rng(10)
+    cases = [(33, 17, 2, 80, False, 0), (100, 130, 1, 30, False, 2), (40, 56, 0, 85, True, 0), (45, 67, 0, 90, False, 0), (150, 90, 2, 75, False, 5)]
+    datas = [_jpeg(rng, *c) for c in cases]
+    infos = [jpeg.parse(d) for d in datas]
+    plan = jpeg.BatchPlan(infos)
+    assert plan.max_blocks > 128 and plan.max_pixels > 256          # more than one workgroup's worth: the loops do iterate
+    coefs = np.empty(plan.total_coefs, np.int16)
+    for i, d in enumerate(datas):
+        jpeg.entropy_decode(d, infos[i], coefs[plan.coef_off[i]:plan.coef_off[i] + int(infos[i].total_coefs)])
+    dev = torch.device('cuda', 0)
+    coefs_dev = torch.from_numpy(coefs).to(dev)
+    descs = torch.frombuffer(bytearray(bytes(plan.descs)), dtype=torch.uint8).to(dev)
+    out = []
+    for max_blocks, max_pixels in ((plan.max_blocks, plan.max_pixels), (1, 1)):
+        planes = torch.zeros(plan.plane_bytes, dtype=torch.uint8, device=dev)
+        rgb = torch.full((plan.rgb_bytes,), 77, dtype=torch.uint8, device=dev)
+        rc = jpeg._fn().fv_jpeg_reconstruct_batch(ctx.handle, ptr(coefs_dev), ptr(descs), plan.n, ptr(planes), ptr(rgb), max_blocks, max_pixels)
+        ctx.check(rc, 'fv_jpeg_reconstruct_batch')
+        out.append(rgb.cpu().numpy())
+    assert np.array_equal(out[0], out[1])
+    got = [out[1][plan.rgb_off[i]:plan.rgb_off[i] + I.height * I.width * 3].reshape(I.height, I.width, 3) for i, I in enumerate(infos)]
+    assert not _against_pillow(cases, datas, got)
+
+
+def test_letterbox_of_narrow_images_from_coefficients_equals_pillow(ctx):
+    """3 x 40 and 40 x 3 as 4:2:0 (one and two chroma columns / rows) through letterbox_batch_device, from coefficients and from
+    Pillow's pixels: the same tensor."""
+    from face_vijnana_yolov3_amd import jpeg
+    from face_vijnana_yolov3_amd.postproc import letterbox_batch_device
+    rng = np.random.default_rng(12)
+    datas = [_jpeg(rng, h, w, 2, 88) for (h, w) in [(3, 40), (40, 3), (4, 40), (40, 4)]]
+    infos = [jpeg.parse(d) for d in datas]
+    plan = jpeg.BatchPlan(infos)
+    coefs = torch.empty(plan.total_coefs, dtype=torch.int16).pin_memory()
+    for i, d in enumerate(datas):
+        jpeg.entropy_decode(d, infos[i], coefs.numpy()[plan.coef_off[i]:plan.coef_off[i] + int(infos[i].total_coefs)])
+    dev = torch.device('cuda', 0)
+    x1, g1 = letterbox_batch_device(ctx, None, 96, dev, packed=('jpeg', coefs, plan))
+    raws = [np.asarray(Image.open(io.BytesIO(d)).convert('RGB')) for d in datas]
+    x2, g2 = letterbox_batch_device(ctx, raws, 96, dev)
+    assert g1 == g2 and torch.equal(x1, x2)
+
+
+def test_loaders_treat_a_truncated_file_as_pillow_does(ctx, tmp_path, monkeypatch):
+    """A file cut in the middle of its scan (Pillow: OSError) through the three other callers of entropy_decode: FaceDetector.test()
+    with hps.device_jpeg on and off, create_db's load_batch with device_jpeg on and off, CropStore.load against Pillow's reader --
+    the same exception type either way; each caller hands the file the strict scan refuses to Pillow, which raises."""
+    from concurrent.futures import ThreadPoolExecutor
+    from face_vijnana_yolov3_amd import crop_store, face_detection
+    from face_vijnana_yolov3_amd import face_identification as fi
+    from face_vijnana_yolov3_amd.face_detection import FaceDetector
+    from face_vijnana_yolov3_amd.postproc import PinnedRing
+    from test_jpeg_cpu import _outcome, truncated_file
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(face_detection, 'DEBUG', False)
+    root = str(tmp_path / 'imgs'); os.makedirs(root)
+    rng = np.random.default_rng(13)
+    good, bad = truncated_file(rng, 64, 64)
+    paths = [os.path.join(root, n) for n in ('img_0.jpg', 'img_1.jpg')]
+    open(paths[0], 'wb').write(good)
+    open(paths[1], 'wb').write(bad)
+    # create_db: load_batch
+    with ThreadPoolExecutor(max_workers=2) as pool:
+        ring = PinnedRing(3)
+        a, b = (_outcome(lambda: fi.load_batch(paths, pool, ring, dj)) for dj in (True, False))
+        assert a[0] == b[0] == 'raised' and a[1] is b[1] is OSError, (a, b)
+        assert fi.load_batch(paths[:1], pool, ring, True)[0] == 'jpeg'                        # the ring is usable afterwards
+        # the crop store: the damaged file alone goes to Pillow
+        store = crop_store.CropStore(ctx, 2, 64, torch.device('cuda', 0))
+        a, b = _outcome(lambda: store.load(paths, [0, 1], pool)), _outcome(lambda: fi._imread(paths[1]))
+        assert a[0] == b[0] == 'raised' and a[1] is b[1] is OSError, (a, b)
+        store.load(paths[:1], [1], pool)
+        assert np.array_equal(store.data[1].cpu().numpy(), fi._imread(paths[0]))
+    # FaceDetector.test()
+    conf = {'mode': 'test', 'raw_data_path': root, 'test_path': root, 'output_file_path': os.path.join(root, 'a.csv'), 'multi_gpu': False,
+            'num_gpus': 1, 'yolov3_base_model_load': False, 'model_loading': False,
+            'hps': {'lr': 1e-4, 'beta_1': 0.99, 'beta_2': 0.99, 'decay': 0.0, 'epochs': 1, 'step': 1, 'batch_size': 2, 'face_conf_th': 0.5,
+                    'nms_iou_th': 0.5, 'num_cands': 60, 'eval_batch_size': 2},
+            'nn_arch': {'image_size': 96, 'bb_info_c_size': 6}}
+    fd = FaceDetector(conf)
+    a = _outcome(fd.test)
+    conf['hps']['device_jpeg'] = False
+    fd.conf = dict(conf, output_file_path=os.path.join(root, 'b.csv'))
+    b = _outcome(fd.test)
+    assert a[0] == b[0] == 'raised' and a[1] is b[1] is OSError, (a, b)
 
 
 def test_letterbox_from_coefficients_equals_letterbox_from_pillow(ctx):
