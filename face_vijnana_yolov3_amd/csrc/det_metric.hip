@@ -10,7 +10,7 @@
 //                          trapezoid terms summed in a fixed order
 //
 // No float atomics anywhere: every sum has one order, whatever the launch geometry.  Integer LDS atomics only count.
-#include "common.h"
+#include "block_ops.h"
 #include "bbox_iou.h"
 
 namespace {
@@ -110,20 +110,12 @@ __global__ __launch_bounds__(256) void det_match_kernel(const double* __restrict
             const double v = s_best[g];
             if (v > lb) { lb = v; lg = g; }                          // ascending g: equal IoUs keep the smaller box
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_down(lb, o);
-            const int og = __shfl_down(lg, o);
-            if (ob > lb || (ob == lb && og < lg)) { lb = ob; lg = og; }
-        }
+        fv_wave_best<max_more>(lb, lg);
         if (lane == 0) { s_riou[wave] = lb; s_rg[wave] = lg; }
         __syncthreads();
-        double bb = s_riou[0];
-        int bg = s_rg[0];
-        for (int w = 1; w < 4; ++w) {
-            const double ob = s_riou[w];
-            const int og = s_rg[w];
-            if (ob > bb || (ob == bb && og < bg)) { bb = ob; bg = og; }
-        }
+        double bb;
+        int bg;
+        fv_block_best<max_more, 4>(s_riou, s_rg, 1, bb, bg);
         if (!(bb > 0.0)) break;                                      // uniform: every thread computed the same pair
         any = true;
         const int bd = s_bd[bg];
@@ -141,14 +133,6 @@ __global__ __launch_bounds__(256) void det_match_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ scans
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // In-place exclusive scan of data[seg * stride + 0 .. n), the total stored at data[seg * stride + n]; one workgroup per segment.
 __global__ __launch_bounds__(1024) void scan_excl_kernel(int* __restrict__ data, long long n, long long stride) {
     __shared__ int s_w[16];
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(1024) void scan_excl_kernel(int* __restrict__ data,
     for (long long base = 0; base < n; base += 1024) {
         const long long i = base + tid;
         const int v = i < n ? d[i] : 0;
-        const int inc = wave_incl_scan(v, lane);
+        const int inc = fv_wave_incl_scan(v, lane);
         if (lane == 63) s_w[wave] = inc;
         __syncthreads();
         int before = 0, total = 0;
@@ -271,7 +255,7 @@ __global__ __launch_bounds__(256) void ap_tp_count_kernel(const int* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x, t = blockIdx.y;
     const int N = *n_ptr;
     int c = __popc(tp_bits(idx, iou_c, (long long)blk * TILE + tid * 8, N, ths.th[t]));
-    c = wave_incl_scan(c, lane);
+    c = fv_wave_incl_scan(c, lane);
     if (lane == 63) s_w[wave] = c;
     __syncthreads();
     if (tid == 0) blk_cnt[(long long)t * (nblk + 1) + blk] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -288,7 +272,7 @@ __global__ __launch_bounds__(256) void ap_sweep_kernel(const int* __restrict__ i
     const long long k0 = (long long)blk * TILE + tid * 8;
     const unsigned bits = tp_bits(idx, iou_c, k0, N, ths.th[t]);
     const int mine = __popc(bits);
-    const int inc = wave_incl_scan(mine, lane);
+    const int inc = fv_wave_incl_scan(mine, lane);
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
     int tp = blk_cnt[(long long)t * (nblk + 1) + blk] + inc - mine;          // true positives among the ranks before k0
@@ -309,7 +293,7 @@ __global__ __launch_bounds__(256) void ap_sweep_kernel(const int* __restrict__ i
             sum += (rk - rp) * (pk + pp) / 2.0;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);   // lane 0 holds fv_wave_sum's tree
     if (lane == 0) s_a[wave] = sum;
     __syncthreads();
     if (tid == 0) blk_ap[(long long)t * nblk + blk] = ((s_a[0] + s_a[1]) + s_a[2]) + s_a[3];

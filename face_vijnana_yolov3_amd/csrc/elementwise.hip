@@ -7,6 +7,7 @@
 // the order of the fp64 additions varies, far below fp32 resolution -- see DESIGN.md 4.3).
 #include <string>
 #include "elementwise.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -30,10 +31,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     }
     ssum[rl][cl] = s; ssq[rl][cl] = q;
     __syncthreads();
-    for (int st = 64; st > 0; st >>= 1) {   // fixed-order tree: deterministic
-        if (rl < st) { ssum[rl][cl] += ssum[rl + st][cl]; ssq[rl][cl] += ssq[rl + st][cl]; }
-        __syncthreads();
-    }
+    fv_block_tree_sum2(ssum, ssq, rl, cl);   // fixed-order tree: deterministic
     if (rl == 0 && c < C) {
         s = ssum[0][cl]; q = ssq[0][cl];
         double mean = s / count;
@@ -207,10 +205,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
     }
     s1[rl][cl] = a; s2[rl][cl] = b;
     __syncthreads();
-    for (int st = 64; st > 0; st >>= 1) {
-        if (rl < st) { s1[rl][cl] += s1[rl + st][cl]; s2[rl][cl] += s2[rl + st][cl]; }
-        __syncthreads();
-    }
+    fv_block_tree_sum2(s1, s2, rl, cl);
     if (rl == 0 && c < C) {
         if (accumulate) { dbeta[c] += (float)s1[0][cl]; dgamma[c] += (float)s2[0][cl]; }
         else { dbeta[c] = (float)s1[0][cl]; dgamma[c] = (float)s2[0][cl]; }
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ yp,
     }
     sred[threadIdx.x] = acc;
     __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
+    fv_block_tree_sum<1024>(sred, threadIdx.x);
     if (threadIdx.x == 0) *loss = (float)(sred[0] / (double)n);
     if (dbias) {
         // column sums: thread = (row lane, column); C <= 32
@@ -338,8 +333,7 @@ __global__ __launch_bounds__(256) void mse_part_kernel(const float* __restrict__
         for (int cc = c; cc < Cpad; cc += 32) dy[(size_t)r * Cpad + cc] = cc < C ? d : 0.f;
     }
     // wave reduction of the squared error (64 lanes = 2 row lanes x 32 columns), then the 4 waves
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = fv_wave_sum(acc);
     if ((tid & 63) == 0) s_acc[tid >> 6] = acc;
     s_col[rl][c] = col;
     __syncthreads();
@@ -395,7 +389,7 @@ __global__ __launch_bounds__(1024) void fd_loss_kernel(const float* __restrict__
     }
     sred[threadIdx.x] = acc;
     __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
+    fv_block_tree_sum<1024>(sred, threadIdx.x);
     if (threadIdx.x == 0) *loss = (float)(sred[0] / (double)cells);
 }
 
@@ -917,9 +911,7 @@ __global__ __launch_bounds__(256) void yolo_loss_part_kernel(const float* __rest
             }
             gp[e] = (float)(g * gs);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
-        acc += l / 3.0;
+        acc += fv_wave_sum(l) / 3.0;
         if (an == A - 1) for (int e = A * E + lane; e < Cpad; e += 64) dy[cell * Cpad + e] = 0.f;   // padding columns
     }
     if (lane == 0) s_w[wave] = acc;

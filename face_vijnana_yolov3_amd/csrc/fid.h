@@ -2,7 +2,7 @@
 // Dense(64, relu) -> l2_normalize, the triplet loss (fi.py:72-76) and the dense layer's two gradients.  All fp32 FMA on the vector
 // units, every sum in a fixed order (no atomics): the same rows give the same bits, whatever else is in the batch.
 #pragma once
-#include "common.h"
+#include "block_ops.h"
 
 constexpr int FID_DIM = 64;    // nn_arch.dense1_dim; the loss slices 0:64 / 64:128 / 128:192 are hard-coded in the reference
 constexpr int FID_KC = 256;    // F per forward partial: fixed, so a row's summation order does not depend on the batch
@@ -11,23 +11,16 @@ constexpr int FID_KC = 256;    // F per forward partial: fixed, so a row's summa
 // maps [per][F] read (written) in place, tower-major.
 struct FidRows { float* p[3]; int per; };
 
-// wave-wide fp64 sum (butterfly), the value of lane 0 broadcast so that every lane holds the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return __shfl(v, 0);
-}
-
 // d pre of one row from d u: back through l2_normalize (the rsqrt factor s is a constant where sum x^2 <= 1e-12) and ReLU (TF's
 // ReluGrad: passes only where pre > 0).  `weight` multiplies the fp64 result once, where it is rounded to float: a power of two
 // scales the stored value exactly.
 __device__ __forceinline__ float l2_relu_bwd(float y, double du, double weight) {
     const double r = y > 0.f ? (double)y : 0.0;
-    const double ss = wave_sum(r * r);
+    const double ss = fv_wave_sum_all(r * r);
     double dr;
     if (ss > 1e-12) {
         const double s = 1.0 / sqrt(ss), uu = r * s;
-        dr = s * (du - uu * wave_sum(uu * du));
+        dr = s * (du - uu * fv_wave_sum_all(uu * du));
     } else {
         dr = du * 1e6;
     }

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void fid_dense_finish_kernel(const 
     for (int k = 0; k < FIN_WAVES; ++k) s += s_part[k][n];
     const float y = (float)s + bias[n];
     const float r = y > 0.f ? y : 0.f;
-    const double ss = wave_sum((double)r * (double)r);
+    const double ss = fv_wave_sum_all((double)r * (double)r);
     const double inv = 1.0 / sqrt(ss > 1e-12 ? ss : 1e-12);
     if (pre) pre[(long long)m * FID_DIM + n] = y;
     u[(long long)m * FID_DIM + n] = (float)((double)r * inv);
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void fid_triplet_kernel(const float* __restric
         // differences in fp64 (exact): an fp32 difference is off by 2^-24 of itself, and where a row's gradient nearly cancels in
         // the projection of l2_relu_bwd that rounding came out many times larger than 2^-24 of the result
         const double dap = (double)u[ra] - (double)u[rp], dan = (double)u[ra] - (double)u[rn];
-        const double dp = sqrt(wave_sum(dap * dap)), dn = sqrt(wave_sum(dan * dan));
+        const double dp = sqrt(fv_wave_sum_all(dap * dap)), dn = sqrt(fv_wave_sum_all(dan * dan));
         const double h = dp - dn + 0.2;
         lsum += h > 0.0 ? h : 0.0;
         double ga = 0.0, gp = 0.0, gn = 0.0;
@@ -174,9 +174,7 @@ __global__ __launch_bounds__(256) void fid_dense_bias_kernel(const float* __rest
 __global__ __launch_bounds__(256) void fid_ids_l2_relu_kernel(const float* __restrict__ ids, int M, float* __restrict__ u) {
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6), n = threadIdx.x & 63;
     const float v = m < M ? ids[(long long)m * FID_DIM + n] : 0.f;
-    float s = v * v;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float s = fv_wave_sum(v * v);
     const float r = v * (1.0f / sqrtf(fmaxf(s, 1e-12f)));
     if (m < M) u[(long long)m * FID_DIM + n] = r > 0.f ? r : 0.f;
 }

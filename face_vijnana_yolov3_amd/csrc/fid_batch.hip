@@ -5,8 +5,8 @@
 // Three launches, the later ones reading what the earlier stored (u is at most 256 KB: it stays in L2, nothing is staged whole):
 //   select  one wave per anchor, four anchors per workgroup.  The anchor lies in LDS (read as broadcasts); lane l computes D(i, r)
 //           of rows r = l, l + 64, ... once (16 float4 loads per row, fid_select.h's chain) and keeps them in registers, since the
-//           negative's class needs dap first.  Every choice is an extremum under a total order -- fid_mine.hip's -- so it does not
-//           depend on the split over lanes.
+//           negative's class needs dap first.  Every choice is an extremum under a total order -- min_less / max_more of
+//           block_ops.h -- so it does not depend on the split over lanes.
 //   grad    one wave per row r (lane = column), four rows per workgroup: the owner GATHERS its row's total in fp64 -- its own
 //           anchor term, then anchors 0 .. M-1 in order, found 64 at a time by a ballot over (pos_index == r, neg_index == r) --
 //           and takes it back through l2_normalize and ReLU (l2_relu_bwd).  No atomics, one writer per element.
@@ -55,9 +55,9 @@ __global__ __launch_bounds__(64 * BT_WAVES) void fid_batch_select_kernel(const f
 #pragma unroll
     for (int j = 0; j < BT_SLOTS; ++j) {
         const int r = 64 * j + lane;
-        if (sub[j] == sa && dist[j] == dist[j] && max_more(dist[j], r, pd, pi)) { pd = dist[j]; pi = r; }
+        if (sub[j] == sa && dist[j] == dist[j] && max_more()(dist[j], r, pd, pi)) { pd = dist[j]; pi = r; }
     }
-    wave_best<true>(pd, pi);
+    fv_wave_best<max_more>(pd, pi);
     const double dap = pd, hi = dap + margin;
 
     // the negative: [0] band (or, mode 0, all candidates), minimum; [1] D <= dap, maximum; [2] D >= hi, minimum
@@ -70,15 +70,15 @@ __global__ __launch_bounds__(64 * BT_WAVES) void fid_batch_select_kernel(const f
             const double d = dist[j];
             if (sub[j] < 0 || sub[j] == sa || d != d) continue;
             if (mode == 0 || (d > dap && d < hi)) {
-                if (min_less(d, r, bd[0], bi[0])) { bd[0] = d; bi[0] = r; }
+                if (min_less()(d, r, bd[0], bi[0])) { bd[0] = d; bi[0] = r; }
             } else if (d <= dap) {
-                if (max_more(d, r, bd[1], bi[1])) { bd[1] = d; bi[1] = r; }
+                if (max_more()(d, r, bd[1], bi[1])) { bd[1] = d; bi[1] = r; }
             } else if (d >= hi) {
-                if (min_less(d, r, bd[2], bi[2])) { bd[2] = d; bi[2] = r; }
+                if (min_less()(d, r, bd[2], bi[2])) { bd[2] = d; bi[2] = r; }
             }
         }
-        wave_best<false>(bd[0], bi[0]);
-        if (mode != 0) { wave_best<true>(bd[1], bi[1]); wave_best<false>(bd[2], bi[2]); }
+        fv_wave_best<min_less>(bd[0], bi[0]);
+        if (mode != 0) { fv_wave_best<max_more>(bd[1], bi[1]); fv_wave_best<min_less>(bd[2], bi[2]); }
     }
     int kd = 3, ni = -1;
     double dn = __builtin_inf();
@@ -114,9 +114,7 @@ __global__ __launch_bounds__(64 * BT_WAVES) void fid_batch_grad_kernel(const flo
     if (r >= M) return;                            // wave-uniform: the wave sums below see all 64 lanes
     int nv = 0;
     for (int i = lane; i < M; i += 64) nv += kind[i] != 3;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o);
-    const double V = (double)nv;
+    const double V = (double)fv_wave_sum(nv);
     const double ur = (double)u[(size_t)r * FID_DIM + lane];
 
     double total = 0.0;
@@ -164,8 +162,7 @@ __global__ __launch_bounds__(128) void fid_batch_finish_kernel(const float* __re
             }
             sh[i] = h;                             // an invalid anchor adds +0: the sum stays what the valid ones give
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o);
+        nv = fv_wave_sum(nv);
     }
     __syncthreads();
     if (threadIdx.x < 64) {

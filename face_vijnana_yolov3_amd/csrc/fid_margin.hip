@@ -113,12 +113,6 @@ struct MarginArgs {
     double s, m, cos_m, sin_m, cos_pm, sin_pm;   // pm: pi - m
 };
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
 __global__ __launch_bounds__(64 * MS_ROW_WAVES) void fid_margin_row_kernel(const int* __restrict__ labels, int M, int C, int ldz,
                                                                            MarginArgs a, double* __restrict__ Z,
                                                                            double* __restrict__ row_loss, int* __restrict__ pred,
@@ -128,8 +122,7 @@ __global__ __launch_bounds__(64 * MS_ROW_WAVES) void fid_margin_row_kernel(const
     if (i >= M) return;                    // wave-uniform, and no barrier below
     int nv = 0;
     for (int r = lane; r < M; r += 64) { const int l = labels[r]; nv += l >= 0 && l < C; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o);
+    nv = fv_wave_sum(nv);
     const int y = labels[i];
     const bool valid = y >= 0 && y < C;
     double* z = Z + (size_t)i * ldz;
@@ -164,12 +157,7 @@ __global__ __launch_bounds__(64 * MS_ROW_WAVES) void fid_margin_row_kernel(const
         if (c != y) mx = fmax(mx, a.s * v.x);
         if (c + 1 < C && c + 1 != y) mx = fmax(mx, a.s * v.y);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
+    fv_wave_best<max_more>(best, bi);
     if (lane == 0) {
         pred[i] = (y >= C) ? -2 : bi;
         cos_t[i] = cy;                     // one quiet NaN where the row has no class
@@ -179,14 +167,14 @@ __global__ __launch_bounds__(64 * MS_ROW_WAVES) void fid_margin_row_kernel(const
         if (lane == 0) row_loss[i] = 0.0;
         return;
     }
-    mx = wave_max(mx);
+    mx = fv_wave_max(mx);
     double sum = 0.0;
     for (int c = 2 * lane; c < C; c += 128) {
         const double2 v = *reinterpret_cast<const double2*>(z + c);
         sum += exp((c == y ? zy : a.s * v.x) - mx);
         if (c + 1 < C) sum += exp((c + 1 == y ? zy : a.s * v.y) - mx);
     }
-    sum = wave_sum(sum);
+    sum = fv_wave_sum_all(sum);
     if (lane == 0) row_loss[i] = mx + log(sum) - zy;
     const double f = a.s / (double)nv, rs = 1.0 / sum;
     for (int c = 2 * lane; c < C; c += 128) {
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(MS_THREADS) void fid_margin_dw_kernel(const double*
     for (int j = 0; j < PER; ++j) {
         const int cl = cg * PER + j;
         const double wh = T.w[cl][k];
-        const double dot = wave_sum(wh * acc[j]);
+        const double dot = fv_wave_sum_all(wh * acc[j]);
         const double d = T.live[cl] ? T.inv[cl] * (acc[j] - wh * dot) : acc[j] * 1e6;
         if (c0 + cl < C) dW[(size_t)(c0 + cl) * FID_DIM + k] = (float)(d * loss_weight);
     }
@@ -291,9 +279,8 @@ __global__ __launch_bounds__(256) void fid_margin_finish_kernel(const float* __r
             const int l = labels[r];
             if (l >= 0 && l < C) { ++nv; s += row_loss[r]; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o);
-        s = wave_sum(s);
+        nv = fv_wave_sum(nv);
+        s = fv_wave_sum_all(s);
         if (lane == 0) *loss = nv ? (float)(s / (double)nv) : 0.f;
     }
 }

@@ -10,7 +10,7 @@
 // (m * 256 B, 2.2 MB at 8 631 rows) re-read from L2 by every workgroup.  Not the bottleneck of identification (one crop's
 // extraction costs more than the whole match of a frame batch), so the kernel stays on the vector units; an MFMA form
 // (|q|^2 + |r|^2 - 2 q.r) would give up the exact tie behaviour.
-#include "common.h"
+#include "block_ops.h"
 #include <climits>
 
 namespace {
@@ -18,16 +18,9 @@ namespace {
 constexpr int FM_DIM = 64;
 constexpr int FM_THREADS = 256;
 
-// the order np.argmin uses: NaN before every number (the first NaN wins), otherwise by distance, then by index
-__device__ __forceinline__ bool lex_less(double d0, int i0, double d1, int i1) {
-    const bool n0 = d0 != d0, n1 = d1 != d1;
-    if (n0 != n1) return n0;
-    if (n0) return i0 < i1;
-    return d0 < d1 || (d0 == d1 && i0 < i1);
-}
-
 // QB queries per workgroup (staged in LDS, read as broadcasts); thread t scans registry rows t, t + 256, ... (16 float4 loads
-// per row), keeping the best (distance, index) per query; then a wave butterfly and the four waves in LDS.
+// per row), keeping the best (distance, index) per query under lex_less (np.argmin's order); then a wave butterfly and the four
+// waves in LDS.
 template <int QB>
 __global__ __launch_bounds__(FM_THREADS) void fid_match_kernel(const float* __restrict__ Q, int n, const float* __restrict__ R, int m,
                                                                int* __restrict__ best_index, double* __restrict__ best_dist) {
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(FM_THREADS) void fid_match_kernel(const float* __re
 #pragma unroll
         for (int q = 0; q < QB; ++q) {
             const double dist = sqrt(s[q]);
-            if (lex_less(dist, r, bd[q], bi[q])) { bd[q] = dist; bi[q] = r; }
+            if (lex_less()(dist, r, bd[q], bi[q])) { bd[q] = dist; bi[q] = r; }
         }
     }
     const int lane = tid & 63, wave = tid >> 6;
@@ -76,21 +69,14 @@ __global__ __launch_bounds__(FM_THREADS) void fid_match_kernel(const float* __re
     for (int q = 0; q < QB; ++q) {
         double d = bd[q];
         int i = bi[q];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double od = __shfl_xor(d, o, 64);
-            const int oi = __shfl_xor(i, o, 64);
-            if (lex_less(od, oi, d, i)) { d = od; i = oi; }
-        }
+        fv_wave_best<lex_less>(d, i);
         if (lane == 0) { wd[wave][q] = d; wi[wave][q] = i; }
     }
     __syncthreads();
     if (tid < QB && q0 + tid < n) {
-        double d = wd[0][tid];
-        int i = wi[0][tid];
-#pragma unroll
-        for (int w = 1; w < FM_THREADS / 64; ++w)
-            if (lex_less(wd[w][tid], wi[w][tid], d, i)) { d = wd[w][tid]; i = wi[w][tid]; }
+        double d;
+        int i;
+        fv_block_best<lex_less, FM_THREADS / 64>(&wd[0][tid], &wi[0][tid], QB, d, i);
         best_index[q0 + tid] = i;
         best_dist[q0 + tid] = d;
     }

@@ -10,8 +10,8 @@
 // One workgroup serves one anchor and up to PB of its positives (a longer group is cut by the launcher): the anchor is staged in
 // LDS and read as broadcasts, thread t scans rows t, t + 256, ... (16 float4 loads per row), so each D(a, r) is computed once and
 // then tested against the PB (dap, hi) pairs, which lie in LDS too.  Per positive a thread keeps three running (double, int) bests,
-// one per class; then a wave butterfly and the four waves in LDS, as in fid_match_kernel.  Work: chunks * n * 64 * 3 fp64 vector
-// ops for the distances plus about 12 compares per (row, positive).
+// one per class; then fv_wave_best and, over the four waves in LDS, fv_block_best (block_ops.h).  Work: chunks * n * 64 * 3 fp64
+// vector ops for the distances plus about 12 compares per (row, positive).
 #include "fid_select.h"
 #include <climits>
 #include <cmath>
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(MN_THREADS) void fid_mine_kernel(const float* __res
         const double dist = dist_to(as, reinterpret_cast<const float4*>(ids + (size_t)r * MN_DIM));
         if (dist != dist) continue;                    // a NaN distance belongs to no class
         if (MODE == 1) {
-            if (min_less(dist, r, bd[0], bi[0])) { bd[0] = dist; bi[0] = r; }
+            if (min_less()(dist, r, bd[0], bi[0])) { bd[0] = dist; bi[0] = r; }
             continue;
         }
 #pragma unroll
@@ -72,11 +72,11 @@ __global__ __launch_bounds__(MN_THREADS) void fid_mine_kernel(const float* __res
             if (j >= c.count) continue;                // uniform
             const double dap = sdap[j], hi = shi[j];
             if (dist > dap && dist < hi) {
-                if (min_less(dist, r, bd[3 * j], bi[3 * j])) { bd[3 * j] = dist; bi[3 * j] = r; }
+                if (min_less()(dist, r, bd[3 * j], bi[3 * j])) { bd[3 * j] = dist; bi[3 * j] = r; }
             } else if (dist <= dap) {
-                if (max_more(dist, r, bd[3 * j + 1], bi[3 * j + 1])) { bd[3 * j + 1] = dist; bi[3 * j + 1] = r; }
+                if (max_more()(dist, r, bd[3 * j + 1], bi[3 * j + 1])) { bd[3 * j + 1] = dist; bi[3 * j + 1] = r; }
             } else if (dist >= hi) {
-                if (min_less(dist, r, bd[3 * j + 2], bi[3 * j + 2])) { bd[3 * j + 2] = dist; bi[3 * j + 2] = r; }
+                if (min_less()(dist, r, bd[3 * j + 2], bi[3 * j + 2])) { bd[3 * j + 2] = dist; bi[3 * j + 2] = r; }
             }
         }
     }
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(MN_THREADS) void fid_mine_kernel(const float* __res
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         if (MODE == 0 && b / 3 >= c.count) continue;   // uniform
-        if (MODE == 0 && b % 3 == 1) wave_best<true>(bd[b], bi[b]); else wave_best<false>(bd[b], bi[b]);
+        if (MODE == 0 && b % 3 == 1) fv_wave_best<max_more>(bd[b], bi[b]); else fv_wave_best<min_less>(bd[b], bi[b]);
         if (lane == 0) { wd[wave][b] = bd[b]; wi[wave][b] = bi[b]; }
     }
     __syncthreads();
@@ -96,21 +96,13 @@ __global__ __launch_bounds__(MN_THREADS) void fid_mine_kernel(const float* __res
         if (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                double d = wd[0][3 * tid + k];
-                int i = wi[0][3 * tid + k];
-                for (int w = 1; w < MN_WAVES; ++w) {
-                    const double od = wd[w][3 * tid + k];
-                    const int oi = wi[w][3 * tid + k];
-                    if (k == 1 ? max_more(od, oi, d, i) : min_less(od, oi, d, i)) { d = od; i = oi; }
-                }
-                best_d[k] = d; best_i[k] = i;
+                const double* sd = &wd[0][3 * tid + k];
+                const int* si = &wi[0][3 * tid + k];
+                if (k == 1) fv_block_best<max_more, MN_WAVES>(sd, si, NB, best_d[k], best_i[k]);
+                else fv_block_best<min_less, MN_WAVES>(sd, si, NB, best_d[k], best_i[k]);
             }
         } else {
-            double d = wd[0][0];
-            int i = wi[0][0];
-            for (int w = 1; w < MN_WAVES; ++w)
-                if (min_less(wd[w][0], wi[w][0], d, i)) { d = wd[w][0]; i = wi[w][0]; }
-            best_d[0] = d; best_i[0] = i;
+            fv_block_best<min_less, MN_WAVES>(&wd[0][0], &wi[0][0], NB, best_d[0], best_i[0]);
         }
         int kd = 3, ni = -1;
         double dn = __builtin_inf();

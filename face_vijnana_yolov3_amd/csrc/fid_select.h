@@ -1,13 +1,8 @@
 // Selection primitives shared by fid_mine.hip and fid_batch.hip: the exact distance D(i, r) between two rows of facial IDs and the
-// two total orders every choice is an extremum of.  D is sqrt of the fp64 sum, in dimension order 0..63, of the squared fp64
-// differences (no FMA contraction: -ffp-contract=off) -- fid_match.hip's numerics.
+// class of a negative.  Every choice is an extremum under min_less / max_more of block_ops.h.  D is sqrt of the fp64 sum, in
+// dimension order 0..63, of the squared fp64 differences (no FMA contraction: -ffp-contract=off) -- fid_match.hip's numerics.
 #pragma once
-#include "common.h"
-
-// minimum of (distance, index); an empty best is (+inf, INT_MAX), which every row beats
-__device__ __forceinline__ bool min_less(double d0, int i0, double d1, int i1) { return d0 < d1 || (d0 == d1 && i0 < i1); }
-// maximum distance, the lowest index among equals; an empty best is (-inf, INT_MAX)
-__device__ __forceinline__ bool max_more(double d0, int i0, double d1, int i1) { return d0 > d1 || (d0 == d1 && i0 < i1); }
+#include "block_ops.h"
 
 // a: the anchor in LDS (the same address in every lane: a broadcast), rp: one row of ids
 __device__ __forceinline__ double dist_to(const float* a, const float4* rp) {
@@ -23,16 +18,6 @@ __device__ __forceinline__ double dist_to(const float* a, const float4* rp) {
         d = (double)x.w - (double)v.w; s += d * d;
     }
     return sqrt(s);
-}
-
-template <bool MAX>
-__device__ __forceinline__ void wave_best(double& d, int& i) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double od = __shfl_xor(d, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (MAX ? max_more(od, oi, d, i) : min_less(od, oi, d, i)) { d = od; i = oi; }
-    }
 }
 
 // class of a negative at distance dist for a positive at dap, hi = dap + margin (none of them NaN): exactly one holds

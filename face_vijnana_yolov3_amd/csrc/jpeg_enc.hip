@@ -17,7 +17,7 @@
 //               call 2, every byte moved to its final place with a 00 behind every FF, each thread owning the bytes it writes
 // The caller reads the n byte counts between the calls and sizes the output exactly.  The packed-word buffer is sized for the
 // worst block the tables admit (1658 bits), so no capacity is ever a guess.  Nothing is allocated, nothing synchronises.
-#include "common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -493,8 +493,7 @@ __global__ __launch_bounds__(256) void jpeg_enc_ffbase_kernel(const unsigned* __
     const unsigned long long w0 = word0[i], t = w0 / ENC_TILE;
     unsigned c = 0;
     for (unsigned long long w = t * ENC_TILE + lane; w < w0; w += 64) c += ff_count(words[w]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
+    c = fv_wave_sum(c);
     if (lane == 0) ffbase[i] = fsum[t] + c;
 }
 

@@ -10,7 +10,7 @@
 //   3. suppression matrix as bitmasks: wave w owns rows w, w+4, ...; one __ballot per 64 columns
 //   4. wave 0 walks the rows in order keeping the alive mask in registers (no barriers)
 //   5. second bitonic sort of the survivors (ascending score) and output of the first num_cands
-#include "common.h"
+#include "block_ops.h"
 #include "bbox_iou.h"
 
 namespace {
@@ -21,40 +21,12 @@ __device__ __forceinline__ float sigmoid_ref(float x) {
     return 1.0f / (1.0f + e);
 }
 
-__device__ __forceinline__ int interval_overlap(int x1, int x2, int x3, int x4) {
-    if (x3 < x1) {
-        if (x4 < x1) return 0;
-        return min(x2, x4) - x1;
-    } else {
-        if (x2 < x3) return 0;
-        return min(x2, x4) - x3;
-    }
-}
-
 // iou(a,b) >= th with the reference's semantics (0/0 = nan compares false).
 __device__ __forceinline__ bool iou_ge(const int4& a, const int4& b, double th) {
-    long long iw = interval_overlap(a.x, a.z, b.x, b.z);
-    long long ih = interval_overlap(a.y, a.w, b.y, b.w);
-    long long inter = iw * ih;
-    long long uni = (long long)(a.z - a.x) * (a.w - a.y) + (long long)(b.z - b.x) * (b.w - b.y) - inter;
+    long long inter, uni;
+    fv_box_inter_union(a, b, inter, uni);
     if (inter == 0) return uni != 0 && 0.0 >= th;  // == (0.0 / uni >= th), without the divide
     return (double)inter / (double)uni >= th;
-}
-
-template <int P, bool DESC>
-__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int tid) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += 256) {
-                int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                int l = i + j;
-                unsigned long long a = keys[i], b = keys[l];
-                bool up = ((i & k) == 0) != DESC;  // ascending run?
-                if (up ? (a > b) : (a < b)) { keys[i] = b; keys[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 template <int P>
@@ -97,7 +69,7 @@ __global__ __launch_bounds__(256) void decode_nms_kernel(const float* __restrict
                 int hw = (int)(pw / 2), hh = (int)(ph / 2);
                 sbox[c] = make_int4(max(px - hw, 0), max(py - hh, 0), min(px + hw, S - 1), min(py + hh, S - 1));
                 sobj[c] = o;
-                key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)c);
+                key = fv_rank_key(s, (unsigned)c);
             }
         }
         keys[c] = key;
@@ -105,7 +77,7 @@ __global__ __launch_bounds__(256) void decode_nms_kernel(const float* __restrict
     __syncthreads();
 
     // ---- 2. descending sort (invalid keys = 0 sink to the end)
-    bitonic_sort<P, true>(keys, tid);
+    fv_bitonic_sort<256, true>(keys, P, tid);
     for (int p = tid; p < P; p += 256)
         if (keys[p] != 0 && (p == P - 1 || keys[p + 1] == 0)) s_n = p + 1;
     __syncthreads();
@@ -114,11 +86,11 @@ __global__ __launch_bounds__(256) void decode_nms_kernel(const float* __restrict
 
     // ---- 3. suppression bitmasks: bit j of row i  <=>  j > i and IoU(i,j) >= th
     for (int i = wave; i < n; i += 4) {
-        const int4 bi = sbox[0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFull)];
+        const int4 bi = sbox[fv_rank_index(keys[i])];
         for (int c = i >> 6; c < nwn; ++c) {
             int j = (c << 6) + lane;
             bool pred = false;
-            if (j > i && j < n) pred = iou_ge(bi, sbox[0xFFFFFFFFu - (unsigned)(keys[j] & 0xFFFFFFFFull)], iou_th);
+            if (j > i && j < n) pred = iou_ge(bi, sbox[fv_rank_index(keys[j])], iou_th);
             unsigned long long word = __ballot(pred);
             if (lane == 0) mask[i * NW + c] = word;
         }
@@ -151,14 +123,13 @@ __global__ __launch_bounds__(256) void decode_nms_kernel(const float* __restrict
         int p = tid + r * 256;
         unsigned long long k = keys[p];
         bool keep = p < n && ((alive[p >> 6] >> (p & 63)) & 1ull);
-        unsigned cellidx = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
-        nk[r] = keep ? ((k & 0xFFFFFFFF00000000ull) | cellidx) : ~0ull;
+        nk[r] = keep ? ((k & 0xFFFFFFFF00000000ull) | fv_rank_index(k)) : ~0ull;
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < P / 256; ++r) keys[tid + r * 256] = nk[r];
     __syncthreads();
-    bitonic_sort<P, false>(keys, tid);
+    fv_bitonic_sort<256, false>(keys, P, tid);
 
     int m = 0;
 #pragma unroll
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(256) void decode_nms_kernel(const float* __restrict
         if (k < cnt) {
             unsigned long long key = keys[k];
             unsigned c = (unsigned)(key & 0xFFFFFFFFull);
-            float s = __uint_as_float((unsigned)(key >> 32));
+            float s = fv_rank_score(key);
             int4 b = sbox[c];
             reinterpret_cast<int4*>(boxes)[o] = b;
             cell_out[o] = (int)c;

@@ -11,7 +11,7 @@
 //    workgroup testing IoU against the current survivor
 // float32 arithmetic in the reference's operation order (NumPy 2 scalar rules); exp is the
 // correctly rounded float32 exponential (NumPy's SIMD exp may differ by 1 ulp).
-#include "common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -58,12 +58,7 @@ __global__ __launch_bounds__(1024) void yolo_decode_kernel(const YoloDecodeArgs 
                 conf = sigf(t[4]);
                 keep = !(conf < a.obj_thresh);
             }
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) wave_cnt[wave] = __popcll(m);
-            __syncthreads();
-            int pre = base;
-            for (int w = 0; w < wave; ++w) pre += wave_cnt[w];
-            const int pos = pre + __popcll(m & ((1ull << lane) - 1ull));
+            const int pos = base + fv_block_compact(keep, wave_cnt, lane, wave);
             if (keep && pos < a.capacity) {
                 const int row = cell / g, col = cell - row * g;
                 float x = ((float)col + sigf(t[0])) / (float)g;
@@ -88,12 +83,6 @@ __global__ __launch_bounds__(1024) void yolo_decode_kernel(const YoloDecodeArgs 
     if (tid == 0) a.count[img] = base < a.capacity ? base : a.capacity;
 }
 
-__device__ __forceinline__ int ovl(int x1, int x2, int x3, int x4) {
-    if (x3 < x1) { if (x4 < x1) return 0; return min(x2, x4) - x1; }
-    if (x2 < x3) return 0;
-    return min(x2, x4) - x3;
-}
-
 template <int P>
 __global__ __launch_bounds__(1024) void yolo_nms_kernel(const int* __restrict__ boxes_all, float* __restrict__ classes_all,
                                                         const int* __restrict__ count_all, int nclass, double nms_thresh, int capacity) {
@@ -109,33 +98,24 @@ __global__ __launch_bounds__(1024) void yolo_nms_kernel(const int* __restrict__ 
         float p = i < n ? classes[(size_t)i * nclass + c] : 0.f;
         pv[i] = p;
         // descending prob, ties -> lower index; non-positive probs (incl. padding) sink to the end
-        keys[i] = (i < n && p > 0.f) ? (((unsigned long long)__float_as_uint(p) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
+        keys[i] = (i < n && p > 0.f) ? fv_rank_key(p, (unsigned)i) : 0ull;
     }
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += 1024) {
-                int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
-                unsigned long long x = keys[i], y = keys[l];
-                bool desc = (i & k) == 0;
-                if (desc ? (x < y) : (x > y)) { keys[i] = y; keys[l] = x; }
-            }
-            __syncthreads();
-        }
+    fv_bitonic_sort<1024, true>(keys, P, tid);
     // greedy sweep over the positive-prob prefix
     for (int a = 0; a < n; ++a) {
         const unsigned long long ka = keys[a];
         if (ka == 0ull) break;                                   // uniform: rest has prob <= 0
-        const int ia = (int)(0xFFFFFFFFu - (unsigned)(ka & 0xFFFFFFFFull));
+        const int ia = (int)fv_rank_index(ka);
         if (pv[ia] != 0.f) {                                     // uniform (LDS value, read after a barrier)
             const int4 A = reinterpret_cast<const int4*>(boxes)[ia];
             for (int b = a + 1 + tid; b < n; b += 1024) {
                 const unsigned long long kb = keys[b];
                 if (kb == 0ull) break;
-                const int ib = (int)(0xFFFFFFFFu - (unsigned)(kb & 0xFFFFFFFFull));
+                const int ib = (int)fv_rank_index(kb);
                 const int4 Bx = reinterpret_cast<const int4*>(boxes)[ib];
-                long long inter = (long long)ovl(A.x, A.z, Bx.x, Bx.z) * ovl(A.y, A.w, Bx.y, Bx.w);
-                long long uni = (long long)(A.z - A.x) * (A.w - A.y) + (long long)(Bx.z - Bx.x) * (Bx.w - Bx.y) - inter;
+                long long inter, uni;
+                fv_box_inter_union(A, Bx, inter, uni);
                 // python ints: union == 0 raises ZeroDivisionError in the reference; here: no suppression
                 if (uni != 0 && (double)inter / (double)uni >= nms_thresh) pv[ib] = 0.f;
             }

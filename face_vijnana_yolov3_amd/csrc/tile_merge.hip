@@ -6,7 +6,7 @@
 //   1. collect: every (view, slot) of the frame with slot < count and score > 0 takes a place in the LDS key array through an
 //      integer LDS counter (the order of arrival does not matter: the key carries the candidate's index)
 //   2. LDS bitonic sort of 64-bit keys (score bits | ~index) over the next power of two -> descending score, ties: lower view,
-//      then lower slot (the scheme of postproc.hip)
+//      then lower slot (fv_rank_key, fv_bitonic_sort of block_ops.h)
 //   3. project: the candidate at rank p becomes an fp64 box in the frame's slice of the workspace, in rank order (4096 x 32 B does
 //      not fit LDS next to the keys; the sweep then reads the slice coalesced)
 //   4. greedy walk, at most FV_DET_ROWS rounds: every wave finds the next alive rank from the 64 alive words (one ballot), then
@@ -14,7 +14,7 @@
 //   5. the kept ranks become corners / rows / src
 // No float atomics: no float is ever summed.  Every coordinate operation is one IEEE double operation (-ffp-contract=off).
 #include <climits>
-#include "common.h"
+#include "block_ops.h"
 #include "bbox_iou.h"
 #include "tile_merge.h"
 
@@ -32,21 +32,6 @@ __device__ __forceinline__ bool overlap_ge(const double* a, double bx0, double b
     const double inter = iw * ih;
     const double aa = (a[2] - a[0]) * (a[3] - a[1]), ab = (bx1 - bx0) * (by1 - by0);
     return inter / fmin(aa, ab) >= th;
-}
-
-__device__ __forceinline__ void bitonic_desc(unsigned long long* keys, int P, int tid) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += 256) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i + j;
-                const unsigned long long a = keys[i], b = keys[l];
-                const bool up = (i & k) != 0;  // ascending run?
-                if (up ? (a > b) : (a < b)) { keys[i] = b; keys[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void tile_merge_kernel(const int* __restrict__ boxes, const float* __restrict__ score,
@@ -80,7 +65,7 @@ __global__ __launch_bounds__(256) void tile_merge_kernel(const int* __restrict__
             const float s = score[(size_t)t * K + k];
             if (!(s > 0.0f)) continue;                              // nan is never > 0
             const int pos = atomicAdd(&s_n, 1);
-            if (pos < MAXC) keys[pos] = ((unsigned long long)__float_as_uint(s) << 32) | (0xFFFFFFFFu - (unsigned)q);
+            if (pos < MAXC) keys[pos] = fv_rank_key(s, (unsigned)q);
         }
     }
     __syncthreads();
@@ -99,11 +84,11 @@ __global__ __launch_bounds__(256) void tile_merge_kernel(const int* __restrict__
     // ---- 2. rank
     int P = 64;
     while (P < n) P <<= 1;
-    bitonic_desc(keys, P, tid);
+    fv_bitonic_sort<256, true>(keys, P, tid);
 
     // ---- 3. project, in rank order
     for (int p = tid; p < n; p += 256) {
-        const unsigned q = 0xFFFFFFFFu - (unsigned)(keys[p] & 0xFFFFFFFFull);
+        const unsigned q = fv_rank_index(keys[p]);
         const int t = v0 + (int)(q / (unsigned)K);
         const int* b = boxes + ((size_t)v0 * K + q) * 4;
         const int* g = tiles + (size_t)t * 5;                       // frame, y0, x0, th, tw
@@ -172,8 +157,8 @@ __global__ __launch_bounds__(256) void tile_merge_kernel(const int* __restrict__
         if (r < nk) {
             const int i = s_kept[r];
             const unsigned long long key = keys[i];
-            const unsigned q = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-            const float s = __uint_as_float((unsigned)(key >> 32));
+            const unsigned q = fv_rank_index(key);
+            const float s = fv_rank_score(key);
             const double x0 = wb[i * 4], y0 = wb[i * 4 + 1], x1 = wb[i * 4 + 2], y1 = wb[i * 4 + 3];
             corners[o * 4 + 0] = x0; corners[o * 4 + 1] = y0; corners[o * 4 + 2] = x1; corners[o * 4 + 3] = y1;
             rows[o * 5 + 0] = x0; rows[o * 5 + 1] = y0; rows[o * 5 + 2] = x1 - x0; rows[o * 5 + 3] = y1 - y0;

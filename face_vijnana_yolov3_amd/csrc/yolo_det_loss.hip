@@ -12,6 +12,7 @@
 //   det_finish_kernel   sums the per-workgroup partials in a fixed order -> loss and stats.
 // fp64 arithmetic throughout; every sum is formed in an order fixed by the launch shape.
 #include "yolo_det_loss.h"
+#include "block_ops.h"
 
 #include <cmath>
 
@@ -54,12 +55,7 @@ __global__ __launch_bounds__(256) void det_gather_kernel(DetArgs a, int S, int E
         for (int base = 0; base < nslot; base += 256) {
             const int i = base + tid;
             const bool flag = i < nslot && tb[(long long)i * E + 4] == 1.0f;
-            const unsigned long long mask = __ballot(flag);
-            if (lane == 0) s_cnt[wave] = __popcll(mask);
-            __syncthreads();
-            int off = running;
-            for (int w = 0; w < wave; ++w) off += s_cnt[w];
-            off += __popcll(mask & ((1ull << lane) - 1ull));
+            const int off = running + fv_block_compact(flag, s_cnt, lane, wave);
             running += (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
             if (flag && off < max_boxes) {
                 const float* tp = tb + (long long)i * E;
@@ -188,9 +184,7 @@ __global__ __launch_bounds__(256) void det_loss_kernel(DetArgs a, int S, int ncl
     q[3] = cls;
 #pragma unroll
     for (int k = 0; k < DET_NQ; ++k) {
-        double v = q[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        const double v = fv_wave_sum(q[k]);
         if (lane == 0) s_red[wave][k] = v;
     }
     __syncthreads();
