@@ -95,6 +95,7 @@ def _declare(L):
         'fv_det_ap_sweep': (i32, [vp, vp, vp, vp, vp, i32, ctypes.POINTER(f64), i32, i64, vp, sz, vp, vp, vp, vp]),
         'fv_tile_merge_workspace_bytes': (sz, [i32]),                     # csrc/tile_merge.h
         'fv_tile_merge': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, sz, vp, vp, vp, vp]),
+        'fv_yolo_select_cands': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),    # csrc/yolo_select.h
         'fv_num_layers': (i32, []),
         'fv_layer': (i32, [i32, ctypes.POINTER(LayerDesc)]),
         'fv_param_count': (i64, []),

@@ -135,16 +135,3 @@ class Validator(object):
         res = summarise(self.iou_ths, host[:3 * T].reshape(3, T), int(host[3 * T]))
         res.update(n_images=len(self.files), n_gt=self.n_gt)
         return res
-
-
-def rows_from_boxes(boxes_per_image):
-    """Host form of fv_det_rows_from_nms for boxes already in image coordinates (the three-scale head's host tail): one list of
-    BoundBox per image -> (rows (n, 60, 5) float64, nrows (n,) int32), the values _write_rows would write."""
-    n = len(boxes_per_image)
-    rows = np.zeros((n, ROWS, 5), np.float64)
-    nrows = np.zeros(n, np.int32)
-    for i, boxes in enumerate(boxes_per_image):
-        nrows[i] = min(len(boxes), ROWS)
-        for r, b in enumerate(boxes[:ROWS]):
-            rows[i, r] = (b.xmin, b.ymin, b.xmax - b.xmin, b.ymax - b.ymin, b.get_score())
-    return rows, nrows

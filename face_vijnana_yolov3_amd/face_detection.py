@@ -286,11 +286,13 @@ class FaceDetector(object):
             # the reference's decode_netout -> correct_yolo_boxes -> do_nms chain (yolov3_detect.py:335-444; its driver loops over the
             # images, yd.py:596-604) on the letterboxed images: ONE launch pair for the batch (fv_yolo_decode_nms_batch), results
             # into pinned memory behind an event, like the single-scale head
-            from .yolov3 import decode_nms_batch
+            from .yolov3 import decode_nms_batch, select_cands
             S = self.image_size
             ys = self.model.predict_device(x)
             res = decode_nms_batch(self.model.ctx, ys[0], ys[1], ys[2], (S, S), (S, S), obj_thresh=self.hps['face_conf_th'],
                                    nms_thresh=self.hps['nms_iou_th'])
+            # detect()'s tail (fd.py:942-947) on the device: only the <= num_cands selected rows per image are copied out
+            res = select_cands(self.model.ctx, res, self.hps['num_cands'], int(ys[0].shape[1]))
             host = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True).copy_(v, non_blocking=True) for k, v in res.items()}
             ev = torch.cuda.Event()
             ev.record()
@@ -310,23 +312,18 @@ class FaceDetector(object):
         if tag == 'tiles':
             return [self._tile_boxes(host, b) for b in range(n)]
         if tag == 'three_scale':
-            return [self._three_scale_boxes(host, b) for b in range(n)]
+            return [self._selected_boxes(host, b) for b in range(n)]
         return [to_boundboxes(host, b) for b in range(n)]
 
-    def _three_scale_boxes(self, host, b):
-        """Image b of a decoded batch -> detect()'s own tail (fd.py:942-947): boxes in network pixels, score > 0, ascending score, at
-        most num_cands.  The selection runs on the arrays (BoundBox.get_score: the probability of the arg-max class, capped at 1);
-        only the <= num_cands survivors become BoundBox objects -- a frame can hold thousands of candidates."""
-        from .yolov3 import check_candidate_count
+    def _selected_boxes(self, host, b):
+        """Image b of a selected batch (yolov3.select_cands: detect()'s own tail, fd.py:942-947, already applied on the device: score
+        > 0, ascending score, at most num_cands) -> list[BoundBox] in network pixels.  A count of -1 is an image whose candidate
+        list may have been cut short: an error, never a shortened result."""
+        from .yolov3 import check_selected_count
         n = int(host['count'][b])
-        check_candidate_count(n, int(host['boxes'].shape[1]), self.image_size // 32)     # never a silently shortened list
-        bx = host['boxes'][b, :n].numpy().astype(np.int64); ob = host['objness'][b, :n].numpy(); cl = host['classes'][b, :n].numpy()
-        if n == 0:
-            return []
-        score = np.minimum(cl[np.arange(n), np.argmax(cl, axis=1)], np.float32(1.0))
-        keep = np.nonzero(score > 0)[0]
-        keep = keep[np.argsort(score[keep], kind='stable')][:self.hps['num_cands']]
-        return [BoundBox(bx[k, 0], bx[k, 1], bx[k, 2], bx[k, 3], objness=ob[k], classes=list(cl[k])) for k in keep]
+        check_selected_count(n, self.image_size // 32)
+        bx = host['boxes'][b, :n].numpy().astype(np.int64); ob = host['obj'][b, :n].numpy(); cl = host['classes'][b, :n].numpy()
+        return [BoundBox(bx[k, 0], bx[k, 1], bx[k, 2], bx[k, 3], objness=ob[k], classes=list(cl[k])) for k in range(n)]
 
     # ------------------------------------------------------------------ tiled inference (hps['tiles'], DESIGN.md section 30)
     def _eval_batch(self):
@@ -654,10 +651,10 @@ class FaceDetector(object):
     def validate(self, epoch=None):
         """cal_mAP_sweep of what evaluate() would write for the held-out set of hps['validate'] (absent: the defaults over
         conf['test_path']), without a csv, an annotated image or a host metric: the batched input path of test(), then per batch
-        fv_decode_nms -> fv_det_rows_from_nms -> fv_det_match_rows with nothing copied to the host (three-scale head: the rows come
-        from the host tail of detect and are uploaded), one fv_det_ap_sweep over the set and one small D2H copy.  Inference on the
-        moving statistics in the inference workspace: no parameter, BN statistic, optimiser state or random generator of train() is
-        touched.  -> dict: epoch, iou_ths, ap (per threshold), mean_ap, precision, recall (final, per threshold), n_det, n_images,
+        fv_decode_nms -> fv_det_rows_from_nms -> fv_det_match_rows with nothing copied to the host (three-scale head:
+        fv_yolo_decode_nms_batch -> fv_yolo_select_cands in fv_decode_nms' place), one fv_det_ap_sweep over the set and one small
+        D2H copy.  Inference on the moving statistics in the inference workspace: no parameter, BN statistic, optimiser state or
+        random generator of train() is touched.  -> dict: epoch, iou_ths, ap (per threshold), mean_ap, precision, recall (final, per threshold), n_det, n_images,
         n_gt."""
         import torch
         from . import det_metric
@@ -669,6 +666,9 @@ class FaceDetector(object):
         state = {'i0': 0}
 
         tiled = getattr(self, 'tiles', None) is not None
+        if self.three_scale:       # select_cands' counts of the whole set (-1: a refused image), read once at the end
+            from .yolov3 import check_selected_count, decode_nms_batch, select_cands, select_cands_buffers
+            selected = torch.zeros((len(v.files),), dtype=torch.int32, device=dev)
 
         def launch(x, geoms, imgs=None):
             i0, n = state['i0'], int(x.shape[0])
@@ -677,31 +677,30 @@ class FaceDetector(object):
                 self._tiles_run(x, imgs, rows=v.rows[i0:i0 + n], nrows=v.nrows[i0:i0 + n])
                 v.match(ctx, i0, n)
                 return i0, None
-            if self.three_scale:
-                return i0, self._detect_launch(x)
-            res = decode_nms(ctx, self.model.predict_device(x), self.image_size, self.hps['face_conf_th'], self.hps['nms_iou_th'],
-                             self.hps['num_cands'])
             geom = torch.tensor(geoms, dtype=torch.int32).reshape(n, 6).to(dev, non_blocking=True)
+            if self.three_scale:   # fv_yolo_select_cands puts the candidate lists into fv_decode_nms' layout: the same chain from there
+                S = self.image_size
+                ys = self.model.predict_device(x)
+                cands = decode_nms_batch(ctx, ys[0], ys[1], ys[2], (S, S), (S, S), obj_thresh=self.hps['face_conf_th'],
+                                         nms_thresh=self.hps['nms_iou_th'])
+                out = select_cands_buffers(n, self.hps['num_cands'], cands['classes'].shape[2], dev)
+                out['count'] = selected[i0:i0 + n]
+                res = select_cands(ctx, cands, self.hps['num_cands'], int(ys[0].shape[1]), out=out)
+            else:
+                res = decode_nms(ctx, self.model.predict_device(x), self.image_size, self.hps['face_conf_th'], self.hps['nms_iou_th'],
+                                 self.hps['num_cands'])
             det_metric.rows_from_nms(ctx, res, geom, self.image_size, v.rows[i0:i0 + n], v.nrows[i0:i0 + n])
             v.match(ctx, i0, n)
             return i0, None
 
-        for _chunk, _raws, geoms, (i0, launched), _imgs in self._launched_batches(v.files, launch, need_raw=False, _with_images=tiled,
-                                                                                   _launch_images=tiled):
-            if launched is None:
-                continue
-            boxes = self._detect_collect(launched)
-            for b, geom in zip(boxes, geoms):
-                self._project_back(b, geom)
-            rows, nrows = det_metric.rows_from_boxes(boxes)
-            n = len(boxes)
-            v.rows[i0:i0 + n].copy_(torch.from_numpy(rows))
-            v.nrows[i0:i0 + n].copy_(torch.from_numpy(nrows))
-            v.match(ctx, i0, n)
+        for _batch in self._launched_batches(v.files, launch, need_raw=False, _with_images=tiled, _launch_images=tiled):
+            pass                   # everything was queued by launch(); nothing is copied back and no event is waited for
         res = v.finish(ctx)
         if tiled and bool((v.nrows < 0).any()):          # the one read of nrows, after the set's only D2H copy
             raise ValueError('fd_conf.hps.tiles: a frame of %s holds more candidates than the merge takes (%d); raise tiles.size or '
                              'lower num_cands' % (v.conf['path'], data.TILE_MAX_CANDS))
+        if self.three_scale and bool((selected < 0).any()):     # after the set's only D2H copy; no metric of a cut list is returned
+            check_selected_count(-1, self.image_size // 32)
         res['epoch'] = epoch
         return res
 

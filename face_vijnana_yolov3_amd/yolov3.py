@@ -219,3 +219,53 @@ def decode_nms_batch(ctx, y13, y26, y52, image_hw, net_hw=(416, 416), anchors=CO
                                         int(image_hw[1]), cap, ptr(boxes), ptr(obj), ptr(cls), ptr(cnt))
     ctx.check(rc, 'fv_yolo_decode_nms_batch')
     return dict(boxes=boxes, objness=obj, classes=cls, count=cnt)
+
+
+INT_MAX = 2 ** 31 - 1
+
+
+def select_refuse_at(capacity, g):
+    """The count from which fv_yolo_select_cands refuses an image: capacity where the list may have been cut short (what
+    check_candidate_count decides on the host), never (INT_MAX) where the capacity holds every slot of grid g."""
+    return int(capacity) if int(capacity) < candidate_slots(g) else INT_MAX
+
+
+def select_cands_buffers(n, num_cands, nclass, device):
+    """The six result tensors of select_cands for n images, uninitialised."""
+    from .postproc import decode_nms_buffers
+    out = decode_nms_buffers(n, num_cands, device)
+    out['classes'] = torch.empty((n, int(num_cands), int(nclass)), dtype=torch.float32, device=device)
+    return out
+
+
+def select_cands(ctx, res, num_cands, grid, out=None):
+    """fv_yolo_select_cands: decode_nms_batch's dict -> the tail of detect() (score > 0, ascending stable argsort, the first
+    num_cands) per image, as a dict of CUDA tensors under fv_decode_nms' key names: boxes (B,K,4) int32, cell (B,K) int32 (the row's
+    index in the candidate list), obj (B,K), score (B,K) (the arg-max class probability capped at 1), count (B,) int32, and classes
+    (B,K,nclass).  det_metric.rows_from_nms and the pinned-copy code of the single-scale path take it as is.  grid: the coarsest
+    grid (image_size // 32); an image whose list may have been cut short (check_candidate_count) gets count -1, which
+    check_selected_count turns into the error where the count is read on the host.  out: such a dict to write into (views along
+    the first axis of a longer buffer are fine).  No host sync."""
+    boxes, obj, cls, cnt = res['boxes'], res['objness'], res['classes'], res['count']
+    B, cap, nclass = int(boxes.shape[0]), int(boxes.shape[1]), int(cls.shape[2])
+    K = int(num_cands)
+    assert boxes.dtype == torch.int32 and obj.dtype == torch.float32 and cls.dtype == torch.float32 and cnt.dtype == torch.int32
+    assert tuple(boxes.shape) == (B, cap, 4) and tuple(obj.shape) == (B, cap) and tuple(cls.shape) == (B, cap, nclass)
+    assert tuple(cnt.shape) == (B,)
+    if out is None:
+        out = select_cands_buffers(B, K, nclass, boxes.device)
+    assert tuple(out['boxes'].shape) == (B, K, 4) and tuple(out['cell'].shape) == (B, K) and tuple(out['obj'].shape) == (B, K)
+    assert tuple(out['score'].shape) == (B, K) and tuple(out['classes'].shape) == (B, K, nclass) and tuple(out['count'].shape) == (B,)
+    rc = lib().fv_yolo_select_cands(ctx.handle, ptr(boxes), ptr(obj), ptr(cls), ptr(cnt), B, cap, nclass, select_refuse_at(cap, grid), K,
+                                    ptr(out['boxes']), ptr(out['cell']), ptr(out['obj']), ptr(out['score']), ptr(out['classes']),
+                                    ptr(out['count']))
+    ctx.check(rc, 'fv_yolo_select_cands')
+    return dict(boxes=out['boxes'], cell=out['cell'], obj=out['obj'], score=out['score'], classes=out['classes'], count=out['count'])
+
+
+def check_selected_count(count, g):
+    """select_cands' count of one image, read on the host: -1 is the image check_candidate_count refuses (its list may have been
+    cut short at the kernel's capacity); the same error."""
+    if count < 0:
+        cap = min(candidate_slots(g), MAX_CANDIDATES)
+        check_candidate_count(cap, cap, g)

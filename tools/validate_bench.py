@@ -7,7 +7,10 @@
   pass     FaceDetector.validate() against FaceDetector.test() over the same folder of JPEG files (S = 416, the default
            eval_batch_size), alternating, wall ms per pass ending in a device synchronise.
 
-    python tools/validate_bench.py [--rounds R] [--images N] [--alternations A] [--skip-host-above N] [--skip-pass]
+    python tools/validate_bench.py [--rounds R] [--images N] [--alternations A] [--skip-host-above N] [--skip-pass] [--skip-metric]
+                                   [--head single|three_scale]
+
+--head three_scale: the pass with nn_arch.head = three_scale (fv_yolo_decode_nms_batch -> fv_yolo_select_cands in fv_decode_nms' place).
 """
 import argparse
 import json
@@ -95,7 +98,7 @@ def metric_bench(ctx, dev, n_img, rounds, host):
     return r
 
 
-def pass_bench(n_images, alternations):
+def pass_bench(n_images, alternations, head='single'):
     from face_vijnana_yolov3_amd import face_detection
     from face_vijnana_yolov3_amd.face_detection import FaceDetector
     face_detection.DEBUG = False
@@ -104,10 +107,16 @@ def pass_bench(n_images, alternations):
         conf = {'mode': 'test', 'raw_data_path': tmp, 'test_path': tmp, 'output_file_path': os.path.join(tmp, 'solution_fd.csv'),
                 'multi_gpu': False, 'num_gpus': 1, 'yolov3_base_model_load': False, 'model_loading': False,
                 'hps': {'face_conf_th': 0.5, 'nms_iou_th': 0.5, 'num_cands': 60, 'face_region_ratio_th': 0.8, 'validate': True},
-                'nn_arch': {'image_size': S, 'bb_info_c_size': 6}}
+                'nn_arch': {'image_size': S, 'bb_info_c_size': 6, 'head': head}}
         fd = FaceDetector(conf)
-        d = fd.model.layers[-1]
-        fd.model.params[d['beta_off']] = 1.0; fd.model.params[d['beta_off'] + 5] = 1.0      # some cells pass the threshold
+        if head == 'single':
+            d = fd.model.layers[-1]
+            fd.model.params[d['beta_off']] = 1.0; fd.model.params[d['beta_off'] + 5] = 1.0  # some cells pass the threshold
+        else:
+            for d in fd.model.layers:                     # the three detection convs: objectness logits around -2, a few cells fire
+                if not d['has_bn']:
+                    fd.model.params[d['w_off']:d['beta_off']] *= 0.05
+                    fd.model.params[d['beta_off'] + 4:d['beta_off'] + d['cout']:6] = -2.0
         times = {'test': [], 'validate': []}
         fd.test(); fd.validate()                                                           # warm-up of both paths
         for _ in range(alternations):
@@ -116,7 +125,7 @@ def pass_bench(n_images, alternations):
                 out = getattr(fd, name)()
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) * 1e3)
-        return dict(images=n_images, eval_batch_size=face_detection.default_eval_batch(S), test_ms=float(np.median(times['test'])),
+        return dict(head=head, images=n_images, eval_batch_size=face_detection.default_eval_batch(S), test_ms=float(np.median(times['test'])),
                     validate_ms=float(np.median(times['validate'])), n_det=out['n_det'])
 
 
@@ -127,15 +136,19 @@ def main():
     ap.add_argument('--alternations', type=int, default=3)
     ap.add_argument('--skip-host-above', type=int, default=10 ** 9, help='no cal_mAP_sweep run for sets of more images than this')
     ap.add_argument('--skip-pass', action='store_true')
+    ap.add_argument('--skip-metric', action='store_true')
+    ap.add_argument('--head', choices=('single', 'three_scale'), default='single', help='nn_arch.head of the pass measurement')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('validate_bench needs the GPU: there is nothing to measure without one')
     from face_vijnana_yolov3_amd._lib import Context
     ctx = Context(0)
     dev = torch.device('cuda', 0)
-    out = {'metric': [metric_bench(ctx, dev, n, a.rounds, n <= a.skip_host_above) for n in (100, 1000, 10000)]}
+    out = {}
+    if not a.skip_metric:
+        out['metric'] = [metric_bench(ctx, dev, n, a.rounds, n <= a.skip_host_above) for n in (100, 1000, 10000)]
     if not a.skip_pass:
-        out['pass'] = pass_bench(a.images, a.alternations)
+        out['pass'] = pass_bench(a.images, a.alternations, a.head)
     print(json.dumps(out))
 
 
