@@ -193,6 +193,8 @@ def _declare(L):
         'fv_fid_pair_dists': (i32, [vp, vp, i64, ctypes.POINTER(PairBlock), i32, ctypes.POINTER(f32), i32, vp, i64, vp]),
         'fv_fid_mine_negatives': (i32, [vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), i32,
                                         ctypes.POINTER(ctypes.c_int32), i32, f64, i32, vp, vp, vp, vp]),
+        'fv_fid_cluster_workspace_bytes': (sz, [i32]),                    # csrc/fid_cluster.h
+        'fv_fid_cluster': (i32, [vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
         'fv_recon_param_count': (i64, [i32]),
         'fv_recon_workspace_bytes': (sz, [i32, i32]),
         'fv_recon_forward': (i32, [vp, vp, vp, i32, i32, vp, sz, vp]),

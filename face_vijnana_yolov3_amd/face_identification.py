@@ -14,6 +14,8 @@ fi_conf.hps['batch_mining'] ('batch_hard' / 'batch_semi_hard'; likewise opt-in) 
 one tower and forms the triplets inside each batch.
 fi_conf.hps['margin_softmax'] ('cosface' / 'arcface'; likewise opt-in) trains the same batches as a classification over the db's
 subjects, a softmax with an additive margin over a class kernel of its own (fv_fid_cls_train_step).
+fi_conf.hps['cluster'] (likewise opt-in) and the mode 'cluster' group the db's crops with subject_id -1 by DBSCAN over their facial
+IDs on the device (fv_fid_cluster; cluster_unknown, register_clusters).
 fi_conf.multi_gpu / num_gpus (the reference's keras.utils.multi_gpu_model around the triplet model,
 fi.py:303-312, 348-361) trains data-parallel: main() starts num_gpus ranks, each runs fv_fid_train_step_dp on its contiguous slice
 of every triplet batch and parallel.DataParallelTrainer all-reduces the gradients over RCCL while backward runs.
@@ -718,6 +720,87 @@ def fid_match(ctx, queries, registry):
     return idx, dist
 
 
+# ----------------------------------------------------------------------------- clustering of facial IDs
+CLUSTER_MAX_ROWS = 65536         # FV_FID_CLUSTER_MAX_N of csrc/fid_cluster.h
+CLUSTER_MIN_PTS = 3
+CLUSTER_KEYS = ('eps', 'min_pts', 'register')
+
+
+def fid_cluster(ctx, ids, eps, min_pts, workspace=None):
+    """fv_fid_cluster: DBSCAN over ids (n, 64) float32 CUDA tensor under fid_match's distance -> dict of CUDA tensors: labels, via,
+    n_nbr (n,) int32, core (n,) uint8, n_clusters (1,) int32 (csrc/fid_cluster.h defines them).  Stream-ordered, no copy back.
+    workspace: a CUDA tensor of at least fv_fid_cluster_workspace_bytes(n) bytes (its contents are ignored); None: one kept on the
+    context and grown to the largest call so far."""
+    if ids.dtype != torch.float32 or ids.dim() != 2 or ids.shape[1] != DENSE1_DIM:
+        raise ValueError('fid_cluster expects float32 (n, 64) ids')
+    x = ids.contiguous()
+    n, dev = int(x.shape[0]), x.device
+    out = dict(labels=torch.empty(n, dtype=torch.int32, device=dev), via=torch.empty(n, dtype=torch.int32, device=dev),
+               n_nbr=torch.empty(n, dtype=torch.int32, device=dev), core=torch.empty(n, dtype=torch.uint8, device=dev),
+               n_clusters=torch.zeros(1, dtype=torch.int32, device=dev))
+    if n == 0:
+        return out
+    need = int(lib().fv_fid_cluster_workspace_bytes(n))
+    if need == 0:
+        raise ValueError('fid_cluster takes 1..%d rows, got %d' % (CLUSTER_MAX_ROWS, n))
+    if workspace is None:
+        workspace = getattr(ctx, '_fid_cluster_ws', None)
+        if workspace is None or workspace.numel() < need or workspace.device != dev:
+            ctx._fid_cluster_ws = None
+            workspace = ctx._fid_cluster_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError('fid_cluster: the workspace holds %d bytes, %d rows need %d'
+                         % (workspace.numel() * workspace.element_size(), n, need))
+    ctx.check(lib().fv_fid_cluster(ctx.handle, ptr(x), n, float(eps), int(min_pts), ptr(workspace), ptr(out['labels']),
+                                   ptr(out['via']), ptr(out['n_nbr']), ptr(out['core']), ptr(out['n_clusters'])), 'fv_fid_cluster')
+    return out
+
+
+def cluster_conf(hps):
+    """hps['cluster'] -> None (absent, None or false: off) or dict(eps, min_pts, register): true takes the defaults, an object may
+    carry eps (a finite number >= 0, default hps['sim_th']: a face within sim_th of a registered ID is that subject, so two faces
+    within it are one person), min_pts (an int >= 1, default 3) and register (a bool, default false).  ValueError for an unknown
+    key, a bool where a number is expected or a value out of range.  Needs no device."""
+    c = hps.get('cluster')
+    if c is None or c is False:
+        return None
+    if c is True:
+        c = {}
+    if not isinstance(c, dict):
+        raise ValueError('fi_conf.hps.cluster must be true, false or an object with the keys %s, got %r' % (', '.join(CLUSTER_KEYS), c))
+    unknown = sorted(set(c) - set(CLUSTER_KEYS))
+    if unknown:
+        raise ValueError('fi_conf.hps.cluster: unknown key %s (available: %s)' % (', '.join(map(repr, unknown)), ', '.join(CLUSTER_KEYS)))
+    eps = c.get('eps', hps.get('sim_th'))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(eps) or eps < 0:
+        raise ValueError('fi_conf.hps.cluster.eps (default: hps.sim_th) must be a finite number >= 0, got %r' % (eps,))
+    min_pts = c.get('min_pts', CLUSTER_MIN_PTS)
+    if isinstance(min_pts, bool) or not isinstance(min_pts, (int, np.integer)) or min_pts < 1:
+        raise ValueError('fi_conf.hps.cluster.min_pts must be an int >= 1, got %r' % (min_pts,))
+    register = c.get('register', False)
+    if not isinstance(register, bool):
+        raise ValueError('fi_conf.hps.cluster.register must be true or false, got %r' % (register,))
+    return dict(eps=float(eps), min_pts=int(min_pts), register=register)
+
+
+def cluster_files(resource_type):
+    """The csv cluster_unknown writes for a resource type."""
+    if resource_type == RESOURCE_TYPE_UCCS:
+        return 'subject_clusters.csv'
+    if resource_type == RESOURCE_TYPE_VGGFACE2:
+        return 'subject_clusters_vggface2.csv'
+    raise ValueError('resource type is not valid.')
+
+
+def cluster_csv_text(names, labels, core, n_nbr, via):
+    """subject_clusters.csv: one row per unlabelled face in db order; via_face_file is the face itself for a core row, the
+    claiming core face for a border row and empty for noise."""
+    rows = ['face_file,cluster,core,n_neighbours,via_face_file\n']
+    for k, name in enumerate(names):
+        rows.append('%s,%d,%d,%d,%s\n' % (name, int(labels[k]), int(core[k]), int(n_nbr[k]), names[int(via[k])] if via[k] >= 0 else ''))
+    return ''.join(rows)
+
+
 PAIR_TRIANGLE, PAIR_RECTANGLE = 0, 1     # fv_pair_block.kind
 
 
@@ -1362,6 +1445,7 @@ class FaceIdentifier(object):
         self.last_batch_mining = None
         self.margin_softmax = margin_softmax_conf(self.hps, self.image_size)   # likewise
         self.last_margin_softmax = None
+        self.cluster = cluster_conf(self.hps)                                  # likewise
         if self.margin_softmax is not None:
             self._check_db_classes()
         if device is None:           # FV_DEVICE: several ranks on ONE device, to rehearse N > 1 on a one-GPU box (gloo transport)
@@ -1694,7 +1778,6 @@ class FaceIdentifier(object):
         image's ID does not depend on the rest of its batch (fv_fid_extract), so this equals the reference's one predict per
         subject."""
         import pandas as pd
-        from .engine import Engine
         db_file, faces_dir, _h5, _pk = db_files(self.conf['resource_type'])
         db = pd.read_csv(db_file).iloc[:, 1:]
         names, sids = [], []
@@ -1703,18 +1786,21 @@ class FaceIdentifier(object):
                 continue
             for ff in list(df.iloc[:, 1]):
                 names.append(ff); sids.append(subject_id)
-        step = max(1, Engine.max_infer_batch(self.image_size))
-        paths = [os.path.join(self.raw_data_path, faces_dir, ff) for ff in names]
-        ids = []
-        if self.hps.get('crop_store', CROP_STORE_DEFAULT) and names:
-            ids = [d.cpu().numpy() for d in self._extract_from_store(paths, step)]
-        else:
-            for i in range(0, len(names), step):
-                x = np.asarray([_imread(f) for f in paths[i:i + step]])
-                ids.append(self.fid_extractor.predict(x))
+        ids = [d.cpu().numpy() for d in self._extract_faces(faces_dir, names)]
         ids = np.concatenate(ids) if ids else np.zeros((0, DENSE1_DIM), np.float32)
         self._db_cache = (names, sids, ids)
         return names, sids, ids
+
+    def _extract_faces(self, faces_dir, names):
+        """Facial IDs of the crop files `names` of faces_dir, in that order -> device tensors, one per chunk of at most
+        Engine.max_infer_batch(S) crops: through the crop store when hps['crop_store'] is on, decoded on the host otherwise."""
+        from .engine import Engine
+        step = max(1, Engine.max_infer_batch(self.image_size))
+        paths = [os.path.join(self.raw_data_path, faces_dir, ff) for ff in names]
+        if self.hps.get('crop_store', CROP_STORE_DEFAULT) and names:
+            return self._extract_from_store(paths, step)
+        return [self.fid_extractor.predict_device(np.asarray([_imread(f) for f in paths[i:i + step]]))
+                for i in range(0, len(names), step)]
 
     def _extract_from_store(self, paths, step):
         """Facial IDs (device tensors, one per chunk of at most `step` crops) of the crop files `paths` through a CropStore:
@@ -1760,6 +1846,65 @@ class FaceIdentifier(object):
         db = {sid: subject_mean(np.asarray(reg[sid])) for sid in order}
         with open(db_files(self.conf['resource_type'])[3], 'wb') as f:
             pickle.dump(db, f)
+
+    # ------------------------------------------------------------------ unlabelled faces
+    def cluster_unknown(self, eps=None, min_pts=None):
+        """Group the faces nobody labelled: every crop of the subject db with subject_id -1, in db order, goes through the
+        extractor (the path _extract_db takes) and fv_fid_cluster (eps, min_pts: hps['cluster']'s, or its defaults -- sim_th and
+        3 -- where the key is off), with one copy back.  Writes subject_clusters.csv (vggface2: subject_clusters_vggface2.csv;
+        cluster_csv_text) and returns dict(names, ids, labels, core, n_nbr, via, n_clusters): lists and NumPy arrays.  A db
+        without such crops writes the header alone."""
+        import pandas as pd
+        conf = self.cluster if self.cluster is not None else cluster_conf(dict(self.hps, cluster=True))
+        eps = conf['eps'] if eps is None else eps
+        min_pts = conf['min_pts'] if min_pts is None else min_pts
+        resource_type = self.conf['resource_type']
+        db_file, faces_dir, _h5, _pk = db_files(resource_type)
+        db = pd.read_csv(db_file).iloc[:, 1:]
+        names = [str(ff) for ff in db.iloc[:, 1][db['subject_id'] == -1]]
+        m = self.model
+        if len(names) > CLUSTER_MAX_ROWS:
+            raise ValueError('cluster_unknown: the db holds %d crops with subject_id -1, one fv_fid_cluster call takes %d'
+                             % (len(names), CLUSTER_MAX_ROWS))
+        chunks = self._extract_faces(faces_dir, names)
+        ids = torch.cat(chunks) if chunks else torch.zeros((0, DENSE1_DIM), dtype=torch.float32, device=m.dev)
+        out = fid_cluster(m.ctx, ids, eps, min_pts)
+        # one copy back: the IDs and the five outputs as bytes of one buffer
+        parts = [ids, out['labels'], out['via'], out['n_nbr'], out['n_clusters'], out['core']]
+        host = torch.cat([t.contiguous().view(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        cut = np.cumsum([0] + [t.numel() * t.element_size() for t in parts])
+        ids_h, labels, via, n_nbr, n_clusters, core = [host[a:b].view(dt).copy() for a, b, dt in zip(
+            cut[:-1], cut[1:], (np.float32, np.int32, np.int32, np.int32, np.int32, np.uint8))]
+        with open(cluster_files(resource_type), 'w') as f:
+            f.write(cluster_csv_text(names, labels, core, n_nbr, via))
+        return dict(names=names, ids=ids_h.reshape(-1, DENSE1_DIM), labels=labels, core=core, n_nbr=n_nbr, via=via,
+                    n_clusters=int(n_clusters[0]))
+
+    def register_clusters(self, result, first_id=None):
+        """One new subject per cluster of cluster_unknown's result, appended to the registry pickle register_facial_ids writes
+        (an absent file is an empty registry): cluster c becomes subject first_id + c (first_id: 1 + the largest registered id, 0
+        for an empty registry) with subject_mean of its members' facial IDs.  Existing entries and their order are kept.
+        ValueError, before the file is written, when a new id is registered already.  -> the new ids."""
+        path = db_files(self.conf['resource_type'])[3]
+        db = {}
+        if os.path.exists(path):
+            with open(path, 'rb') as f:
+                db = pickle.load(f)
+        C = int(result['n_clusters'])
+        if first_id is None:
+            first_id = 1 + max(int(k) for k in db) if db else 0
+        new_ids = [int(first_id) + c for c in range(C)]
+        taken = sorted(set(new_ids) & set(int(k) for k in db))
+        if taken:
+            raise ValueError('register_clusters: subject id %s is registered already (first_id %d, %d clusters)'
+                             % (', '.join(map(str, taken)), int(first_id), C))
+        labels, ids = np.asarray(result['labels']), np.asarray(result['ids'])
+        out = dict(db)
+        for c, sid in enumerate(new_ids):
+            out[sid] = subject_mean(ids[labels == c])
+        with open(path, 'wb') as f:
+            pickle.dump(out, f)
+        return new_ids
 
     # ------------------------------------------------------------------ evaluate / test (fi.py:772-992, 994-1153)
     def _identify_files(self, on_batch):
@@ -1920,14 +2065,16 @@ def main():
               alone builds the database (the others return after train());
       fid_db  make_facial_ids_db, then register_facial_ids -- the reference leaves the second call commented out, but nothing else
               would register the IDs of a loaded model, and test() reads the registry;
-      test    test() -> output_file_path.
+      test    test() -> output_file_path;
+      cluster cluster_unknown() -> subject_clusters.csv: the db's crops with subject_id -1 grouped by fv_fid_cluster (not in the
+              reference), then register_clusters() when hps.cluster.register is true.
     'evaluate' is not implemented here; the other modes ignore multi_gpu."""
     name = 'face_vijnana_yolov3_win.json' if platform.system() == 'Windows' else 'face_vijnana_yolov3.json'
     with open(name, 'r') as f:
         conf = json.load(f)
     mode = conf['fi_conf']['mode']
-    if mode not in ('data', 'train', 'fid_db', 'test'):
-        raise NotImplementedError('fi_conf.mode %r is not implemented (available: data, train, fid_db, test)' % mode)
+    if mode not in ('data', 'train', 'fid_db', 'test', 'cluster'):
+        raise NotImplementedError('fi_conf.mode %r is not implemented (available: data, train, fid_db, test, cluster)' % mode)
     if mode == 'data':                     # needs no model
         resource_type = conf['fi_conf'].get('resource_type')
         if resource_type not in (RESOURCE_TYPE_UCCS, RESOURCE_TYPE_VGGFACE2):
@@ -1956,6 +2103,10 @@ def main():
     elif mode == 'fid_db':
         fi.make_facial_ids_db()
         fi.register_facial_ids()
+    elif mode == 'cluster':
+        result = fi.cluster_unknown()
+        if fi.cluster is not None and fi.cluster['register']:
+            fi.register_clusters(result)
     else:
         fi.test()
     print('Elasped time: {0:f}s'.format(time.time() - ts))
